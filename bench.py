@@ -2,8 +2,16 @@
 """bench.py -- the headline metric of BASELINE.json on MI355X:
 grid-points x timesteps / sec of the batched Douglas ADI sweep (512x256 grid, 1000 time steps by default).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--instances I]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|c5] [--instances I] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the headline line (metric, value, ms_per_step, ...).  --full adds
+everything else below (price check, roofline, batch sweep, single instance, the other workloads, the reference harness
+shape, the CPU baseline), each measured outside the timed region as before.  --dump-outputs DIR writes what the timed path
+returned in its last step as DIR/<name>.npy (rank 0's shard): U of the sweep workloads (c2 / c3 / c5), the Jacobian, base
+and trial prices of c4.  An array over the 48 MiB budget is written as a fixed, seeded sample of its elements
+(<name>_sample.npy, the same indices on every run).  Inputs depend on the arguments only, so two builds can be compared
+output for output.
 
 A "step" is one pass of the hot path over one batch, inputs already resident in HBM, including operator setup, layout
 pack/unpack and all time steps.  Workloads (BASELINE.json configs 2..5):
@@ -17,7 +25,7 @@ Instances are sharded across ranks with no data-path collective (scaling: weak; 
 Collectives of the timed region (barrier, MAX of the elapsed time, c4's LM all-reduce) run over RCCL; if RCCL cannot
 come up on every rank the run exits non-zero unless --allow-gloo is given (rehearsals on a box without one GPU per rank).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full only):
   roofline      dominant kernel = the row pass.  achieved = algorithmic bytes per launch / mean launch duration against
                 the 8 TB/s HBM peak; the mean launch duration comes from HIP events on the library's own stream: the
                 time-loop events of the TIMED steps (hadi_get_timing().sweep_ms) split between the two kernels by the
@@ -52,6 +60,39 @@ WORKLOADS = {
     "c5": (1024, 512, 2000, 64, 8.0, 8.0),
     "c4": (50, 25, 0, 500, 16.0, 16.0),
 }
+
+DUMP_BYTES = 48 << 20        # --dump-outputs: budget of all arrays together
+DUMP_SEED = 20240601         # --dump-outputs: the sample of an array over the budget
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: `arrays` = [(name, float64 tensor)], smallest first, written as outdir/<name>.npy.  An array that does
+    not fit what is left of DUMP_BYTES is written as a seeded sample of its flattened elements (outdir/<name>_sample.npy,
+    indices ascending; they depend only on the array's size)."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    left = DUMP_BYTES
+    for name, x in arrays:
+        cap = max(0, left - 4096) // x.element_size()
+        if x.numel() > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(x.numel(), cap, replace=False))
+            x, name = x.reshape(-1)[torch.from_numpy(idx).to(x.device)], name + "_sample"
+        a = x.detach().cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.nbytes
+
+
+def use_built_library():
+    """libhadi.so as build() left it.  The benchmark may run as another user than the one who built the tree and cannot count
+    on writing into it, so an up-to-date library is used as it is: no build lock, no compiler, nothing written.  Only a
+    missing or out-of-date one is built here.  Neither torch nor the library is loaded (the launcher of spawn_ranks calls
+    this too); `nm -D` checks the exports against include/hadi.h.  The CPU oracle serves --full alone and builds itself there."""
+    import __graft_entry__ as G
+    srcs = [os.path.join(G.CSRC, f) for f in os.listdir(G.CSRC)] + [os.path.join(G.ROOT, "include", "hadi.h")]
+    if G._newer(G.LIB, srcs):
+        G.build_libhadi()
+    G.check_exports()
 
 
 def init_distributed(args, torch, dev_index):
@@ -116,17 +157,14 @@ def spawn_ranks(args, argv):
     itself -- one process per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment, rendezvous on
     127.0.0.1 -- relays rank 0's JSON line and exits non-zero if any rank failed (the same contract as `python -m
     torch.distributed.run --nproc-per-node N bench.py --gpus N`).  The launcher itself never imports torch and never maps
-    libhadi.so (a HIP fat binary): it compiles the artefacts (hipcc / gcc need no GPU) and checks the exports with `nm -D`
-    against include/hadi.h.  All ranks are supervised: the first rank that exits non-zero ends its siblings (a rank left
+    libhadi.so (a HIP fat binary): it builds libhadi.so only if it is missing or out of date (hipcc needs no GPU) and checks
+    the exports with `nm -D` against include/hadi.h.  All ranks are supervised: the first rank that exits non-zero ends its siblings (a rank left
     alone in the rendezvous would sit there until the backend's time-out, holding the GPU lease), and the whole run has an
     upper bound (--spawn-timeout)."""
     import socket
     import subprocess
     import threading
-    import __graft_entry__ as G
-    G.build_libhadi()   # once, here: the ranks then find the artefacts up to date
-    G.build_oracle()
-    G.check_exports()
+    use_built_library()   # once, here: the ranks then find it up to date
     with socket.socket() as sock:
         sock.setsockopt(socket.SOL_SOCKET, socket.SO_REUSEADDR, 1)
         sock.bind(("127.0.0.1", 0))
@@ -196,9 +234,16 @@ def main():
     ap.add_argument("--spawn-timeout", type=int, default=1500, help="--gpus N without a launcher: upper bound of the whole run in seconds")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal only: every rank uses GPU 0 (a 1-GPU box cannot host one GPU per rank)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline figure (price check, roofline, batch sweep, single "
+                         "instance, other workloads, reference harness shape, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (rank 0's shard)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             spawn_ranks(args, sys.argv[1:])  # does not return
@@ -210,8 +255,7 @@ def main():
 
     import numpy as np
     import torch
-    import __graft_entry__ as G
-    G.build()
+    use_built_library()
     import pde_based_heston_solver_gpu_accelerated_amd as H
 
     wl = args.workload
@@ -332,6 +376,7 @@ def main():
             solver.wait_stream()
             err = comm.allreduce_sum(np.array([float(((market - trial) ** 2).sum().item())]))
             holder["price"], holder["err"] = float(base[0].item()), float(err[0])
+            holder["outputs"] = [("base_prices", base), ("trial_prices", trial), ("jacobian", J)]
         units = 7.0 * cm * sum(p.time_steps for p in pts_all)   # 6 Jacobian solves + 1 trial solve per option
         return step, units, holder, ks
 
@@ -376,6 +421,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX, group=group)
         elapsed = float(tt.item())
     value = units_step * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state_holder["outputs"] if wl == "c4" else [("U", case.U)])
 
     def timed_pass(fn, reps=2):
         """one warm-up, then the best wall time of `reps` passes (synchronised on both sides), with that pass's sweep_ms"""
@@ -395,15 +442,15 @@ def main():
     if rank == 0:
         info = solver.device_info()
         roofline, single, sweep_obj, price_check, cpu, others, harness = None, None, None, None, None, None, None
-        extras = n_gpus == 1 and not args.skip_single
-        if wl != "c4":
+        extras = args.full and n_gpus == 1 and not args.skip_single
+        if args.full and wl != "c4":
             # price sanity inside the bench: the instance nearest K = 100
             k_mid = min(range(n_loc), key=lambda k: abs(strikes[k] - 100.0))
             price_check = {"strike": strikes[k_mid], "price": case.price(k_mid)}
             # ---- roofline of the dominant kernel, one extra profiled pass outside the timed region -----
             roofline = case.roofline(sweep_ms / max(1, args.steps) / N)  # time-loop events of the timed steps (incl. the rare dividend launches)
             roofline["sweep"]["sweep_ms"] = round(sweep_ms / max(1, args.steps), 3)
-        else:
+        elif args.full:
             path = solver.describe_last_sweep()
             roofline = {"bound": "hbm", "kernel": path, "achieved": round(value * 32.0 / 1e9 / n_gpus, 1), "peak": HBM_PEAK_GBS,
                         "unit": "GB/s", "frac": round(value * 32.0 / 1e9 / n_gpus / HBM_PEAK_GBS, 4), "traffic": None,
@@ -508,7 +555,7 @@ def main():
                                  "the fp32 state does not guarantee a 1e-6 price tolerance"}
 
         # ---- CPU baseline: the oracle (port of the reference algorithm) on the host cores ------------
-        if n_gpus == 1 and not args.no_cpu_baseline and wl != "c4":
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline and wl != "c4":
             from oracle import oracle as O
             cores = O.max_threads()
             n_cpu = max(1, min(cores, 64, n_glob))
@@ -547,16 +594,19 @@ def main():
                        "timing_collective": collective},
             "effective_GBps": value * B_STEP / 1e9,
             "sweep_only_point_steps_per_s": (units_step / n_gpus) * args.steps / (sweep_ms * 1e-3) if wl != "c4" else None,
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "batch_sweep": sweep_obj,
-            "single_instance": single,
-            "other_workloads": others,
-            "reference_harness": harness,
-            "fp32_state_error": state_err, "two_streams": two_streams,
-            "price_check": price_check,
             "device": info,
         }
+        if args.full:
+            out.update({
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+                "batch_sweep": sweep_obj,
+                "single_instance": single,
+                "other_workloads": others,
+                "reference_harness": harness,
+                "fp32_state_error": state_err, "two_streams": two_streams,
+                "price_check": price_check,
+            })
     if dist is not None:
         barrier()
         dist.destroy_process_group()

@@ -41,12 +41,17 @@ class _Dump(C.Structure):
 def build(force=False):
     """Compile the oracle with gcc (oracle/Makefile)."""
     import fcntl
+    srcs = [os.path.join(_HERE, f) for f in ("heston_oracle.c", "heston_oracle.h", "heston_oracle_xp.c", "Makefile")]
+    newest = max(os.path.getmtime(f) for f in srcs)
+
+    def stale():
+        return force or any(not os.path.exists(l) or os.path.getmtime(l) < newest for l in (_LIB_PATH, _LIB_XP_PATH))
+    if not stale():
+        return _LIB_PATH  # up to date: no lock taken, nothing written (the tree may belong to the user who built it)
     fd = os.open(os.path.join(_HERE, ".build.lock"), os.O_CREAT | os.O_RDWR, 0o644)
     try:  # several test ranks may get here at once
         fcntl.flock(fd, fcntl.LOCK_EX)
-        srcs = [os.path.join(_HERE, f) for f in ("heston_oracle.c", "heston_oracle.h", "heston_oracle_xp.c", "Makefile")]
-        newest = max(os.path.getmtime(f) for f in srcs)
-        if force or any(not os.path.exists(l) or os.path.getmtime(l) < newest for l in (_LIB_PATH, _LIB_XP_PATH)):
+        if stale():
             subprocess.check_call(["make", "-C", _HERE, "-s"])
     finally:
         fcntl.flock(fd, fcntl.LOCK_UN)

@@ -88,7 +88,7 @@ if "--reps" in argv:
 for name, lib in [(n, l) for n in (argv or ["c2"]) for _ in range(reps) for l in libs]:
     head = [sys.executable, os.path.join(ROOT, "bench.py")] if lib in (None, "head") else \
            [sys.executable, os.path.join(ROOT, "tools", "bench_variant.py"), os.path.join(ROOT, lib)]
-    out = subprocess.run(head + ["--steps", "2", "--warmup", "1", "--skip-single", "--no-cpu-baseline"] + CASES[name],
+    out = subprocess.run(head + ["--full", "--steps", "2", "--warmup", "1", "--skip-single", "--no-cpu-baseline"] + CASES[name],
                          capture_output=True, text=True)
     name = name if lib in (None,) else "%s[%s]" % (name, os.path.basename(lib).replace("_var_", "").replace(".so", ""))
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -1,7 +1,8 @@
 #!/bin/bash
-# run the bench for a while and sample clocks / power
+# run the bench for a while and sample clocks / power:   bash tools/smi_probe.sh [outdir]   (default: a new temporary directory)
 cd $GRAFT_REPO_ROOT
-timeout -k 10 200 python bench.py --steps 40 --warmup 1 --no-cpu-baseline --skip-single > gpurun_out/bw.json 2>gpurun_out/bw.err &
+OUT=${1:-$(mktemp -d)}; mkdir -p "$OUT"
+timeout -k 10 200 python bench.py --full --steps 40 --warmup 1 --no-cpu-baseline --skip-single > "$OUT/bw.json" 2>"$OUT/bw.err" &
 BP=$!
 sleep 6
 for i in 1 2 3 4 5 6; do
@@ -10,6 +11,6 @@ for i in 1 2 3 4 5 6; do
 done
 wait $BP
 python -c "
-import json; d=json.loads(open('gpurun_out/bw.json').read().strip().splitlines()[-1]); print('%.4g'%d['value'], d['roofline']['avg_launch_ms'], d['roofline']['pass_b']['avg_launch_ms'])"
+import json; d=json.loads(open('$OUT/bw.json').read().strip().splitlines()[-1]); print('%.4g'%d['value'], d['roofline']['avg_launch_ms'], d['roofline']['pass_b']['avg_launch_ms'])"
 echo idle:
 rocm-smi --showclocks --showpower 2>/dev/null | grep -E "sclk|mclk|Power" | tr '\n' ';'; echo
