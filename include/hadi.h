@@ -68,8 +68,12 @@ enum hadi_variant { HADI_EU = 0, HADI_AM = 1, HADI_DIV = 2, HADI_AM_DIV = 3 };
 enum hadi_memspace { HADI_MEM_HOST = 0, HADI_MEM_DEVICE = 1 };
 /* Splitting scheme.  The reference's device path is Douglas only (src/device_solver.hpp:194-266); Craig-Sneyd
  * exists in its host family (CS_scheme_shuffled, src/solver.hpp:781-907, European) and is offered here on the
- * device for the European variant. */
-enum hadi_scheme { HADI_SCHEME_DOUGLAS = 0, HADI_SCHEME_CRAIG_SNEYD = 1 };
+ * device for the European variant.  Modified Craig-Sneyd and Hundsdorfer-Verwer (in 't Hout & Foulon) are second order
+ * for every theta (Douglas is first order with the mixed-derivative term); the usual choices are theta = 1/3 for MCS and
+ * theta = 1/2 + sqrt(3)/6 for HV.  MCS at theta = 1/2 is Craig-Sneyd.  All three predictor-corrector schemes: European
+ * variant, call boundary data, fp64 state, m1 <= 1024 and m2 <= 527 (HADI_ERR_UNSUPPORTED otherwise); MCS and HV also
+ * need theta > 0. */
+enum hadi_scheme { HADI_SCHEME_DOUGLAS = 0, HADI_SCHEME_CRAIG_SNEYD = 1, HADI_SCHEME_MCS = 2, HADI_SCHEME_HV = 3 };
 /* Precision of the state arrays BETWEEN the two directional passes.  FP64 is what the reference computes in.  FP32
  * ("mixed-precision fp32 ADI sweep with fp64 tridiag pivots", BASELINE.json config 5): U and the A2 right-hand side are
  * stored as fp32 in HBM (half the traffic: 16 B per point-step), every operator, pivot and line solve is still

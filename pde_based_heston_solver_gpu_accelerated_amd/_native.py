@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libhadi.so")
 HADI_OK = 0
 EU, AM, DIV, AM_DIV = 0, 1, 2, 3
 MEM_HOST, MEM_DEVICE = 0, 1
-SCHEME_DOUGLAS, SCHEME_CRAIG_SNEYD = 0, 1
+SCHEME_DOUGLAS, SCHEME_CRAIG_SNEYD, SCHEME_MCS, SCHEME_HV = 0, 1, 2, 3
 STATE_FP64, STATE_FP32 = 0, 1
 CALL, PUT = 0, 1
 

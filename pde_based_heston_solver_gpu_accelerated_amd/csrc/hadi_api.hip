@@ -266,8 +266,32 @@ hipError_t raise_pass_a() {
     if (e == hipSuccess) e = raise_lds_limit(hadi_pass_a<B, G, 4, NG, PD, false, 2>);
     return e != hipSuccess ? e : raise_lds_limit(hadi_pass_a<B, G, 4, NG, PD, true>);
 }
+template <int B, int G, int NG, int PD, int SCH>
+hipError_t raise_pass_a_sch() {
+    hipError_t e = raise_lds_limit(hadi_pass_a_sch<B, G, 4, NG, PD, 1, SCH>);
+    return e != hipSuccess ? e : raise_lds_limit(hadi_pass_a_sch<B, G, 4, NG, PD, 2, SCH>);
+}
+// the Modified Craig-Sneyd / Hundsdorfer-Verwer row passes of one scheme (shared ring and strips)
+template <int SCH>
+hipError_t raise_sch_lds_limits() {
+    hipError_t e;
+    if ((e = raise_pass_a_sch<1, 1, 1, 2, SCH>()) != hipSuccess) return e;
+    if ((e = raise_pass_a_sch<2, 1, 1, 2, SCH>()) != hipSuccess) return e;
+    if ((e = raise_pass_a_sch<4, 1, 1, 2, SCH>()) != hipSuccess) return e;
+    if ((e = raise_pass_a_sch<8, 1, 1, 1, SCH>()) != hipSuccess) return e;
+    if ((e = raise_pass_a_sch<8, 2, 1, 1, SCH>()) != hipSuccess) return e;
+    if ((e = raise_lds_limit(hadi_pass_a_strip_sch<8, 1, 1, SCH>)) != hipSuccess) return e;
+    if ((e = raise_lds_limit(hadi_pass_a_strip_sch<8, 1, 2, SCH>)) != hipSuccess) return e;
+    if ((e = raise_lds_limit(hadi_pass_a_strip_sch<4, 1, 1, SCH>)) != hipSuccess) return e;
+    if ((e = raise_lds_limit(hadi_pass_a_strip_sch<4, 1, 2, SCH>)) != hipSuccess) return e;
+    if ((e = raise_lds_limit(hadi_pass_a_strip_sch<2, 1, 1, SCH>)) != hipSuccess) return e;
+    if ((e = raise_lds_limit(hadi_pass_a_strip_sch<2, 1, 2, SCH>)) != hipSuccess) return e;
+    return raise_lds_limit(hadi_pass_a_strip_sch<8, 2, 2, SCH>);
+}
 hipError_t raise_all_lds_limits() {
     hipError_t e;
+    if ((e = raise_sch_lds_limits<HADI_SCH_MCS>()) != hipSuccess) return e;
+    if ((e = raise_sch_lds_limits<HADI_SCH_HV>()) != hipSuccess) return e;
     if ((e = raise_pass_a<1, 1, 1, 2>()) != hipSuccess) return e;
     if ((e = raise_pass_a<2, 1, 1, 2>()) != hipSuccess) return e;
     if ((e = raise_pass_a<4, 1, 1, 2>()) != hipSuccess) return e;
@@ -430,9 +454,44 @@ struct PassEnv {
     bool american, amp, xstep, f32;  // amp: P representation; xstep: this step runs on the explicit (U, lambda_bar) pair
     int col_prefetch;
     int cs_strips;                   // Craig-Sneyd row passes on strips where the plan chose strips (tuning key "cs_strips", default on)
+    int scheme;                      // enum hadi_scheme: which predictor / corrector kernels modes 1 / 2 run
 };
-// Row pass of one time step.  mode: 0 Douglas, 1 / 2 Craig-Sneyd predictor / corrector.
+template <int B, int G, int NG, int PD, int SCH>
+void launch_pass_a_sch(const HadiPlan &pl, const HadiSweepArgs &a, int n, hipStream_t s, int mode) {
+    if (mode == 1) hipLaunchKernelGGL((hadi_pass_a_sch<B, G, 4, NG, PD, 1, SCH>), dim3(pl.grid_a), dim3(64 * pl.W * G * NG), pl.smem_a, s, a, n);
+    else hipLaunchKernelGGL((hadi_pass_a_sch<B, G, 4, NG, PD, 2, SCH>), dim3(pl.grid_a), dim3(64 * pl.W * G * NG), pl.smem_a, s, a, n);
+}
+template <int B, int G, int SCH>
+void launch_strip_sch(const HadiPlan &pl, const HadiSweepArgs &a, int n, hipStream_t s, int mode) {
+    const dim3 g(pl.grid_as), b(64 * HADI_STRIP_WAVES(B));
+    if (mode == 1) hipLaunchKernelGGL((hadi_pass_a_strip_sch<B, G, 1, SCH>), g, b, pl.smem_as, s, a, n);
+    else hipLaunchKernelGGL((hadi_pass_a_strip_sch<B, G, 2, SCH>), g, b, pl.smem_as, s, a, n);
+}
+// Predictor (mode 1) / corrector (mode 2) row pass of a Modified Craig-Sneyd or Hundsdorfer-Verwer step: the same choice of
+// strips or shared ring as for Craig-Sneyd (launch_row_pass), on the kernels of the scheme.
+template <int SCH>
+void launch_row_pass_sch(const PassEnv &e, const HadiSweepArgs &ar, int mode) {
+    const HadiPlan &pl = e.pl; const HadiLayout &L = e.L; const int nstep = e.nstep; hipStream_t q = e.q;
+    // (paired strips: the corrector only -- the predictor of those shapes runs on the shared ring, see hadi_pass_a_strip_sch)
+    if (pl.use_strip && !pl.use_pairs && (e.cs_strips == 1 || e.cs_strips == 1 + mode) && !(L.G == 2 && mode == 1)) {
+        if (L.G == 2) hipLaunchKernelGGL((hadi_pass_a_strip_sch<8, 2, 2, SCH>), dim3(pl.grid_as), dim3(64 * HADI_STRIP_WAVES(8)), pl.smem_as, q, ar, nstep);
+        else if (L.B == 8) launch_strip_sch<8, 1, SCH>(pl, ar, nstep, q, mode);
+        else if (L.B == 4) launch_strip_sch<4, 1, SCH>(pl, ar, nstep, q, mode);
+        else launch_strip_sch<2, 1, SCH>(pl, ar, nstep, q, mode);
+        return;
+    }
+    switch (L.B * 10 + L.G) {
+        case 11: launch_pass_a_sch<1, 1, 1, 2, SCH>(pl, ar, nstep, q, mode); break;
+        case 21: launch_pass_a_sch<2, 1, 1, 2, SCH>(pl, ar, nstep, q, mode); break;
+        case 41: launch_pass_a_sch<4, 1, 1, 2, SCH>(pl, ar, nstep, q, mode); break;
+        case 81: launch_pass_a_sch<8, 1, 1, 1, SCH>(pl, ar, nstep, q, mode); break;
+        default: launch_pass_a_sch<8, 2, 1, 1, SCH>(pl, ar, nstep, q, mode); break;
+    }
+}
+// Row pass of one time step.  mode: 0 Douglas, 1 / 2 predictor / corrector of the scheme e.scheme (Craig-Sneyd, MCS, HV).
 void launch_row_pass(const PassEnv &e, const HadiSweepArgs &ar, int mode) {
+    if (mode != 0 && e.scheme == HADI_SCHEME_MCS) return launch_row_pass_sch<HADI_SCH_MCS>(e, ar, mode);
+    if (mode != 0 && e.scheme == HADI_SCHEME_HV) return launch_row_pass_sch<HADI_SCH_HV>(e, ar, mode);
     const HadiPlan &pl = e.pl; const HadiLayout &L = e.L; const int nsb = e.nsb, nstep = e.nstep; hipStream_t q = e.q;
     const bool american = e.american, amp = e.amp, xstep = e.xstep, f32 = e.f32;
     if (pl.row_seq) {  // more than 1024 s-intervals: one lane per v-row, sequential along s
@@ -570,27 +629,32 @@ void launch_col_pass(const PassEnv &e, const HadiSweepArgs &ar) {
 }
 
 // ---- run_sweep, part 3: the kernels of the streaming path in words (hadi_describe_last_sweep) ------------------------
-std::string describe_streaming_path(const Ctx *c, const HadiPlan &pl, const BatchPlan &bp, bool american, bool amp, bool cs, bool f32) {
+std::string describe_streaming_path(const Ctx *c, const HadiPlan &pl, const BatchPlan &bp, bool american, bool amp, int scheme, bool f32) {
+    const bool cs = scheme != HADI_SCHEME_DOUGLAS;
+    const char *sch = scheme == HADI_SCHEME_MCS ? "MCS" : scheme == HADI_SCHEME_HV ? "HV" : "CS";
+    const char *strip_k = scheme == HADI_SCHEME_CRAIG_SNEYD ? "hadi_pass_a_strip" : "hadi_pass_a_strip_sch";
+    const char *ring_k = scheme == HADI_SCHEME_MCS || scheme == HADI_SCHEME_HV ? "hadi_pass_a_sch" : "hadi_pass_a";
     const HadiLayout &L = pl.L;
     const std::vector<SubBatch> &subs = bp.subs;
     const int nsub = (int)subs.size();
     const bool two_streams = bp.two_streams;
     const int fork_before = bp.fork_before;
     std::string last_path;
-    char buf[256];
-    char rowk[96];
+    char buf[384];
+    char rowk[160];
     if (amp && pl.use_strip && !cs && L.G == 2) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<8,AM-P,double,2> (paired strips of %d rows, no lambda_bar array)", pl.RS);
     else if (amp && pl.use_strip && !cs) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<%d,AM-P> (strips of %d rows, no lambda_bar array)", L.B, pl.RS);
     else if (amp) std::snprintf(rowk, sizeof rowk, "hadi_pass_a<%d,%d,%d,%d,%d,AM-P> (tiles of %d rows, no lambda_bar array)", L.B, L.G, pl.W, pl.NG, pl.PD, pl.R);
     else if (f32 && pl.use_strip && L.B == 8 && L.G == 2) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<8,EU,float,2> (paired strips of %d rows, fp32 state)", pl.RS);
     else if (f32 && pl.use_strip && L.B == 8) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<8,EU,float> (strips of %d rows, fp32 state)", pl.RS);
     else if (f32) std::snprintf(rowk, sizeof rowk, "hadi_pass_a<%d,%d,%d,%d,%d,EU,float> (tiles of %d rows, fp32 state)", L.B, L.G, pl.W, pl.NG, pl.PD, pl.R);
-    else if (pl.use_strip && cs && c->cs_strips && !pl.use_pairs && L.G == 2) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<8,EU,double,2,CS> (paired strips of %d rows)", pl.RS);
-    else if (pl.use_strip && cs && c->cs_strips && !pl.use_pairs) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<%d,EU,double,1,CS> (strips of %d rows)", L.B, pl.RS);
+    else if (pl.use_strip && cs && c->cs_strips && !pl.use_pairs && L.G == 2) std::snprintf(rowk, sizeof rowk, "%s<8,EU,double,2,%s> (paired strips of %d rows%s)", strip_k, sch, pl.RS,
+                      scheme == HADI_SCHEME_CRAIG_SNEYD ? "" : "; the predictor on hadi_pass_a_sch");
+    else if (pl.use_strip && cs && c->cs_strips && !pl.use_pairs) std::snprintf(rowk, sizeof rowk, "%s<%d,EU,double,1,%s> (strips of %d rows)", strip_k, L.B, sch, pl.RS);
     else if (pl.use_strip && !cs && L.G == 2) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<8,%s,double,2> (paired strips of %d rows)", american ? "AM" : "EU", pl.RS);
     else if (pl.use_strip && !cs) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<%d,%s> (strips of %d rows)", L.B, american ? "AM" : "EU", pl.RS);
-    else std::snprintf(rowk, sizeof rowk, "hadi_pass_a<%d,%d,%d,%d,%d,%s%s> (tiles of %d rows)", L.B, L.G, pl.W, pl.NG, pl.PD,
-                       american ? "AM" : "EU", cs ? ",CS" : "", pl.R);
+    else std::snprintf(rowk, sizeof rowk, "%s<%d,%d,%d,%d,%d,%s%s%s> (tiles of %d rows)", ring_k, L.B, L.G, pl.W, pl.NG, pl.PD,
+                       american ? "AM" : "EU", cs ? "," : "", cs ? sch : "", pl.R);
     if (pl.use_pairs && pl.use_strip && !cs && !f32)
         std::snprintf(rowk, sizeof rowk, "hadi_pass_a_pairs<%s> (two strips of %d rows per wavefront%s)", amp ? "AM-P" : american ? "AM" : "EU", pl.RS,
                       amp ? ", no lambda_bar array" : "");
@@ -645,7 +709,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
         if ((rc = ensure(c, c->U0, st))) return rc;
     }
     if (dividend && (rc = ensure(c, c->UT, st))) return rc;
-    const bool cs = d.scheme == HADI_SCHEME_CRAIG_SNEYD;
+    const bool cs = d.scheme != HADI_SCHEME_DOUGLAS;  // a predictor-corrector scheme (CS, MCS, HV): R1 / C2 carry-over, V = Y2
     const bool f32 = d.prec == HADI_STATE_FP32;  // European Douglas (with or without dividends) only (validated)
     if (f32 && ((rc = ensure(c, c->Uf, st / 2)) || (rc = ensure(c, c->Yf, st / 2)))) return rc;
     if (cs && ((rc = ensure(c, c->V, st)) || (rc = ensure(c, c->R1, st)) || (rc = ensure(c, c->C2, st)))) return rc;
@@ -830,7 +894,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
                     hipLaunchKernelGGL(hadi_narrow_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, Ub, reinterpret_cast<float *>(a.U), tot);
             }
             if (prof) HIP_TRY(c, hipEventRecord(c->kev[ev0 + 4 * (nstep - 1) + 0], q));
-            const PassEnv env{pl, L, nsb, q, nstep, american, amp, xstep, f32, c->col_prefetch, c->cs_strips};
+            const PassEnv env{pl, L, nsb, q, nstep, american, amp, xstep, f32, c->col_prefetch, c->cs_strips, d.scheme};
             auto row_pass = [&](const HadiSweepArgs &ar, int mode) { launch_row_pass(env, ar, mode); };
             auto col_pass = [&](const HadiSweepArgs &ar) { launch_col_pass(env, ar); };
             if (d.debug == 2) {  // diagnostics: one column solve of the packed input (moved to Y), nothing else
@@ -947,7 +1011,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
         return HADI_OK;
     }
 
-    c->last_path = describe_streaming_path(c, pl, bp, american, amp, cs, f32);
+    c->last_path = describe_streaming_path(c, pl, bp, american, amp, d.scheme, f32);
     c->last_nsub = nsub;
     HIP_TRY(c, hipEventRecord(c->ev[1], s));
     // ---- instance-resident launch: up to 8 large European instances, one per XCD, whole time loop in one kernel ----------
@@ -1146,10 +1210,12 @@ int check_problem(Ctx *c, const hadi_problem *p, bool need_U, bool need_vgrid) {
     if (dividend && p->num_dividends > 0 && (!p->dividend_dates || !p->dividend_amounts || !p->dividend_percentages))
         return fail(c, HADI_ERR_INVALID, "dividend arrays missing");
     if (p->num_dividends < 0) return fail(c, HADI_ERR_INVALID, "num_dividends < 0");
-    if (p->scheme != HADI_SCHEME_DOUGLAS && p->scheme != HADI_SCHEME_CRAIG_SNEYD)
+    if (p->scheme != HADI_SCHEME_DOUGLAS && p->scheme != HADI_SCHEME_CRAIG_SNEYD && p->scheme != HADI_SCHEME_MCS && p->scheme != HADI_SCHEME_HV)
         return fail(c, HADI_ERR_INVALID, "bad scheme %d", p->scheme);
-    if (p->scheme == HADI_SCHEME_CRAIG_SNEYD && p->variant != HADI_EU)
-        return fail(c, HADI_ERR_UNSUPPORTED, "Craig-Sneyd is available for the European variant only (as in the reference)");
+    if (p->scheme != HADI_SCHEME_DOUGLAS && p->variant != HADI_EU)
+        return fail(c, HADI_ERR_UNSUPPORTED, "the predictor-corrector schemes (Craig-Sneyd, MCS, HV) are available for the European variant only");
+    if ((p->scheme == HADI_SCHEME_MCS || p->scheme == HADI_SCHEME_HV) && !(p->theta > 0))
+        return fail(c, HADI_ERR_UNSUPPORTED, "MCS / HV steps need theta > 0");
     if (p->state_precision != HADI_STATE_FP64 && p->state_precision != HADI_STATE_FP32)
         return fail(c, HADI_ERR_INVALID, "bad state_precision %d", p->state_precision);
     if (p->state_precision == HADI_STATE_FP32 &&

@@ -10,6 +10,25 @@
 // unknown boundary value (a second right-hand side carried through the cyclic reduction) and the two
 // boundary values follow from a 2x2 system exchanged through LDS -- small per-lane state (B = 4 at
 // m1 = 512) is what lets four wavefronts share a SIMD.
+// Splitting schemes of the predictor / corrector kernels (MODE 1 / 2): the values of enum hadi_scheme (hadi.h).
+#define HADI_SCH_CS 1
+#define HADI_SCH_MCS 2
+#define HADI_SCH_HV 3
+// Their scalars (hadi_row_step): the corrector adds ka theta dt A1 Y2 + kb A2 Y2 + kc C2, the predictor kt theta dt A1 U to R1
+// (and kb-weighted b1 terms).  theta > 0: the host refuses theta = 0 for these schemes.
+HADI_DEV HADI_FORCEINLINE double hadi_sch_ka(double dt, double thdt) { return (0.5 * dt - thdt) / thdt; }
+template <int SCH>
+HADI_DEV HADI_FORCEINLINE double hadi_sch_kb(double dt, double thdt) { return SCH == HADI_SCH_MCS ? 0.5 * dt - thdt : 0.5 * dt; }
+template <int SCH>
+HADI_DEV HADI_FORCEINLINE double hadi_sch_kc(double dt, double thdt) { return SCH == HADI_SCH_MCS ? (0.5 * dt - thdt) / thdt : -(0.5 * dt) / thdt; }
+template <int SCH>
+HADI_DEV HADI_FORCEINLINE double hadi_sch_kt(double dt, double thdt) { return SCH == HADI_SCH_MCS ? -((0.5 * dt - thdt) / thdt) : (0.5 * dt) / thdt; }
+struct HadiSchK { double ka, kb, kc, kt; };
+template <int SCH>
+HADI_DEV HADI_FORCEINLINE HadiSchK hadi_sch_consts(double dt, double thdt) {
+    return HadiSchK{hadi_sch_ka(dt, thdt), hadi_sch_kb<SCH>(dt, thdt), hadi_sch_kc<SCH>(dt, thdt), hadi_sch_kt<SCH>(dt, thdt)};
+}
+
 template <class T>
 struct HadiRowCtxT {
     const double *coef;  // LDS: Bm, Bp, Dm, Dp, each 64*B*G doubles in row layout
@@ -20,6 +39,7 @@ struct HadiRowCtxT {
     int j0;              // first v-row of the tile
     const double *b2r;   // instance b2 row (global)
     double *R1i, *C2i;   // instance bases of the Craig-Sneyd carry-over arrays (MODE 1 writes, MODE 2 reads)
+    double ka, kb, kc, kt;  // SCH = MCS / HV only (hadi_sch_ka ...)
     int lane, half, wrow, posL, posR, rowp;
     double dt, thdt, qd, half_rd, e_nm1, e_n;
     double hr0, inv0;    // i = 0 row of A1: reaction term (0 for the call) and 1 / (1 + theta dt hr0)
@@ -161,7 +181,16 @@ HADI_DEV HADI_FORCEINLINE void hadi_get_block_nt(const double *row, int half, in
 // with  P = U_bar - dt lambda_bar_old  (device_solver.hpp:358-372 rewritten), so ONE array -- P, stored where U is --
 // carries both, provided the payoff U0 depends on s only (then it is a per-lane constant here).  The row pass rebuilds U on
 // the five stencil rows and lambda_bar on row j from P; no lambda_bar array is read or written by the sweep.
-template <int B, int G, int AMER, bool LAST, int MODE = 0, class T = double>
+// SCH (MODE 1 / 2): HADI_SCH_CS as above, or Modified Craig-Sneyd / Hundsdorfer-Verwer (in 't Hout & Foulon).  Every
+// U-dependent part of the corrector's A1 right-hand side is folded into the two carry-over rows; the A2 part of it is C2 up to
+// a factor, C2 = -theta dt (A2U + b2 (e_{n-1} - e_n)), so the predictor adds only A1 / b1 terms to R1 (the strips' paired
+// predictor has no register to spare) and the corrector forms, with ka = (1/2 - theta) / theta,
+//   MCS  R1 = CS's R1 - (1/2 - theta) dt (A1U + b1 (e_{n-1} - e_n))                  col: + C2
+//        rhs = R1 + dt/2 A0Y2 + (1/2 - theta) dt (A1Y2 + A2Y2) + ka C2
+//   HV   R1 = U + dt/2 (A0U + A1U + b1 (e_{n-1} + e_n)) + dt b2 e_n                col: - theta dt A2Y2
+//        rhs = R1 + dt/2 A0Y2 + (1/2 - theta) dt A1Y2 + dt/2 A2Y2 - dt / (2 theta dt) C2
+// Same loads and stores as CS (96 B per point and step); MCS at theta = 1/2 is CS.
+template <int B, int G, int AMER, bool LAST, int MODE = 0, class T = double, int SCH = HADI_SCH_CS>
 HADI_DEV HADI_FORCEINLINE void hadi_row_step(const HadiRowCtxT<T> &c, bool active, int j, const T *rm2, const T *rm1,
                                              const T *r0, const T *rp1, const T *rp2) {
     const int lane = c.lane, rowp = c.rowp, half = c.half;
@@ -209,15 +238,21 @@ HADI_DEV HADI_FORCEINLINE void hadi_row_step(const HadiRowCtxT<T> &c, bool activ
         double y0c0 = c0 + dt * (a2c0 + a1c0 + (b1c0 + b2c0) * e_nm1 + lamc0);
         y0c0 = y0c0 + thdt * (b1c0 * e_n - (a1c0 + b1c0 * e_nm1));
         double c2c0 = thdt * (b2c0 * e_n - (a2c0 + b2c0 * e_nm1));
-        if constexpr (MODE == 1) {  // A0 is zero on i = 0: R1 = Y1rhs there
+        if constexpr (MODE == 1) {  // A0 is zero on i = 0: R1 = Y1rhs there (CS)
             if (lane == 0 && first_half) {
-                c.R1i[(size_t)j * rowp + c0slot] = y0c0;
+                double r1c0 = y0c0;
+                if constexpr (SCH == HADI_SCH_MCS) r1c0 = fma(c.kt * thdt, a1c0, fma(-c.kb * (e_nm1 - e_n), b1c0, y0c0));
+                if constexpr (SCH == HADI_SCH_HV)
+                    r1c0 = fma(dt * e_n, b2c0, fma(c.kt * thdt, a1c0, fma(c.kb * (e_nm1 + e_n), b1c0, c0)));
+                c.R1i[(size_t)j * rowp + c0slot] = r1c0;
                 c.C2i[(size_t)j * rowp + c0slot] = c2c0;
             }
         }
         if constexpr (MODE == 2) {
             y0c0 = c.R1i[(size_t)j * rowp + c0slot];
             c2c0 = c.C2i[(size_t)j * rowp + c0slot];
+            if constexpr (SCH != HADI_SCH_CS) y0c0 = fma(c.kc, c2c0, fma(c.ka, thdt * a1c0, fma(c.kb, a2c0, y0c0)));
+            if constexpr (SCH == HADI_SCH_HV) c2c0 = -thdt * a2c0;
         }
         const double x0 = y0c0 * c.inv0;  // A1 row 0 is decoupled: the identity for the call (hes_a1_kernels.hpp:56-61)
         yout_c0 = x0 + c2c0;
@@ -314,8 +349,20 @@ HADI_DEV HADI_FORCEINLINE void hadi_row_step(const HadiRowCtxT<T> &c, bool activ
             double y = fma(dt, S, u0[r]);
             y = fma(-thdt, A1U, y);
             y = fma(b1l, (r == b1r) ? 1.0 : 0.0, y);  // wave-uniform selector: one FMA with a scalar operand
-            if constexpr (MODE == 1) r1v[r] = fma(-0.5 * dt, A0U, y);
+            if constexpr (MODE == 1 && SCH == HADI_SCH_CS) r1v[r] = fma(-0.5 * dt, A0U, y);
+            if constexpr (MODE == 1 && SCH == HADI_SCH_MCS)
+                r1v[r] = fma(c.kt * thdt, A1U, fma(-c.kb * (e_nm1 - e_n), (lane == b1lane && r == b1r) ? b1val : 0.0, fma(-0.5 * dt, A0U, y)));
+            if constexpr (MODE == 1 && SCH == HADI_SCH_HV) {
+                double bn = fma(c.kb * (e_nm1 + e_n), (lane == b1lane && r == b1r) ? b1val : 0.0, fma(0.5 * dt, A0U, u0[r]));
+                if constexpr (LAST) bn = fma(dt * e_n, b2v[r], bn);
+                r1v[r] = fma(c.kt * thdt, A1U, bn);
+            }
             if constexpr (MODE == 2) y = fma(0.5 * dt, A0U, r1v[r]);  // A0U is A0 applied to Y2 here
+            if constexpr (MODE == 2 && SCH != HADI_SCH_CS) {             // ... and so are A1U and A2U
+                y = fma(c.ka * thdt, A1U, y);
+                y = fma(c.kb, A2U[r], y);
+                y = fma(c.kc, c2v[r], y);
+            }
             double il = -thdt * lo;
             const double im = 1.0 - thdt * mn;
             iu[r] = -thdt * up;
@@ -528,7 +575,8 @@ HADI_DEV HADI_FORCEINLINE void hadi_row_step(const HadiRowCtxT<T> &c, bool activ
             if (r < NB) x = ys[r] - XL * ps[r] - X * gs[r];
             else x = X;
             double corr;
-            if constexpr (MODE == 2) corr = c2v[r];
+            if constexpr (MODE == 2 && SCH == HADI_SCH_HV) corr = -thdt * A2U[r];
+            else if constexpr (MODE == 2) corr = c2v[r];
             else if constexpr (LAST) corr = thdt * (b2v[r] * e_n - (A2U[r] + b2v[r] * e_nm1));
             else corr = -thdt * A2U[r];
             yo[r] = x + corr;
@@ -592,152 +640,25 @@ HADI_DEV HADI_FORCEINLINE void hadi_wait_vmcnt(int n) {
 // Every shape runs NG = 1 (hadi_plan.h: two groups behind one barrier measured slower); PD = 1 at 8 nodes per lane
 // (two 4-wave blocks per CU), 2 below.  Large batches at 8 nodes per lane use hadi_pass_a_strip instead.
 // T = float: fp32-state sweep (a.U / a.Y then point to float arrays of the same element layout; European Douglas only).
-template <int B, int G, int W, int NG, int PD, int AMER, int MODE = 0, class T = double>
 // Minimum blocks per CU of the shared-ring kernel at 4 nodes per lane: 3 (170 VGPRs) -- at 4 (128 VGPRs) the American
 // variants spill into scratch inside the row loop (measured, 256x128 x512 American puts: 0.0966 -> 0.0942 ms per launch)
 #ifndef HADI_RING_OCC_B4
 #define HADI_RING_OCC_B4 3
 #endif
+// The body of both kernels below (SCH: the splitting scheme of the predictor / corrector roles) is hadi_k_row_ring_body.h,
+// included into each (as an inlined function it changed the code hipcc made of the existing instantiations).
+template <int B, int G, int W, int NG, int PD, int AMER, int MODE = 0, class T = double>
 __global__ void __launch_bounds__(64 * W * G * NG, (B >= 8 ? 2 : B == 4 ? HADI_RING_OCC_B4 : 4)) hadi_pass_a(HadiSweepArgs a, int n) {
-    static_assert(sizeof(T) == 8 || (!AMER && MODE == 0), "the fp32-state sweep covers the European Douglas step only");
-    HADI_DYN_SMEM(double, smem);
-    constexpr int RING = (PD + 1) * W + 4;
-    constexpr int NT = 64 * W * G * NG;
-    const int lane = threadIdx.x & 63;
-    const int wave = HADI_UNIFORM((int)(threadIdx.x >> 6));
-    const int grp = wave / (W * G), wv = wave - grp * (W * G);
-    const int wrow = wv / G, half = wv - wrow * G;
-    const int tblocks = (a.ntiles + NG - 1) / NG;  // blocks per instance
-    const int total = a.n_inst * tblocks;
-    const int logical = hadi_xcd_remap(blockIdx.x, gridDim.x);
-    if (logical >= total) return;
-    const int inst = logical / tblocks, tb = logical - inst * tblocks;
-    const HadiInstPar ip = a.ipar[inst];
-    if (n > ip.N) return;
-    const int nrows = a.L.nrows, npad = a.L.nrows_pad, rowp = a.L.rowp;
-    const int tile = tb * NG + grp;
-    const int j0 = tile * a.R;  // may be >= nrows for the last block's spare group: that group only joins barriers
-    const int j1 = (j0 + a.R < nrows) ? j0 + a.R : nrows;
-
-    HadiRowCtxT<T> c;
-    c.lane = lane;
-    c.half = half;
-    c.wrow = wrow;
-    c.rowp = rowp;
-    c.dt = ip.dt; c.thdt = ip.thdt; c.qd = ip.q; c.half_rd = ip.half_rd;
-    c.hr0 = ip.hr0; c.inv0 = 1.0 / (1.0 + ip.thdt * ip.hr0);
-    c.e_nm1 = exp(ip.bc_rate * ip.dt * (n - 1));  // device_solver.hpp:238
-    c.e_n = exp(ip.bc_rate * ip.dt * n);          // device_solver.hpp:246
-    const T *__restrict__ Ub = reinterpret_cast<const T *>(a.U) + (size_t)inst * a.L.inst_stride;
-    c.Yi = reinterpret_cast<T *>(a.Y) + (size_t)inst * a.L.inst_stride;
-    c.Li = (AMER == 1) ? a.LAM + (size_t)inst * a.L.inst_stride : nullptr;
-    c.b2r = a.b2row + (size_t)inst * rowp;
-    c.R1i = MODE ? a.R1 + (size_t)inst * a.L.inst_stride : nullptr;
-    c.C2i = MODE ? a.C2 + (size_t)inst * a.L.inst_stride : nullptr;
-    c.j0 = j0;
-    c.err = a.err; c.debug = a.debug;
-    constexpr int c0slot = 64 * B * G;
-    // storage positions of the s-neighbours of this lane's block (node before its first, node after its
-    // last).  Before i = 1 comes the i = 0 slot; after the row's last node comes a pad slot (always 0).
-    {
-        const int ifirst = 1 + 64 * B * half + B * lane;
-        if constexpr (sizeof(T) == 4) {
-            c.posL = hadi_pos_f32(B, G, ifirst - 1);
-            c.posR = (ifirst + B <= 64 * B * G) ? hadi_pos_f32(B, G, ifirst + B) : c0slot + 1;
-        } else {
-            c.posL = hadi_pos(B, G, ifirst - 1);
-            c.posR = (ifirst + B <= 64 * B * G) ? hadi_pos(B, G, ifirst + B) : c0slot + 1;
-        }
-    }
-
-    // LDS: [NG rings of RING rows of T] [4 coefficient arrays of 64*B*G] [NG*W*8 exchange] [NG compact row tables]
-    T *ring = reinterpret_cast<T *>(smem) + (size_t)grp * RING * rowp;
-    double *coef = reinterpret_cast<double *>(reinterpret_cast<T *>(smem) + (size_t)NG * RING * rowp);
-    {
-        const double *__restrict__ sc = a.scoef + (size_t)inst * 4 * 64 * B * G;
-        for (int e = threadIdx.x; e < 4 * 64 * B * G; e += NT) coef[e] = sc[e];
-    }
-    c.coef = coef;
-    c.xch = coef + 4 * 64 * B * G + grp * 8 * W;  // per v-row: 4 exchange values + the two rendezvous tokens
-    if (threadIdx.x < 8 * W * NG) coef[4 * 64 * B * G + threadIdx.x] = 0.0;  // (tokens start at 0; the first loop barrier publishes this)
-    {
-        double *rtab = coef + 4 * 64 * B * G + NG * 8 * W + (size_t)grp * a.R * HADI_RCL;
-        const double *__restrict__ rg = a.rowc + ((size_t)inst * nrows + j0) * HADI_RC;
-        const int tl = threadIdx.x - grp * 64 * W * G;
-        for (int e = tl; e < (j1 - j0) * HADI_RCL; e += 64 * W * G) rtab[e] = rg[(e / HADI_RCL) * HADI_RC + e % HADI_RCL];
-        c.rowc = rtab;
-        c.payrow = nullptr; c.inv_dt = 0.0; c.m1_lane = -1; c.m1_r = -1;
-        if constexpr (AMER == 2) {  // payoff row (v-row 0 of the packed payoff; it depends on s only) after the tables
-            double *prow = coef + 4 * 64 * B * G + NG * 8 * W + (size_t)NG * a.R * HADI_RCL;
-            const double *__restrict__ pg = a.U0 + (size_t)inst * a.L.inst_stride;
-            for (int e = threadIdx.x; e < rowp; e += NT) prow[e] = pg[e];
-            c.payrow = prow;
-            c.inv_dt = 1.0 / ip.dt;
-            const int e1 = a.L.m1 - 1;  // node i = m1 is element m1-1 of the row's 64*B*G interior nodes
-            if (e1 / (64 * B) == half) {
-                c.m1_lane = (e1 - half * 64 * B) / B;
-                c.m1_r = (e1 - half * 64 * B) % B;
-            }
-        }
-    }
-
-    const int iters = (j1 > j0) ? (j1 - j0 + W - 1) / W : 0;  // this group's iterations
-    const int iters_all = (a.R + W - 1) / W;                   // every group of the block runs this many barriers
-    auto slot = [&](int jj) { return ring + (size_t)((jj + 4 * RING) % RING) * rowp; };
-    // fetch returns the number of vector-memory instructions it issued
-    auto fetch = [&](int jj) -> int {
-        const bool exists = jj >= 0 && jj < npad;
-        if constexpr ((64 * B * G + HADI_ROW_PAD(B, (int)sizeof(T))) % (16 / (int)sizeof(T)) == 0)
-            hadi_row_to_lds_fixed<B, T, G>(Ub + (ptrdiff_t)jj * rowp, slot(jj), lane, exists);
-        else
-            hadi_row_to_lds(Ub + (size_t)jj * rowp, slot(jj), rowp, lane, exists);
-        return exists ? hadi_row_dma_count<T>(rowp) : 0;
-    };
-    // prologue: rows of iterations 0 .. PD-1
-    if (iters > 0)
-        for (int rr = wv; rr < PD * W + 4; rr += W * G) fetch(j0 - 2 + rr);
-
-    // Vector-memory operations retire in issue order.  ya[k] = (lower bound of the) number of operations this
-    // wavefront issued after the DMA batch that iteration it+k needs, so hadi_wait_vmcnt(ya[0]) retires that
-    // batch and leaves younger batches and result stores in flight.
-    int ya[PD];
-#pragma unroll
-    for (int k = 0; k < PD; k++) ya[k] = 0;
-#if defined(HADI_STAMPS) && !defined(HADI_EMU)
-    unsigned long long stamp_store_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    c.stamp_acc_ = stamp_store_;
-#endif
-    HADI_STAMP_DECL(stamp_store_)
-    HADI_STAMP(8);  // prologue
-    for (int it = 0; it < iters_all; it++) {
-        const int J = j0 + it * W;
-        hadi_wait_vmcnt(ya[0]);
-        __syncthreads();  // this iteration's rows have landed; everyone is done with the rows replaced below
-        HADI_STAMP(9);  // barrier wait (incl. DMA drain)
-        int z = 0;
-        if (it + PD < iters && wv < W) z = fetch(J + PD * W + 2 + wv);
-#pragma unroll
-        for (int k = 0; k + 1 < PD; k++) ya[k] = ya[k + 1] + z;
-        ya[PD - 1] = 0;
-        if constexpr (PD == 1) ya[0] = 0;
-        const int j = J + wrow;
-        const bool active = it < iters && j < j1;
-        if constexpr (G == 1) {
-            if (!active) continue;
-        }
-        if (j == nrows - 1)
-            hadi_row_step<B, G, AMER, true, MODE, T>(c, active, j, slot(j - 2), slot(j - 1), slot(j), slot(j + 1), slot(j + 2));
-        else
-            hadi_row_step<B, G, AMER, false, MODE, T>(c, active, j, slot(j - 2), slot(j - 1), slot(j), slot(j + 1), slot(j + 2));
-        if (active) {  // B/2 (one for B = 1) vector stores of the block; the i = 0 store is not counted (lower bound)
-#pragma unroll
-            for (int k = 0; k < PD; k++) ya[k] += hadi_put_block_stores<B, T>();
-        }
-        HADI_STAMP(10);  // whole row step (+ fetch issue)
-    }
-#if defined(HADI_STAMPS) && !defined(HADI_EMU)
-    if (lane == 0)
-        for (int k = 0; k < 12; k++) atomicAdd(&g_hadi_stamps[k], stamp_store_[k]);
-#endif
+    constexpr int SCH = HADI_SCH_CS;
+#include "hadi_k_row_ring_body.h"
+}
+// Modified Craig-Sneyd / Hundsdorfer-Verwer (SCH = HADI_SCH_MCS / HADI_SCH_HV) predictor (MODE 1) and corrector (MODE 2) on the
+// shared ring: European, fp64 state, the geometry and LDS of hadi_pass_a<B, G, W, NG, PD, 0, MODE>.
+template <int B, int G, int W, int NG, int PD, int MODE, int SCH>
+__global__ void __launch_bounds__(64 * W * G * NG, (B >= 8 ? 2 : B == 4 ? HADI_RING_OCC_B4 : 4)) hadi_pass_a_sch(HadiSweepArgs a, int n) {
+    static_assert((MODE == 1 || MODE == 2) && (SCH == HADI_SCH_MCS || SCH == HADI_SCH_HV), "MCS / HV predictor or corrector");
+    constexpr int AMER = 0;
+    typedef double T;
+#include "hadi_k_row_ring_body.h"
 }
 

@@ -238,7 +238,8 @@ class HestonADI:
                         variant=EU, U_0=None, lambda_bar=None, dividends=None, per_instance=None, scheme=0,
                         state_precision=0, option_type=CALL, strikes=None):
         """Boundary init + operator build + N Douglas steps on the caller's grids; U is updated in
-        place (initial condition in, solution at T out).  scheme=1 runs Craig-Sneyd (European only);
+        place (initial condition in, solution at T out).  scheme=1 runs Craig-Sneyd, scheme=2 Modified Craig-Sneyd (theta = 1/3
+        is the usual choice), scheme=3 Hundsdorfer-Verwer (theta = 1/2 + sqrt(3)/6) -- European call, fp64 state only;
         state_precision=1 keeps the state between the two passes in fp32 (European Douglas only, arithmetic stays fp64)."""
         p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids,
                           U=U, U_0=U_0, lambda_bar=lambda_bar, dividends=dividends, per_instance=per_instance,
@@ -284,6 +285,18 @@ class HestonADI:
         the explicit mixed-derivative increment (the reference has it in its host operator family only)."""
         return self.DO_timestepping(m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U,
                                     per_instance=per_instance, scheme=nat.SCHEME_CRAIG_SNEYD)
+
+    def MCS_scheme(self, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U, per_instance=None):
+        """Modified Craig-Sneyd time stepping of European options (in 't Hout & Foulon; second order for every theta, usually
+        theta = 1/3): the Craig-Sneyd corrector with the whole explicit increment re-weighted by 1/2 - theta."""
+        return self.DO_timestepping(m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U,
+                                    per_instance=per_instance, scheme=nat.SCHEME_MCS)
+
+    def HV_scheme(self, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U, per_instance=None):
+        """Hundsdorfer-Verwer time stepping of European options (in 't Hout & Foulon; second order for every theta, usually
+        theta = 1/2 + sqrt(3)/6): a second Douglas-type sweep from the predictor's result."""
+        return self.DO_timestepping(m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U,
+                                    per_instance=per_instance, scheme=nat.SCHEME_HV)
 
     # ---- parallel_DO_solve (src/device_solver.hpp:52-185) --------------------------------------
     def parallel_DO_solve(self, nInstances, S_0, V_0, m1, m2, N, T, delta_t, theta, r_d, r_f, rho, sigma,
