@@ -5,6 +5,8 @@
 #include "hadi_kernels.h"
 #include "hadi_plan.h"
 
+#include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -19,7 +21,8 @@ thread_local int t_lane;
 static HadiTuning g_tune;
 static int g_err = 0, g_debug = 0;  // the handle's device error word and the "debug_fault" test hook
 static int g_tile_il = 0;           // "tile_interleave": the column pass's blocks take their full tiles interleaved (opt-in, as in the library)
-static int g_cs_strips = 1;         // "cs_strips": Craig-Sneyd row passes on strips where the plan chose strips (default, as in the library)
+static int g_cs_strips = 1;         // "cs_strips": predictor-corrector row passes on strips where the plan chose strips (default, as in
+                                    // the library); 2 / 3: only the predictor / only the corrector on strips, the other on the ring
 static int g_team_blocks = 1;       // "team_blocks": blocks per team of the instance-resident launch (> 1: the grid's blocks run concurrently)
 static int g_col_prefetch = 0;      // "col_prefetch": hadi_pass_b2 for European sweeps of 9 .. 16 chunks (opt-in, as in the library)
 extern "C" int emu_take_error() { const int e = g_err; g_err = 0; return e; }
@@ -32,7 +35,7 @@ extern "C" int emu_set_tuning(const char *key, int value) {
     else if (k == "pair_strips") g_tune.pair_strips = value < 0 ? -1 : (value ? 1 : 0);
     else if (k == "col_groups") g_tune.col_groups = value > 0 ? value : 0;
     else if (k == "col_prefetch") g_col_prefetch = value ? 1 : 0;
-    else if (k == "cs_strips") g_cs_strips = value ? 1 : 0;
+    else if (k == "cs_strips") g_cs_strips = (value >= 0 && value <= 3) ? value : 1;  // (as hadi_set_tuning)
     else if (k == "team_blocks") g_team_blocks = value > 0 ? value : 1;
     else if (k == "tile_interleave") g_tile_il = value ? 1 : 0;
     else if (k == "reset") { g_tune = HadiTuning(); g_debug = 0; g_col_prefetch = 0; g_tile_il = 0; g_cs_strips = 1; g_team_blocks = 1; }
@@ -49,7 +52,44 @@ static void run_pass_a(const HadiPlan &pl, const HadiSweepArgs &a, int n, int mo
     else emu::launch(pl.grid_a, nt, [&]() { hadi_pass_a<B, G, 4, NG, PD, false>(a, n); }, pl.smem_a);
 }
 
-static int run_row_pass(const HadiPlan &pl, const HadiSweepArgs &a, int n, int mode) {
+// Modified Craig-Sneyd / Hundsdorfer-Verwer predictor (mode 1) and corrector (mode 2): same choice as launch_row_pass_sch
+template <int B, int G, int NG, int PD, int SCH>
+static void run_pass_a_sch(const HadiPlan &pl, const HadiSweepArgs &a, int n, int mode) {
+    const unsigned nt = 64 * pl.W * G * NG;
+    if (mode == 1) emu::launch(pl.grid_a, nt, [&]() { hadi_pass_a_sch<B, G, 4, NG, PD, 1, SCH>(a, n); }, pl.smem_a);
+    else emu::launch(pl.grid_a, nt, [&]() { hadi_pass_a_sch<B, G, 4, NG, PD, 2, SCH>(a, n); }, pl.smem_a);
+}
+template <int B, int G, int SCH>
+static void run_strip_sch(const HadiPlan &pl, const HadiSweepArgs &a, int n, int mode) {
+    const unsigned nt = 64 * HADI_STRIP_WAVES(B);
+    if (mode == 1) emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip_sch<B, G, 1, SCH>(a, n); }, pl.smem_as);
+    else emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip_sch<B, G, 2, SCH>(a, n); }, pl.smem_as);
+}
+template <int SCH>
+static int run_row_pass_sch(const HadiPlan &pl, const HadiSweepArgs &a, int n, int mode) {
+    // (paired strips: the corrector only -- the predictor of those shapes runs on the shared ring)
+    if (pl.use_strip && !pl.use_pairs && (g_cs_strips == 1 || g_cs_strips == 1 + mode) && !(pl.L.G == 2 && mode == 1)) {
+        if (pl.L.G == 2) emu::launch(pl.grid_as, 64 * HADI_STRIP_WAVES(8), [&]() { hadi_pass_a_strip_sch<8, 2, 2, SCH>(a, n); }, pl.smem_as);
+        else if (pl.L.B == 8) run_strip_sch<8, 1, SCH>(pl, a, n, mode);
+        else if (pl.L.B == 4) run_strip_sch<4, 1, SCH>(pl, a, n, mode);
+        else run_strip_sch<2, 1, SCH>(pl, a, n, mode);
+        return 0;
+    }
+    switch (pl.L.B * 10 + pl.L.G) {
+        case 11: run_pass_a_sch<1, 1, 1, 2, SCH>(pl, a, n, mode); break;
+        case 21: run_pass_a_sch<2, 1, 1, 2, SCH>(pl, a, n, mode); break;
+        case 41: run_pass_a_sch<4, 1, 1, 2, SCH>(pl, a, n, mode); break;
+        case 81: run_pass_a_sch<8, 1, 1, 1, SCH>(pl, a, n, mode); break;
+        case 82: run_pass_a_sch<8, 2, 1, 1, SCH>(pl, a, n, mode); break;
+        default: return 2;
+    }
+    return 0;
+}
+
+// sch: 0 Douglas / Craig-Sneyd, HADI_SCH_MCS, HADI_SCH_HV (modes 1 / 2 only)
+static int run_row_pass(const HadiPlan &pl, const HadiSweepArgs &a, int n, int mode, int sch = 0) {
+    if (mode != 0 && sch == HADI_SCH_MCS) return run_row_pass_sch<HADI_SCH_MCS>(pl, a, n, mode);
+    if (mode != 0 && sch == HADI_SCH_HV) return run_row_pass_sch<HADI_SCH_HV>(pl, a, n, mode);
     if (pl.row_seq) {  // same choice as hadi_api.hip
         if (mode) return 2;
         const unsigned g = a.n_inst * ((pl.L.nrows + 63) / 64);
@@ -62,7 +102,7 @@ static int run_row_pass(const HadiPlan &pl, const HadiSweepArgs &a, int n, int m
         else emu::launch(pl.grid_as, 64 * HADI_PAIR_WAVES, [&]() { hadi_pass_a_pairs<0>(a, n); }, pl.smem_pairs_eu);
         return 0;
     }
-    if (pl.use_strip && mode != 0 && !pl.use_pairs && g_cs_strips) {  // Craig-Sneyd on strips: same choice as hadi_api.hip
+    if (pl.use_strip && mode != 0 && !pl.use_pairs && (g_cs_strips == 1 || g_cs_strips == 1 + mode)) {  // Craig-Sneyd on strips: same choice as hadi_api.hip
         const unsigned nt = 64 * HADI_STRIP_WAVES(pl.L.B);
         if (pl.L.G == 2) {
             if (mode == 1) emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip<8, 0, double, 2, 1>(a, n); }, pl.smem_as);
@@ -222,20 +262,35 @@ extern "C" long long emu_plan_row_idle_ppm(int m1, int m2, int n_inst, int cus) 
 }
 
 // variant bit0 = american, bit1 = dividends.  Arrays natural layout [n][...].
+// scheme: 0 Douglas, 1 Craig-Sneyd, 2 Douglas with the fp32 state, 3 Douglas with the American P representation, 4 Modified
+// Craig-Sneyd, 5 Hundsdorfer-Verwer.  N_i / dt_i: per-instance time steps and step sizes (NULL: N and dt for every instance);
+// the time loop then runs to the largest N_i, as in the library.  Returns 0, 1 (no plan), 2 / 3 (unsupported), 4 (device error
+// word set) or 5 (a row pass wrote to an instance after its last step).
 extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double theta, double r_d, double r_f,
                          const double *par /*[n][4] rho sigma kappa eta*/, int variant, const double *vec_s,
                          const double *vec_v, const double *delta_s, const double *delta_v, double *U,
                          const double *U0, double *lam_out, int target_waves, int ndiv, const double *ddates,
                          const double *damounts, const double *dpcts, int setup_threads, int use_small, int scheme,
-                         const double *put_strikes /* NULL = call boundary data */) {
+                         const double *put_strikes /* NULL = call boundary data */, const int *N_i, const double *dt_i) {
     HadiPlan pl;
     if (hadi_make_plan(m1, m2, n_inst, target_waves, &pl, g_tune, scheme == 2 ? 4 : 8)) return 1;
+    if (!(theta > 0.0) || r_d == r_f) pl.use_strip = 0;  // as hadi_api.hip (no_strips): the strip kernels divide by theta dt
     const HadiLayout &L = pl.L;
     const int american = variant & 1, dividend = (variant >> 1) & 1;
     const size_t st = (size_t)L.inst_stride * n_inst;
-    const bool cs = scheme == 1, f32 = scheme == 2, amp = scheme == 3;
+    const int sch = scheme == 4 ? HADI_SCH_MCS : scheme == 5 ? HADI_SCH_HV : 0;
+    const bool cs = scheme == 1 || sch, f32 = scheme == 2, amp = scheme == 3;
+    if (scheme < 0 || scheme > 5) return 3;
     if (amp && !american) return 3;
     if (f32 && (american || dividend)) return 3;
+    if (cs && (american || dividend || put_strikes)) return 3;  // (the library's predictor-corrector schemes: European calls)
+    if (sch && !(theta > 0.0)) return 3;
+    if ((N_i || dt_i) && (!N_i || !dt_i || dividend)) return 3;  // (per-instance step grids: no per-instance dividend tables here)
+    int Nmax = N;
+    if (N_i) {
+        Nmax = 0;
+        for (int k = 0; k < n_inst; k++) Nmax = N_i[k] > Nmax ? N_i[k] : Nmax;
+    }
     std::vector<double> dV(cs ? st : 0), dR1(cs ? st : 0), dC2(cs ? st : 0);
     std::vector<double> dU(st), dY(st, 0.0), dLAM(american ? st : 0), dU0(american ? st : 0), dUT(dividend ? st : 0);
     std::vector<double> scoef(pl.n_scoef * n_inst), b2row(pl.n_b2row * n_inst), rowc(pl.n_rowc * n_inst),
@@ -244,8 +299,8 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
     std::vector<double> par8((size_t)n_inst * 8);
     for (int k = 0; k < n_inst; k++) {
         for (int z = 0; z < 4; z++) par8[(size_t)k * 8 + z] = par[(size_t)k * 4 + z];
-        par8[(size_t)k * 8 + 4] = dt;
-        par8[(size_t)k * 8 + 5] = (double)N;
+        par8[(size_t)k * 8 + 4] = dt_i ? dt_i[k] : dt;
+        par8[(size_t)k * 8 + 5] = (double)(N_i ? N_i[k] : N);
         par8[(size_t)k * 8 + 6] = put_strikes ? put_strikes[k] : 0.0;
         par8[(size_t)k * 8 + 7] = put_strikes ? 1.0 : 0.0;
     }
@@ -279,7 +334,7 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
     HadiSweepArgs av = a;
     if (cs) av.U = dV.data();
 
-    std::vector<int> flags(N, -1);
+    std::vector<int> flags(Nmax, -1);
     if (dividend) hadi_dividend_steps(N, dt, ndiv, ddates, flags.data(), N);
     if (use_small == 4) {  // instance-resident launch (hadi_team_kernel) with teams of ONE block: the emulator runs the blocks of a
                            // grid one after the other, so the team barrier is trivially met; indexing and arithmetic are real
@@ -289,7 +344,7 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
         // "team_blocks" > 1: teams of several blocks, all blocks of the grid running at once (the team barrier, the formation
         // counters and the row / column-tile split over the blocks are then real); 1: block after block, a team per block
         const int nb = g_team_blocks;
-        ta.form = team.data(); ta.bar = team.data() + 64; ta.nb = nb; ta.N = N; ta.stamps = nullptr;
+        ta.form = team.data(); ta.bar = team.data() + 64; ta.nb = nb; ta.N = Nmax; ta.stamps = nullptr;
         ta.div_flag = dividend ? flags.data() : nullptr; ta.flag_stride = 0; ta.div_amounts = damounts; ta.div_pcts = dpcts; ta.vec_s = vec_s;
         const size_t smem = ((size_t)4 * 64 * L.B + hadi_pb_mf_doubles(L.P) + (size_t)L.P * HADI_LC * HADI_PBW +
                              (dividend ? (size_t)(L.m1 + 2) + (size_t)8 * L.rowp : 0)) * sizeof(double) + 64;
@@ -302,7 +357,7 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
     if (use_small && !cs && !f32 && smem_small > 0) {
         HadiSmallArgs sm;
         sm.div_flag = dividend ? flags.data() : nullptr; sm.flag_stride = 0; sm.div_amounts = damounts; sm.div_pcts = dpcts;
-        sm.vec_s = vec_s; sm.Nmax = N; sm.order = nullptr;
+        sm.vec_s = vec_s; sm.Nmax = Nmax; sm.order = nullptr;
         if (use_small == 5 && !american && pl.L.nrows <= 32) {  // ... two instances per wavefront
             const size_t smem_seq = (size_t)hadi_small_seq_layout(pl.L.m1, pl.L.nrows).total * sizeof(double);
             if (pl.L.B == 1) emu::launch((n_inst + 1) / 2, 64, [&]() { hadi_small_seq2_kernel<1>(a, sm); }, 2 * smem_seq);
@@ -339,18 +394,28 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
         HadiSweepArgs af = a;
         af.U = reinterpret_cast<double *>(fU.data());
         af.Y = reinterpret_cast<double *>(fY.data());
-        for (int n = 1; n <= N; n++)
+        for (int n = 1; n <= Nmax; n++)
             if (run_sweep_f32(pl, af, n)) return 2;
         emu::launch(8, 64, [&]() { hadi_widen_kernel(L, fU.data(), dU.data(), st); });
         emu::launch(8, 64, [&]() { hadi_unpack_kernel(L, n_inst, dU.data(), U); });
         return 0;
     }
-    for (int n = 1; n <= N; n++) {
+    // per-instance step grids: an instance that has taken its last step gets NaN in its slices of the arrays the row passes write
+    // (Y, R1, C2); a later row pass that still worked on it would overwrite them, a later column pass would carry the NaN into U
+    auto poison_finished = [&](int n) {
+        for (int k = 0; N_i && k < n_inst; k++) {
+            if (N_i[k] != n || n == Nmax) continue;
+            for (double *arr : {dY.data(), cs ? dR1.data() : nullptr, cs ? dC2.data() : nullptr})
+                if (arr) std::fill(arr + (size_t)k * L.inst_stride, arr + (size_t)(k + 1) * L.inst_stride, std::nan(""));
+        }
+    };
+    for (int n = 1; n <= Nmax; n++) {
         const bool xstep = amp && (n == 1 || (dividend && flags[n - 1] >= 0));  // explicit (U, lambda_bar) step, as in hadi_api.hip
         if (xstep && n > 1)
             emu::launch(8, 64, [&]() { hadi_am_materialise_kernel(L, n_inst, ipar.data(), dU0.data(), dU.data(), dLAM.data(), pl.pos_m1); });
         if (amp && !xstep) {
             if (run_sweep_amp(pl, a, n)) return 2;
+            poison_finished(n);
             continue;
         }
         if (dividend && flags[n - 1] >= 0) {  // device_solver.hpp:426-517 (host builds the step table, kernel applies)
@@ -359,14 +424,21 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
                 hadi_dividend_kernel(L, n_inst, ipar.data(), vec_s, dUT.data(), dU.data(), flags.data(), 0, n, damounts, dpcts);
             });
         }
-        if (run_row_pass(pl, a, n, cs ? 1 : 0)) return 2;
+        if (run_row_pass(pl, a, n, cs ? 1 : 0, sch)) return 2;
         run_col_pass(pl, cs ? av : a, n);
         if (cs) {
-            run_row_pass(pl, av, n, 2);
+            run_row_pass(pl, av, n, 2, sch);
             run_col_pass(pl, a, n);
         }
         if (xstep)
             emu::launch(8, 64, [&]() { hadi_am_dematerialise_kernel(L, n_inst, ipar.data(), dU0.data(), dU.data(), dLAM.data()); });
+        poison_finished(n);
+    }
+    for (int k = 0; N_i && k < n_inst; k++) {
+        if (N_i[k] >= Nmax) continue;
+        for (double *arr : {dY.data(), cs ? dR1.data() : nullptr, cs ? dC2.data() : nullptr})
+            for (size_t e = 0; arr && e < (size_t)L.inst_stride; e++)
+                if (!std::isnan(arr[(size_t)k * L.inst_stride + e])) return 5;  // a row pass ran past the instance's N
     }
     if (amp)
         emu::launch(8, 64, [&]() { hadi_am_materialise_kernel(L, n_inst, ipar.data(), dU0.data(), dU.data(), dLAM.data(), pl.pos_m1); });

@@ -52,7 +52,8 @@ def _run(emu, m1, m2, N, strikes, variant, target_waves, r_f=0.0, small=0, schem
     dd = [np.array(x, dtype=np.float64) for x in Cm.DIVS]
     rc = emu.emu_solve(n, m1, m2, N, C.c_double(Cm.T / N), C.c_double(Cm.THETA), C.c_double(Cm.R_D),
                        C.c_double(r_f), _P(par), variant, _P(vs), _P(vv), _P(ds), _P(dv), _P(U), _P(U0), _P(lam),
-                       target_waves, len(dd[0]), _P(dd[0]), _P(dd[1]), _P(dd[2]), 64, small, scheme, _P(ks) if put else None)
+                       target_waves, len(dd[0]), _P(dd[0]), _P(dd[1]), _P(dd[2]), 64, small, scheme, _P(ks) if put else None,
+                       None, None)
     assert rc == 0
     scale = np.abs(Uo).max()
     # fp32 state: an fp64 last-bit difference before a store can flip the float rounding (6e-8 relative), per step
@@ -417,7 +418,7 @@ def test_one_node_per_lane_line_solve_keeps_close_nodes_together(emu):
             U, lam = U0.copy(), np.zeros_like(U0)
             rc = emu.emu_solve(1, m1, m2, N, C.c_double(Cm.T / N), C.c_double(Cm.THETA), C.c_double(Cm.R_D), C.c_double(c["r_f"]),
                                _P(par), variant, _P(vs), _P(vv), _P(ds), _P(dv), _P(U), _P(U0), _P(lam), 8, len(dd[0]),
-                               _P(dd[0]), _P(dd[1]), _P(dd[2]), 64, small, 0, None)
+                               _P(dd[0]), _P(dd[1]), _P(dd[2]), 64, small, 0, None, None, None)
             assert rc == 0
             e = np.abs(U[0] - Ux).max() / scale
             assert e < max(3 * e_oracle, 1e-9), (variant, small, e, e_oracle)  # was 1.7e-7 (AM_DIV) / 2.2e-7 (EU)
@@ -439,7 +440,7 @@ def test_rendezvous_timeout_sets_the_error_word(emu):
         U, lam = U0.copy(), np.zeros_like(U0)
         rc = emu.emu_solve(1, m1, m2, N, C.c_double(Cm.T / 10), C.c_double(Cm.THETA), C.c_double(Cm.R_D), C.c_double(0.0), _P(par),
                            O.EU, _P(vs), _P(vv), _P(ds), _P(dv), _P(U), _P(U0), _P(lam), 1, len(dd[0]), _P(dd[0]), _P(dd[1]),
-                           _P(dd[2]), 64, 0, 0, None)
+                           _P(dd[2]), 64, 0, 0, None, None, None)
         assert rc == 0
         return emu.emu_take_error()
 
@@ -576,6 +577,195 @@ def test_random_shapes_and_kernel_choices_vs_oracle(emu, seed):
         try:
             _run(emu, c["m1"], c["m2"], c["N"], c["strikes"], c["variant"], c["target_waves"], r_f=c["r_f"], scheme=c["scheme"], put=c["put"],
                  small=c["small"], tol=1e-10)  # (the bound of the GPU parity tests)
+        except AssertionError as e:
+            raise AssertionError("seed %d case %d: %r" % (seed, k, c)) from e
+        finally:
+            emu.emu_set_tuning(b"reset", 0)
+
+
+# ---- the predictor-corrector schemes (Craig-Sneyd, Modified Craig-Sneyd, Hundsdorfer-Verwer) and per-instance step grids ----
+# emu_solve's scheme codes: 0 Douglas, 1 CS, 3 Douglas with the American P representation, 4 MCS, 5 HV
+EMU_CS, EMU_AMP, EMU_MCS, EMU_HV = 1, 3, 4, 5
+TH_MCS, TH_HV = 1.0 / 3.0, 0.5 + np.sqrt(3.0) / 6.0
+# per-instance model parameters (rho, sigma, kappa, eta) of the mixed batches below
+PARS3 = [(-0.9, 0.3, 1.5, 0.04), (-0.5, 0.5, 2.0, 0.09), (0.3, 0.2, 0.5, 0.02)]
+
+
+def _plan(emu, m1, m2, n, target_waves):
+    """(B, G, use_strip, use_pairs) of the plan emu_solve starts from (the current tuning overrides applied)."""
+    o = (C.c_longlong * 26)()
+    assert emu.emu_plan_full(m1, m2, n, target_waves, o) == 0
+    return int(o[0]), int(o[1]), bool(o[14]), bool(o[24])
+
+
+def _run_pc(emu, m1, m2, strikes, scheme, target_waves, theta=Cm.THETA, r_f=0.0, N=2, Ns=None, dts=None, pars=None,
+            variant=O.EU, tol=1e-10):
+    """One batch through emu_solve, each instance's full field against its own reference solve: oracle.solve for Douglas / CS /
+    the P representation, scheme_ref.solve_one for MCS / HV (built from the instance's own make_params).  Ns / dts: per-instance
+    step counts and step sizes (emu_solve's N_i / dt_i; None: N steps of T / N for everybody).  pars: per-instance (rho, sigma,
+    kappa, eta).  tol: relative to max |U_ref| of the instance (the bound of the GPU parity tests)."""
+    import scheme_ref as S
+    n = len(strikes)
+    vs, vv, ds, dv, U0 = Cm.oracle_grids(m1, m2, strikes)
+    pars = pars or [(Cm.RHO, Cm.SIGMA, Cm.KAPPA, Cm.ETA)] * n
+    par = np.ascontiguousarray(np.array(pars[:n], dtype=np.float64))
+    Ni = np.array(Ns if Ns is not None else [N] * n, dtype=np.int32)
+    dti = np.array(dts if dts is not None else [Cm.T / N] * n, dtype=np.float64)
+    U, lam = U0.copy(), np.zeros_like(U0)
+    dd = [np.array(x, dtype=np.float64) for x in Cm.DIVS]
+    rc = emu.emu_solve(n, m1, m2, N, C.c_double(Cm.T / N), C.c_double(theta), C.c_double(Cm.R_D), C.c_double(r_f), _P(par),
+                       variant, _P(vs), _P(vv), _P(ds), _P(dv), _P(U), _P(U0), _P(lam), target_waves, len(dd[0]), _P(dd[0]),
+                       _P(dd[1]), _P(dd[2]), 64, 0, scheme, None,
+                       Ni.ctypes.data_as(C.POINTER(C.c_int)) if Ns is not None else None, _P(dti) if Ns is not None else None)
+    assert rc == 0, rc
+    for k in range(n):
+        p = O.make_params(m1, m2, int(Ni[k]), float(dti[k]), theta, Cm.R_D, r_f, *pars[k], variant,
+                          scheme=1 if scheme == EMU_CS else 0)
+        if scheme in (EMU_MCS, EMU_HV):
+            Uo, lo = S.solve_one(p, vs[k], vv[k], ds[k], dv[k], U0[k], S.MCS if scheme == EMU_MCS else S.HV), None
+        else:
+            Uo, lo, _ = O.solve(p, vs[k], vv[k], ds[k], dv[k], U0[k], U0[k])
+        scale = np.abs(Uo).max()
+        err = np.abs(U[k] - Uo).max()
+        assert err <= tol * scale, (k, err / scale)
+        if variant in (O.AM, O.AM_DIV):
+            assert np.abs(lam[k] - lo).max() <= 1e-9 * max(1.0, np.abs(lo).max()), k
+
+
+@pytest.mark.parametrize("scheme,theta", [(EMU_MCS, TH_MCS), (EMU_HV, TH_HV)], ids=["MCS", "HV"])
+def test_mcs_and_hv_on_ring_and_strips(emu, scheme, theta):
+    """hadi_pass_a_strip_sch (predictor and corrector at 2, 4 and 8 nodes per lane; the corrector on paired strips, whose
+    predictor runs on the shared ring) and hadi_pass_a_sch (`cs_strips` = 0, and the one-node-per-lane ring) against the
+    restatement: the shapes of test_craig_sneyd_on_barrier_free_strips -- a short last strip, a strip without a partner, r_f != 0."""
+    emu.emu_set_tuning(b"strip", 1)
+    try:
+        for m1, m2, N, ks, r_f, want in ((100, 20, 3, [100.0, 92.0], 0.01, (2, 1)), (200, 26, 2, [100.0], 0.0, (4, 1)),
+                                         (300, 34, 2, [104.0], 0.02, (8, 1)), (700, 20, 2, [100.0], 0.01, (8, 2))):
+            assert _plan(emu, m1, m2, len(ks), 1) == want + (True, False)
+            for cs_strips in (1, 0):
+                emu.emu_set_tuning(b"cs_strips", cs_strips)
+                _run_pc(emu, m1, m2, ks, scheme, 1, theta=theta, r_f=r_f, N=N)
+    finally:
+        emu.emu_set_tuning(b"reset", 0)
+    _run_pc(emu, 40, 12, [100.0, 91.0], scheme, 8, theta=theta, r_f=0.01, N=3)  # one node per lane
+
+
+@pytest.mark.parametrize("scheme,theta", [(EMU_CS, 0.5), (EMU_MCS, TH_MCS), (EMU_HV, TH_HV)], ids=["CS", "MCS", "HV"])
+def test_predictor_and_corrector_split_between_strips_and_ring(emu, scheme, theta):
+    """`cs_strips` = 2 (only the predictor on strips, the corrector on the shared ring) and 3 (the other way round): the strip
+    and ring kernels hand each other the R1 / C2 carry-over rows, so each must read what the other wrote."""
+    emu.emu_set_tuning(b"strip", 1)
+    try:
+        for m1, m2, N, ks, r_f in ((100, 20, 2, [100.0, 92.0], 0.01), (200, 26, 2, [100.0], 0.0), (300, 34, 2, [104.0], 0.02)):
+            for cs_strips in (2, 3):
+                emu.emu_set_tuning(b"cs_strips", cs_strips)
+                _run_pc(emu, m1, m2, ks, scheme, 1, theta=theta, r_f=r_f, N=N)
+    finally:
+        emu.emu_set_tuning(b"reset", 0)
+
+
+MIXED = dict(Ns=[3, 1, 2], dts=[1.0 / 3.0, 0.45, 0.35], pars=PARS3)
+
+
+@pytest.mark.parametrize("path,m1,m2,tuning,want", [
+    ("ring", 40, 12, {}, (1, 1, False, False)),
+    ("strips4", 200, 26, {"strip": 1}, (4, 1, True, False)),
+    ("strips8", 300, 34, {"strip": 1}, (8, 1, True, False)),
+    ("paired", 700, 20, {"strip": 1}, (8, 2, True, False)),
+    ("pairs", 256, 54, {"strip": 1, "pair_strips": 1}, (4, 1, True, True)),
+])
+def test_mixed_maturities_and_per_instance_parameters(emu, path, m1, m2, tuning, want):
+    """Multi-maturity batches (N_i = 3, 1, 2 with their own delta_t_i) with per-instance rho / sigma / kappa / eta on every row
+    kernel: each kernel must take dt, theta dt, e_n / e_{n-1} and the MCS / HV constants from ITS instance's parameter block and
+    leave the instances that have taken their last step alone (emu_solve poisons their Y / R1 / C2 and returns 5 if a row pass
+    wrote there).  Douglas (European, American in the P representation), CS, MCS, HV; on `pairs` (hadi_pass_a_pairs) the
+    predictor-corrector schemes run on the shared ring."""
+    for k, v in tuning.items():
+        emu.emu_set_tuning(k.encode(), v)
+    try:
+        ks, tw = [100.0, 93.0, 106.0], 1 if tuning else 8
+        assert _plan(emu, m1, m2, 3, tw) == want
+        _run_pc(emu, m1, m2, ks, 0, tw, r_f=0.01, **MIXED)
+        _run_pc(emu, m1, m2, ks, EMU_AMP, tw, variant=O.AM, **MIXED)
+        _run_pc(emu, m1, m2, ks, EMU_CS, tw, theta=0.5, r_f=0.01, **MIXED)
+        _run_pc(emu, m1, m2, ks, EMU_MCS, tw, theta=TH_MCS, r_f=0.01, **MIXED)
+        _run_pc(emu, m1, m2, ks, EMU_HV, tw, theta=TH_HV, r_f=0.01, **MIXED)
+    finally:
+        emu.emu_set_tuning(b"reset", 0)
+
+
+def test_per_instance_step_grids_are_refused_with_dividends(emu):
+    m1, m2 = 40, 12
+    vs, vv, ds, dv, U0 = Cm.oracle_grids(m1, m2, [100.0])
+    par = np.array([[Cm.RHO, Cm.SIGMA, Cm.KAPPA, Cm.ETA]])
+    dd = [np.array(x, dtype=np.float64) for x in Cm.DIVS]
+    Ni, dti = np.array([4], dtype=np.int32), np.array([0.25])
+    U = U0.copy()
+    rc = emu.emu_solve(1, m1, m2, 4, C.c_double(0.25), C.c_double(Cm.THETA), C.c_double(Cm.R_D), C.c_double(0.0), _P(par),
+                       O.DIV, _P(vs), _P(vv), _P(ds), _P(dv), _P(U), _P(U0), None, 8, len(dd[0]), _P(dd[0]), _P(dd[1]),
+                       _P(dd[2]), 64, 0, 0, None, Ni.ctypes.data_as(C.POINTER(C.c_int)), _P(dti))
+    assert rc == 3
+
+
+def _random_pc_case(rng):
+    """One random predictor-corrector problem (the emulator's own generator, independent of _random_case and its seeds)."""
+    scheme = rng.choice([EMU_CS, EMU_MCS, EMU_HV])
+    theta = rng.choice({EMU_CS: [0.0, 0.3, 0.5, 1.0], EMU_MCS: [0.25, TH_MCS, 0.5, 0.75, 1.0],
+                        EMU_HV: [0.5, 0.6, TH_HV, 1.0]}[scheme])
+    cls = rng.choice(["one", "two", "four", "eight", "wide", "tall"])
+    m1 = {"one": rng.randint(8, 64), "two": rng.randint(65, 128), "four": rng.randint(129, 256), "eight": rng.randint(257, 512),
+          "wide": rng.randint(513, 1024), "tall": rng.randint(20, 140)}[cls]
+    if cls == "tall":
+        m2 = rng.randint(264, 527)
+    elif rng.random() < 0.2:
+        m2 = rng.randint(3, 5)
+    else:
+        m2 = rng.randint(6, 70)
+    n = rng.choice([1, 2, 3])
+    if rng.random() < 0.5:
+        pars = [(rng.uniform(-0.9, 0.5), rng.uniform(0.1, 0.6), rng.uniform(0.5, 3.0), rng.uniform(0.02, 0.1)) for _ in range(n)]
+    else:
+        pars = None
+    if rng.random() < 0.5:
+        Ns = [rng.randint(1, 3) for _ in range(n)]
+        dts = [rng.uniform(0.25, 1.5) / k for k in Ns]
+    else:
+        Ns = dts = None
+    tuning = {}
+    if rng.random() < 0.6: tuning["strip"] = 1
+    if rng.random() < 0.6: tuning["cs_strips"] = rng.choice([0, 1, 2, 3])
+    if cls == "four" and rng.random() < 0.5: tuning["pair_strips"] = 1
+    if rng.random() < 0.2: tuning["strip_blocks"] = rng.choice([2, 3])
+    if rng.random() < 0.25: tuning["col_prefetch"] = 1
+    if rng.random() < 0.25: tuning["tile_interleave"] = 1
+    N = rng.randint(1, 3)
+    if theta == 0.0:  # explicit Craig-Sneyd: one step (more steps of these sizes grow without bound, round-off with them)
+        N, Ns = 1, Ns and [1] * n
+    return dict(m1=m1, m2=m2, N=N, strikes=[rng.uniform(85, 115) for _ in range(n)], scheme=scheme, theta=theta,
+                r_f=rng.choice([0.0, 0.01, 0.03, Cm.R_D, 0.06]), target_waves=rng.choice([1, 8]), tuning=tuning, pars=pars,
+                Ns=Ns, dts=dts)
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_random_predictor_corrector_cases_vs_references(emu, seed):
+    """8 x 20 random CS / MCS / HV problems: theta off the usual values (MCS above 1/2 and at 1, HV at and above 1/2, CS at 0
+    and 1), r_f = 0, r_f = r_d (the library then keeps the strips off) and r_f > r_d, every streaming shape class incl. 9 .. 16
+    column chunks and grids of 4 .. 6 v-nodes, per-instance parameters and maturities, `cs_strips` 0 .. 3, strip / pair-strip /
+    strip-block / column-pass overrides -- each instance's full field against its own reference solve."""
+    import random
+    rng = random.Random(7000 + seed)
+    for k in range(20):
+        c = _random_pc_case(rng)
+        for _ in range(50):  # well-conditioned s-grids only (see test_random_shapes_and_kernel_choices_vs_oracle)
+            d = np.diff(Cm.oracle_grids(c["m1"], 8, c["strikes"])[0], axis=1)
+            if np.maximum(d[:, 1:] / d[:, :-1], d[:, :-1] / d[:, 1:]).max() <= 30.0:
+                break
+            c["strikes"] = [rng.uniform(85, 115) for _ in c["strikes"]]
+        for key, val in c["tuning"].items():
+            assert emu.emu_set_tuning(key.encode(), val) == 0
+        try:
+            _run_pc(emu, c["m1"], c["m2"], c["strikes"], c["scheme"], c["target_waves"], theta=c["theta"], r_f=c["r_f"], N=c["N"],
+                    Ns=c["Ns"], dts=c["dts"], pars=c["pars"])
         except AssertionError as e:
             raise AssertionError("seed %d case %d: %r" % (seed, k, c)) from e
         finally:

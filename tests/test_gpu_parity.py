@@ -333,6 +333,41 @@ def test_per_instance_parameters_and_maturities(solver):
         _assert_field(U[k], Uo)
 
 
+@pytest.mark.parametrize("variant,kind", [(H.EU, "EU"), (H.AM, "AM-P")])
+@pytest.mark.parametrize("m1,m2,tuning,want", [
+    (200, 60, {"strip": 1, "pair_strips": 0}, "hadi_pass_a_strip<4,%s>"), (300, 80, {"strip": 1}, "hadi_pass_a_strip<8,%s>"),
+    (600, 40, {"strip": 1}, "hadi_pass_a_strip<8,%s,double,2>"), (256, 128, {"strip": 1, "pair_strips": 1}, "hadi_pass_a_pairs<%s>")])
+def test_per_instance_maturities_on_strips(solver, variant, kind, m1, m2, tuning, want):
+    """Douglas multi-maturity batches with per-instance model parameters on the strip kernels (4 and 8 nodes per lane, paired
+    strips, two strips per wavefront), European and American in the P representation: the blocks of the instances that have
+    taken their last step leave the row pass early (after draining their row fetches) beside blocks that go on."""
+    strikes = [90.0, 100.0, 110.0, 95.0]
+    Ts, Ns = [0.5, 1.0, 0.8, 0.25], [5, 8, 3, 1]
+    rhos, sigmas, kappas, etas = [-0.9, -0.5, 0.0, 0.3], [0.3, 0.5, 0.2, 0.4], [1.5, 2.0, 0.5, 3.0], [0.04, 0.09, 0.02, 0.06]
+    per = {"rho_i": rhos, "sigma_i": sigmas, "kappa_i": kappas, "eta_i": etas, "N_i": Ns,
+           "delta_t_i": [t / n for t, n in zip(Ts, Ns)]}
+    grids, U0 = _batch(m1, m2, strikes)
+    U, lam = U0.copy(), np.zeros_like(U0)
+    american = variant == H.AM
+    tuning = dict(tuning, team_launch=0, small_grid=0)
+    for k, v in tuning.items():
+        solver.set_tuning(k, v)
+    try:
+        solver.DO_timestepping(m1, m2, 1, 1.0, Cm.THETA, Cm.R_D, 0.01, 0.0, 0.1, 1.0, 0.04, grids, U, variant=variant,
+                               U_0=U0 if american else None, lambda_bar=lam if american else None, per_instance=per)
+        d = solver.describe_last_sweep()
+    finally:
+        for k in tuning:
+            solver.set_tuning(k, -1)
+    assert want % kind in d, d
+    for k in range(len(strikes)):
+        p = O.make_params(m1, m2, Ns[k], Ts[k] / Ns[k], Cm.THETA, Cm.R_D, 0.01, rhos[k], sigmas[k], kappas[k], etas[k], variant)
+        Uo, lo, _ = O.solve(p, grids.Vec_s[k], grids.Vec_v[k], grids.Delta_s[k], grids.Delta_v[k], U0[k], U0[k])
+        _assert_field(U[k], Uo)
+        if american:
+            assert np.abs(lam[k] - lo).max() <= 1e-8 * max(1.0, np.abs(lo).max())
+
+
 @pytest.mark.parametrize("variant", [H.DIV, H.AM_DIV], ids=["DIV", "AM_DIV"])
 @pytest.mark.parametrize("m1,m2,path", [(50, 25, "small"), (50, 25, "graph"), (50, 25, "stream"), (150, 60, "graph")])
 def test_dividends_with_per_instance_maturities(solver, variant, m1, m2, path):
