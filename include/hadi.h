@@ -174,7 +174,15 @@ int hadi_get_timing(const hadi_ctx *ctx, hadi_timing *out);
  *   "small_seq"   ... European / dividend sweeps of such grids on the one-wavefront-per-instance kernel that solves the
  *                 lines sequentially, one per lane: -1 automatic (default: batches of more instances than CUs), 0 never
  *                 (the block-per-instance kernel, which the American sweeps always use), 1 always
- *   "graph"       hipGraph replay of the time loop for small batches (default 1)
+ *   "graph"       hipGraph replay of the time loop for small batches (default 1).  The handle caches up to 8 captured loops,
+ *                 keyed by everything their nodes bake in: the launch geometry of every sub-batch, the scheme, variant and
+ *                 precision, the steps that carry a dividend, and every device address the loop uses (the library's buffers --
+ *                 rs_tab and the fp64 packed U of an fp32-state sweep among them -- and the caller's s-grid).  Whenever a call
+ *                 frees a buffer to grow it, the whole cache is dropped first, so a replay never touches freed memory.
+ *                 Read-only counters, cumulative over the handle's life (hadi_get_tuning only; hadi_set_tuning returns
+ *                 HADI_ERR_INVALID): "graph_captures" loops captured, "graph_replays" loops replayed from the cache,
+ *                 "graph_drops" cache entries destroyed because a buffer was freed, "graph_evictions" entries evicted as least
+ *                 recently used (counted apart from the drops)
  *   "american_p"  American sweeps keep P = U_bar - dt*lambda_bar in place of U and no lambda_bar array whenever every
  *                 payoff of the batch depends on s only (default 1; 0 = always the explicit (U, lambda_bar) pair)
  *   "strip"       strip row pass: -1 automatic (default), 0 never, 1 whenever the geometry allows it

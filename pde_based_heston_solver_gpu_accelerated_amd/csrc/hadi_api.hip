@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -46,6 +47,9 @@ struct Ctx {
     struct GraphEntry { std::string key; hipGraph_t graph; hipGraphExec_t exec; unsigned long long stamp; };
     std::vector<GraphEntry> graphs;
     unsigned long long graph_clock = 0;
+    // cumulative per handle (hadi_get_tuning "graph_captures" / "graph_replays" / "graph_drops" / "graph_evictions"): time loops
+    // captured, replayed from the cache, cache entries destroyed because a buffer was freed (ensure), evicted as least recently used
+    unsigned long long graph_captures = 0, graph_replays = 0, graph_drops = 0, graph_evictions = 0;
     int use_graph = 1;
     int graph_max_melems = 8;  // hipGraph replay for batches of up to this many Mi state elements (hadi_set_tuning "graph_max_melems")
     int use_small = 1;  // LDS-resident one-launch path for small grids
@@ -123,10 +127,20 @@ int fail(Ctx *c, int code, const char *fmt, ...) {
                         __FILE__, __LINE__);                                                      \
     } while (0)
 
+// Destroys every cached time loop (the caller has synchronised the stream: none of them is in flight).
+void drop_graphs(Ctx *c) {
+    for (auto &g : c->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
+    c->graph_drops += c->graphs.size();
+    c->graphs.clear();
+}
+
+// Grows a buffer.  A captured time loop bakes the addresses of the handle's buffers into its nodes, so freeing any of them
+// empties the graph cache first: no later call can replay a freed address, whatever the graph key holds.
 int ensure(Ctx *c, DevBuf &b, size_t bytes) {
     if (bytes <= b.cap) return HADI_OK;
     if (b.p) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
+        drop_graphs(c);
         HIP_TRY(c, hipFree(b.p));
         b.p = nullptr;
         b.cap = 0;
@@ -1056,16 +1070,24 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     }
     // Small batches are launch-bound (2*N dependent launches of a few microseconds each): replay the loop
     // from a cached hipGraph.  Every kernel argument is baked into the nodes, so the key is everything they
-    // depend on; the library's own buffers are stable between calls.
+    // depend on.  Addresses: every pointer of both argument blocks, and every array enqueue_body names itself (the fp64 packed
+    // U, which the table kernel and the fp32 dividend steps use even when the state is fp32; lambda_bar, payoff, U_temp, the
+    // dividend tables and the caller's s-grid).  The library's buffers only move when ensure() grows one, and that empties the
+    // cache (drop_graphs).
     const bool graphable = c->use_graph && !prof && !d.debug && (long long)d.n * L.inst_stride <= ((long long)c->graph_max_melems << 20);
     if (graphable) {
         std::string key;
         auto put = [&](const void *p_, size_t nbytes) { key.append(static_cast<const char *>(p_), nbytes); };
         {  // field by field: struct padding is not initialised
-            const void *ptrs[] = {a.pay_mis, a.U, a.Y, a.LAM, a.U0, a.scoef, a.b2row, a.rowc, a.pb, a.rinv, a.ipar, a.R1, a.C2, av.U, a.err};
+            const void *pa[HADI_SWEEP_ARGS_NPTRS], *pv[HADI_SWEEP_ARGS_NPTRS];
+            hadi_sweep_args_ptrs(a, pa);
+            hadi_sweep_args_ptrs(av, pv);
+            const void *own[] = {c->U.p, c->LAM.p, c->U0.p, c->UT.p, c->div_flag.p, c->div_amt.p, c->div_pct.p, d.d_vec_s};
             const int ints[] = {a.debug, a.L.m1, a.L.m2, a.L.B, a.L.G, a.L.P, a.n_inst, a.R, a.ntiles, a.ctiles, a.btpw, a.bgroups,
                                 a.american, a.pos_m1, d.scheme, d.prec, (int)amp, (int)two_streams, nsub, pl.row_seq, pl.col_seq, pl.use_pairs, pl.use_strip, pl.RS, pl.sblocks, pl.grid_as, pl.grid_a, pl.grid_b, pl.block_b, pl.W, (int)pl.smem_a, (int)pl.smem_b};
-            put(ptrs, sizeof(ptrs));
+            put(pa, sizeof(pa));
+            put(pv, sizeof(pv));
+            put(own, sizeof(own));
             put(ints, sizeof(ints));
         }
         for (const auto &sbt : subs) {  // the launch geometry of EVERY sub-batch is baked into the nodes (unequal halves on two
@@ -1076,14 +1098,11 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
             put(geo, sizeof(geo));
         }
         put(&d.Nmax, sizeof(int)); put(&d.dt0, sizeof(double));
-        put(&d.variant, sizeof(int)); put(&d.d_vec_s, sizeof(void *));
-        void *ut = c->UT.p; put(&ut, sizeof(ut));
+        put(&d.variant, sizeof(int));
         if (have_div) {  // amounts / percentages / per-instance tables are re-uploaded every call; the node list
                          // only depends on which steps carry a dividend launch
             put(&flag_stride, sizeof(int));
             put(div_step.data(), div_step.size());
-            void *fl = c->div_flag.p, *am = c->div_amt.p, *pc = c->div_pct.p;
-            put(&fl, sizeof(fl)); put(&am, sizeof(am)); put(&pc, sizeof(pc));
         }
         Ctx::GraphEntry *hit = nullptr;
         for (auto &g : c->graphs)
@@ -1096,6 +1115,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
                 (void)hipGraphExecDestroy(c->graphs[lru].exec);
                 (void)hipGraphDestroy(c->graphs[lru].graph);
                 c->graphs.erase(c->graphs.begin() + lru);
+                c->graph_evictions++;
             }
             hipGraph_t graph = nullptr;
             hipGraphExec_t exec = nullptr;
@@ -1110,6 +1130,9 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
             HIP_TRY(c, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
             c->graphs.push_back(Ctx::GraphEntry{key, graph, exec, 0});
             hit = &c->graphs.back();
+            c->graph_captures++;
+        } else {
+            c->graph_replays++;
         }
         hit->stamp = ++c->graph_clock;
         HIP_TRY(c, hipGraphLaunch(hit->exec, s));
@@ -1321,6 +1344,9 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
     }
     if ((rc = to_device(c, p->memspace, p->U, n * m, c->natU, &d.d_natU))) return rc;
     if ((rc = to_device(c, p->memspace, p->U_0, n * m, c->natU0, &d.d_natU0))) return rc;
+    // the buffers the outputs pass through, grown before the sweep: growing one after it would drop the loop it just captured
+    if (p->memspace != HADI_MEM_DEVICE && (rc = ensure(c, c->natOut, n * m * 8))) return rc;
+    if (pick && ((rc = ensure(c, c->prices, n * 8)) || (rc = ensure(c, c->status, n * sizeof(int))))) return rc;
 
     HadiPlan pl;
     if ((rc = run_sweep(c, d, pl))) return rc;
@@ -1329,10 +1355,7 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
     double *const host_dst = debug ? debug_out : p->U;
     double *d_out;
     if (p->memspace == HADI_MEM_DEVICE) d_out = host_dst;
-    else {
-        if ((rc = ensure(c, c->natOut, n * m * 8))) return rc;
-        d_out = ptr<double>(c->natOut);
-    }
+    else d_out = ptr<double>(c->natOut);
     hipLaunchKernelGGL(hadi_unpack_kernel, dim3(grid1d(n * m)), dim3(256), 0, c->stream, pl.L, n,
                        debug == 1 ? ptr<double>(c->Y) : ptr<double>(c->U), d_out);
     if (p->memspace == HADI_MEM_HOST && (rc = from_device(c, p->memspace, host_dst, d_out, n * m))) return rc;
@@ -1349,7 +1372,6 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
     }
     std::vector<int> hstatus;
     if (pick) {
-        if ((rc = ensure(c, c->prices, n * 8)) || (rc = ensure(c, c->status, n * sizeof(int)))) return rc;
         hipLaunchKernelGGL(hadi_pick_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, pl.L, n, d.d_vec_s, d.d_vec_v,
                            ptr<double>(c->U), S_0, per_inst_v0 ? ptr<double>(c->v0_i) : (const double *)nullptr, V_0,
                            ptr<double>(c->prices), 1, ptr<int>(c->status));
@@ -1391,6 +1413,11 @@ int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, doubl
     }
     // s-grids: replicate the caller's rows into the 6 groups
     const double *src_s, *src_ds;
+    // (natOut stages delta_s here and takes J and the base prices after the sweep; prices / status: the pick.  All grown before
+    // the sweep: growing one after it would drop the loop it just captured)
+    if ((rc = ensure(c, c->natOut, (size_t)n0 * std::max(m1, 6) * 8)) || (rc = ensure(c, c->prices, n * 8)) ||
+        (rc = ensure(c, c->status, n * sizeof(int))))
+        return rc;
     if ((rc = to_device(c, p->memspace, p->vec_s, (size_t)n0 * (m1 + 1), c->natU, &src_s))) return rc;
     if ((rc = to_device(c, p->memspace, p->delta_s, (size_t)n0 * m1, c->natOut, &src_ds))) return rc;
     std::vector<int> sel_a(n), sel_b(n);
@@ -1440,14 +1467,12 @@ int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, doubl
 
     HadiPlan pl;
     if ((rc = run_sweep(c, d, pl))) return rc;
-    if ((rc = ensure(c, c->prices, n * 8)) || (rc = ensure(c, c->status, n * sizeof(int)))) return rc;
     hipLaunchKernelGGL(hadi_pick_kernel, dim3((n + 63) / 64), dim3(64), 0, s, pl.L, n, d.d_vec_s, d.d_vec_v,
                        ptr<double>(c->U), S_0, ptr<double>(c->v0_i), V_0, ptr<double>(c->prices), 1, ptr<int>(c->status));
     // J(k, param) = (pert - base) / eps on the device (jacobian_computation.cpp:329,360): with HADI_MEM_DEVICE the rows
     // never leave HBM (hadi_lm_partials_device reduces them there); only the n status words come back
     double *dJ = J, *db = base_prices;
     if (p->memspace == HADI_MEM_HOST) {
-        if ((rc = ensure(c, c->natOut, (size_t)n0 * 6 * 8))) return rc;
         dJ = ptr<double>(c->natOut);
         db = dJ + (size_t)n0 * 5;
     }
@@ -1482,7 +1507,7 @@ void release_handle(Ctx *c) {
                       &c->rinv, &c->rwork, &c->ipar, &c->par8, &c->g_s, &c->g_v, &c->g_ds, &c->g_dv, &c->src_v,
                       &c->src_dv, &c->sel_a, &c->sel_b, &c->v0_i, &c->natU, &c->natU0, &c->natOut, &c->prices,
                       &c->status, &c->div_flag, &c->div_amt, &c->div_pct, &c->V, &c->R1, &c->C2, &c->pay_mis, &c->Uf, &c->Yf,
-                      &c->order, &c->lm31, &c->team};
+                      &c->order, &c->lm31, &c->team, &c->rs_tab};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &g : c->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
@@ -1632,6 +1657,9 @@ int hadi_set_tuning(hadi_ctx *ctx, const char *key, int value) {
     else if (!std::strcmp(key, "small_waves")) {
         if (value != 0 && value != 4 && value != 8) return fail(c, HADI_ERR_INVALID, "small_waves must be 0, 4 or 8");
         c->tune.small_waves = value;
+    } else if (!std::strcmp(key, "graph_captures") || !std::strcmp(key, "graph_replays") || !std::strcmp(key, "graph_drops") ||
+               !std::strcmp(key, "graph_evictions")) {
+        return fail(c, HADI_ERR_INVALID, "'%s' is a read-only counter", key);
     } else return fail(c, HADI_ERR_INVALID, "unknown tuning key '%s'", key);
     return HADI_OK;
 }
@@ -1665,6 +1693,10 @@ int hadi_get_tuning(const hadi_ctx *ctx, const char *key, int *value) {
     else if (!std::strcmp(key, "model_pring_row_ps")) *value = c->tune.pring_row_ps;
     else if (!std::strcmp(key, "model_pring_fixed_ns")) *value = c->tune.pring_fixed_ns;
     else if (!std::strcmp(key, "small_waves")) *value = c->tune.small_waves;
+    else if (!std::strcmp(key, "graph_captures")) *value = (int)std::min<unsigned long long>(c->graph_captures, INT_MAX);
+    else if (!std::strcmp(key, "graph_replays")) *value = (int)std::min<unsigned long long>(c->graph_replays, INT_MAX);
+    else if (!std::strcmp(key, "graph_drops")) *value = (int)std::min<unsigned long long>(c->graph_drops, INT_MAX);
+    else if (!std::strcmp(key, "graph_evictions")) *value = (int)std::min<unsigned long long>(c->graph_evictions, INT_MAX);
     else return HADI_ERR_INVALID;
     return HADI_OK;
 }

@@ -29,6 +29,18 @@ struct HadiSweepArgs {
     int debug;       // test hooks, 0 in production (hadi_set_tuning "debug_fault"): HADI_DEBUG_* bits
 };
 
+// Every address a HadiSweepArgs carries.  A captured time loop (hadi_api.hip, run_sweep) bakes the argument block into its
+// nodes, so the graph key lists all of them through this helper.  A field added to the struct trips the size check below:
+// a pointer goes into the list, anything else into the key's integers.  tests/test_emu_kernel_logic.py checks that every
+// pointer-sized word outside L and the ints is listed.
+#define HADI_SWEEP_ARGS_NPTRS 15
+inline void hadi_sweep_args_ptrs(const HadiSweepArgs &a, const void *(&p)[HADI_SWEEP_ARGS_NPTRS]) {
+    const void *const v[HADI_SWEEP_ARGS_NPTRS] = {a.U, a.Y, a.LAM, a.R1, a.C2, a.rs_tab, a.U0, a.pay_mis,
+                                                  a.scoef, a.b2row, a.rowc, a.pb, a.rinv, a.ipar, a.err};
+    for (int k = 0; k < HADI_SWEEP_ARGS_NPTRS; k++) p[k] = v[k];
+}
+static_assert(sizeof(HadiSweepArgs) == 224, "HadiSweepArgs changed: update hadi_sweep_args_ptrs and the graph key in run_sweep");
+
 // Device-side error codes (bits of *HadiSweepArgs.err)
 #define HADI_DEVERR_RENDEZVOUS 1  // a pair rendezvous of the two-wavefront rows ran out of polls: the partner's token never came
 // Test hooks (bits of HadiSweepArgs.debug)

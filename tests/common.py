@@ -139,3 +139,15 @@ class OracleSolver:
                                                               total_size, theta, points, n, grids, U_0, ws, dividends):
         return self._mm_base(O.AM_DIV, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, theta, points, grids, ws.U, U_0,
                              dividends)
+
+
+GRAPH_COUNTERS = ("graph_captures", "graph_replays", "graph_drops", "graph_evictions")
+
+
+def graph_counts(solver):
+    """The handle's cumulative graph-cache counters (hadi.h, "graph"): captures, replays, drops, evictions."""
+    return {k.split("_", 1)[1]: solver.get_tuning(k) for k in GRAPH_COUNTERS}
+
+
+def graph_delta(before, after):
+    return {k: after[k] - before[k] for k in before}

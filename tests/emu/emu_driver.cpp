@@ -7,6 +7,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -252,6 +254,41 @@ extern "C" int emu_col_tiles(int m1, int m2, int n_inst, int target_waves, int i
     const HadiTileSet ts = hadi_pb_tiles(a, grp);
     for (int i = 0; i < ts.cnt; i++) out[i] = hadi_pb_tile(ts, i);
     return ts.cnt;
+}
+
+// The graph key's view of HadiSweepArgs (hadi_sweep_args_ptrs).  Every 8-byte word of the struct that holds no part of L or of
+// an int field is a pointer; each one is set in turn to a value no other field holds, and the helper's list must change.
+// Writes the byte offsets of the words whose change the list misses to `out` and returns their number (0: the key sees every
+// pointer field).  `nptr_words` receives how many words were probed.
+extern "C" int emu_sweep_args_unkeyed(int *out, int cap, int *nptr_words) {
+    struct Span { size_t off, len; };
+#define HADI_SPAN(f) Span{offsetof(HadiSweepArgs, f), sizeof(HadiSweepArgs::f)}
+    const Span ints[] = {HADI_SPAN(L), HADI_SPAN(n_inst), HADI_SPAN(R), HADI_SPAN(ntiles), HADI_SPAN(RS), HADI_SPAN(sblocks),
+                         HADI_SPAN(ctiles), HADI_SPAN(btpw), HADI_SPAN(bgroups), HADI_SPAN(tile_il), HADI_SPAN(american),
+                         HADI_SPAN(pos_m1), HADI_SPAN(debug)};
+#undef HADI_SPAN
+    HadiSweepArgs base;
+    std::memset(&base, 0, sizeof base);
+    const void *p0[HADI_SWEEP_ARGS_NPTRS];
+    hadi_sweep_args_ptrs(base, p0);
+    int bad = 0, words = 0;
+    for (size_t off = 0; off + 8 <= sizeof(HadiSweepArgs); off += 8) {
+        bool other = false;
+        for (const Span &s : ints) other = other || (off < s.off + s.len && s.off < off + 8);
+        if (other) continue;
+        words++;
+        HadiSweepArgs b = base;
+        const unsigned long long v = 0x5000 + off;
+        std::memcpy(reinterpret_cast<char *>(&b) + off, &v, 8);
+        const void *p1[HADI_SWEEP_ARGS_NPTRS];
+        hadi_sweep_args_ptrs(b, p1);
+        if (!std::memcmp(p0, p1, sizeof p0)) {
+            if (bad < cap) out[bad] = (int)off;
+            bad++;
+        }
+    }
+    *nptr_words = words;
+    return bad;
 }
 
 // the fraction of its CU-rounds the plan's row pass leaves idle (decides one or two streams: hadi_plan_row_idle), x 1e6

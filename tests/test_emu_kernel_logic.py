@@ -770,3 +770,15 @@ def test_random_predictor_corrector_cases_vs_references(emu, seed):
             raise AssertionError("seed %d case %d: %r" % (seed, k, c)) from e
         finally:
             emu.emu_set_tuning(b"reset", 0)
+
+
+def test_graph_key_lists_every_pointer_of_the_sweep_arguments(emu):
+    """A captured time loop bakes the whole HadiSweepArgs block into its nodes, so the graph key (run_sweep) takes every address
+    in it from hadi_sweep_args_ptrs.  Each pointer-sized word of the struct outside L and the int fields -- rs_tab, the
+    paired strips' coupling table, among them -- must change that list when it changes; a pointer the helper forgets would let
+    a call replay a graph whose nodes hold another buffer's address."""
+    out = (C.c_int * 32)()
+    words = C.c_int()
+    bad = emu.emu_sweep_args_unkeyed(out, 32, C.byref(words))
+    assert words.value == 15, words.value  # U Y LAM R1 C2 rs_tab U0 pay_mis scoef b2row rowc pb rinv ipar err
+    assert bad == 0, "pointer words missing from the graph key at byte offsets %s" % list(out[:min(bad, 32)])

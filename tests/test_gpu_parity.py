@@ -171,11 +171,15 @@ def test_small_grid_kernel_and_streaming_kernels_agree(solver, variant, name):
         solver.set_tuning("graph", graph)
         solver.set_tuning("small_seq", seq)  # (European / dividends: sequential one-wavefront kernel or the block kernel)
         try:
+            g0 = Cm.graph_counts(solver)
             grids, U0, U, lam = _hadi_solve(solver, m1, m2, N, strikes, variant, want_lambda=variant in (H.AM, H.AM_DIV))
+            dg = Cm.graph_delta(g0, Cm.graph_counts(solver))
         finally:
             solver.set_tuning("small_grid", 1)
             solver.set_tuning("graph", 1)
             solver.set_tuning("small_seq", -1)
+        # only the streaming run with graphs on goes through the cache (captured or replayed); the others launch directly
+        assert dg["captures"] + dg["replays"] == (1 if (small, graph) == (0, 1) else 0), ((small, graph, seq), dg)
         fields.append((U, lam))
     Uo, lamo, _ = O.solve_batch(p, grids.Vec_s, grids.Vec_v, grids.Delta_s, grids.Delta_v, U0, U0, want_lambda=True)
     for U, lam in fields:
@@ -369,7 +373,7 @@ def test_per_instance_maturities_on_strips(solver, variant, kind, m1, m2, tuning
 
 
 @pytest.mark.parametrize("variant", [H.DIV, H.AM_DIV], ids=["DIV", "AM_DIV"])
-@pytest.mark.parametrize("m1,m2,path", [(50, 25, "small"), (50, 25, "graph"), (50, 25, "stream"), (150, 60, "graph")])
+@pytest.mark.parametrize("m1,m2,path", [(50, 25, "small"), (50, 25, "graph"), (50, 25, "stream"), (150, 60, "graph"), (150, 60, "auto")])
 def test_dividends_with_per_instance_maturities(solver, variant, m1, m2, path):
     """Multi-maturity batches with a shared dividend schedule (compute_*_multi_maturity_american_dividends,
     heston_calibration.cpp:2936-3243): every instance pays the dividends on ITS OWN step grid (n*dt_k evaluated in
@@ -383,15 +387,25 @@ def test_dividends_with_per_instance_maturities(solver, variant, m1, m2, path):
     div = H.Dividends(*Cm.DIVS)
     solver.set_tuning("small_grid", 1 if path == "small" else 0)
     solver.set_tuning("graph", 0 if path == "stream" else 1)
+    # ("graph": the captured time loop, so not the instance-resident kernel that the default picks for a few European
+    # instances of 150x60; "auto": whatever the default picks)
+    solver.set_tuning("team_launch", 0 if path == "graph" else -1)
     try:
-        for _ in range(2 if path == "graph" else 1):  # second call replays the cached graph
+        for call in range(2 if path == "graph" else 1):  # second call replays the cached graph
             U[...] = U0
+            g0 = Cm.graph_counts(solver)
             solver.DO_timestepping(m1, m2, 1, 1.0, Cm.THETA, Cm.R_D, Cm.R_F, Cm.RHO, Cm.SIGMA, Cm.KAPPA, Cm.ETA, grids, U,
                                    variant=variant, U_0=U0, lambda_bar=lam if variant == H.AM_DIV else None,
                                    dividends=div, per_instance=per)
+            dg = Cm.graph_delta(g0, Cm.graph_counts(solver))
+            if path in ("small", "stream"):
+                assert dg["captures"] == dg["replays"] == 0, dg
+            elif call == 1:
+                assert dg["replays"] == 1 and dg["captures"] == 0 and dg["drops"] == 0, dg
     finally:
         solver.set_tuning("small_grid", 1)
         solver.set_tuning("graph", 1)
+        solver.set_tuning("team_launch", -1)
     for k in range(len(strikes)):
         p = O.make_params(m1, m2, Ns[k], Ts[k] / Ns[k], Cm.THETA, Cm.R_D, Cm.R_F, Cm.RHO, Cm.SIGMA, Cm.KAPPA, Cm.ETA,
                           variant, Cm.DIVS)

@@ -258,15 +258,21 @@ def test_two_stream_sweep_matches_one_stream(solver, m1, m2, N, n, variant, fp32
     american = v in (H.AM, H.AM_DIV)
     dt = Cm.T / 500
     out = {}
-    for streams in (1, 2, 2, 0):  # (twice on two streams: the second call replays the cached graph where there is one)
+    graphed = n * (m1 + 1) * (m2 + 1) <= (4 << 20)  # (within "graph_max_melems" = 8 Mi packed elements: 160 x 512x256 is not)
+    for call, streams in enumerate((1, 2, 2, 0)):  # (twice on two streams: the second call replays the cached graph where there is one)
         solver.set_tuning("streams", streams)
         try:
             U, lam = U0.copy(), np.zeros_like(U0)
+            g0 = Cm.graph_counts(solver)
             solver.DO_timestepping(m1, m2, N, dt, Cm.THETA, Cm.R_D, 0.01, Cm.RHO, Cm.SIGMA, Cm.KAPPA, Cm.ETA, grids, U, variant=v,
                                    U_0=U0, lambda_bar=lam if american else None,
                                    dividends=H.Dividends(*Cm.DIVS) if v in (H.DIV, H.AM_DIV) else None,
                                    state_precision=H.STATE_FP32 if fp32 else H.STATE_FP64)
             path = solver.describe_last_sweep()
+            dg = Cm.graph_delta(g0, Cm.graph_counts(solver))
+            assert dg["captures"] + dg["replays"] == (1 if graphed else 0), (streams, dg)
+            if call == 2:
+                assert dg["replays"] == (1 if graphed else 0) and dg["captures"] == 0, dg
             if streams:
                 assert ("two streams" in path) == (streams == 2), path
         finally:

@@ -120,7 +120,10 @@ def test_graph_replay_does_not_cross_schemes(solver):
     m1, m2, N, n = 50, 25, 20, 4
     grids, U0 = _batch(m1, m2, Cm.strikes_for(n))
     a = _run(solver, H.SCHEME_MCS, TH_MCS, m1, m2, N, grids, U0)
+    g0 = Cm.graph_counts(solver)
     b = _run(solver, H.SCHEME_MCS, TH_MCS, m1, m2, N, grids, U0)
+    dg = Cm.graph_delta(g0, Cm.graph_counts(solver))
+    assert dg["replays"] == 1 and dg["captures"] == 0, dg  # the second call really replayed
     assert np.array_equal(a, b)
     seq = [(H.SCHEME_MCS, TH_MCS), (H.SCHEME_CRAIG_SNEYD, TH_MCS), (H.SCHEME_HV, TH_MCS)]
     got = [_run(solver, sc, th, m1, m2, N, grids, U0) for sc, th in seq]
@@ -221,9 +224,13 @@ def test_per_instance_parameters_and_maturities(solver, scheme, theta, name, pat
     grids, U0 = _batch(m1, m2, strikes)
     _tuned(solver, tuning)
     try:
-        for _ in range(2 if path == "graph" else 1):  # (graph: the second call replays the captured time loop)
+        for call in range(2 if path == "graph" else 1):  # (graph: the second call replays the captured time loop)
             U = U0.copy()
+            g0 = Cm.graph_counts(solver)
             solver.DO_timestepping(m1, m2, 1, 1.0, theta, Cm.R_D, R_F, 0.0, 0.1, 1.0, 0.04, grids, U, scheme=scheme, per_instance=per)
+            if call == 1:
+                dg = Cm.graph_delta(g0, Cm.graph_counts(solver))
+                assert dg["replays"] == 1 and dg["captures"] == 0, dg
         d = solver.describe_last_sweep()
     finally:
         _untune(solver, tuning)
