@@ -229,6 +229,17 @@ int hadi_get_timing(const hadi_ctx *ctx, hadi_timing *out);
  *                 (hadi_team_kernel): -1 automatic (default), 0 never, 1 whenever the shape allows it.  If the team
  *                 protocol fails (it is bounded everywhere) the batch is solved again on the two-launches-per-step path
  *                 and the automatic choice stays away from it for the rest of the handle's life (get: -2)
+ *   "resident_sweep" both passes of every Douglas step in ONE launch per sub-batch, one 512-thread block per instance running
+ *                 its whole time loop (hadi_sweep_resident<8>: the row phase is the body of hadi_pass_a_strip<8,EU>, the column
+ *                 phase the hadi_pb_* functions of hadi_pass_b<8,EU>, a workgroup barrier between them): -1 automatic
+ *                 (default), 0 never, 1 wherever eligible.  Eligible: European Douglas sweeps with the fp64 state,
+ *                 256 < m1 <= 512, m2 <= 263, theta > 0, r_d != r_f, a sub-batch whose strip row pass is one block per
+ *                 instance in one round of CUs with less than 4 % of them idle (512x256: 246 .. 256 instances per round;
+ *                 a remainder sub-batch stays streaming).  Under -1 a caller who pins the streaming geometry ("strip",
+ *                 "row_tile", "col_groups", "strip_blocks") gets the streaming kernels, and so does any "debug_fault" hook.
+ *                 Per-launch profiling
+ *                 (hadi_set_profiling) needs a kernel per pass: with it on, the sweep runs on the streaming kernels.  Same
+ *                 bits as the streaming path; 512x256 x256 x1000 steps 212.3 -> 201.2 ms
  *   "debug_fault" TEST HOOK, 0 in production: 1 = the high half of every two-wavefront row (m1 > 512) withholds its
  *                 rendezvous token on v-row 1, so that the partner's bounded poll runs out (~0.2 s) -- the call must then
  *                 return HADI_ERR_INTERNAL instead of a field solved with stale exchange values; 128 = one block of every

@@ -93,6 +93,9 @@ struct Ctx {
     // when a team could not form or a team barrier timed out once on this handle (the automatic choice then stays away)
     int team_launch = -1, team_failed = 0;
     DevBuf team;
+    // resident sweep (hadi_sweep_resident: both passes of every step in one launch, one block per instance): -1 automatic, 0 never,
+    // 1 wherever the sub-batch is eligible (run_sweep)
+    int resident_sweep = -1;
 };
 
 // Every GPU entry point runs on the handle's device whatever the caller's current device is (a torch rank that
@@ -325,6 +328,7 @@ hipError_t raise_all_lds_limits() {
     if ((e = raise_lds_limit(hadi_pass_a_pairs<2>)) != hipSuccess) return e;
     if ((e = raise_lds_limit(hadi_team_kernel<8>)) != hipSuccess) return e;
     if ((e = raise_lds_limit(hadi_team_kernel<4>)) != hipSuccess) return e;
+    if ((e = raise_lds_limit(hadi_sweep_resident<8>)) != hipSuccess) return e;
     if ((e = raise_lds_limit(hadi_small_seq2_kernel<1>)) != hipSuccess) return e;
     if ((e = raise_lds_limit(hadi_small_seq2_kernel<2>)) != hipSuccess) return e;
     if ((e = raise_lds_limit(hadi_small_seq_kernel<1>)) != hipSuccess) return e;
@@ -864,6 +868,19 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
         x.pb += (size_t)o * pl.n_pb; x.rinv += (size_t)o * pl.n_rinv; x.ipar += o;
         return x;
     };
+    // Resident sweep (hadi_sweep_resident): European Douglas steps with the fp64 state, 8 nodes per lane on one wavefront per
+    // v-row, at most 8 column chunks, and a sub-batch whose strip row pass is ONE block per instance in ONE round of CUs with
+    // less than HADI_TWO_STREAM_IDLE of them idle -- a block that waited for a second round would wait for a whole time loop.
+    // Other sub-batches of the same call (a small remainder) stay on the streaming kernels.  "resident_sweep" = -1 (default):
+    // wherever eligible unless the caller pinned the streaming geometry; 1: wherever eligible; 0: never.
+    const bool geo_pinned = c->tune.strip >= 0 || c->tune.row_tile > 0 || c->tune.col_groups > 0 || c->tune.strip_blocks > 0;
+    const bool resident_shape = (c->resident_sweep > 0 || (c->resident_sweep < 0 && !geo_pinned)) && d.scheme == HADI_SCHEME_DOUGLAS &&
+                                d.variant == HADI_EU && !f32 && L.B == 8 && L.G == 1 && L.P <= 8 && !seq_shape && d.theta > 0.0 &&
+                                d.r_d != d.r_f && !d.debug && !c->debug_fault && !prof;  // (test hooks: the streaming kernels they are for)
+    auto resident = [&](const SubBatch &sbt) {
+        return resident_shape && sbt.pl.use_strip && !sbt.pl.use_pairs && sbt.pl.sblocks == 1 && sbt.cnt <= c->cu_count &&
+               hadi_plan_row_idle(sbt.pl, sbt.cnt, c->cu_count) < HADI_TWO_STREAM_IDLE;
+    };
     const HadiSweepArgs a_all = a, av_all = av;
     bool forked = false;
     auto enqueue_body = [&](hipStream_t q0) -> int {
@@ -889,6 +906,10 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
             // (its own LDS size: the fp64 ring of 4 pairs x 3 slots, whatever the state precision of the sweep -- hadi_plan.h)
             const size_t sm = (size_t)4 * HADI_STRIP_NS(8, 2, 8) * L.rowp * sizeof(double) + ((size_t)4 * 64 * 8 * 2 + (size_t)4 * 16) * sizeof(double);
             hipLaunchKernelGGL((hadi_pass_a_strip<8, 0, double, 2, 3>), dim3(pl.grid_as), dim3(512), sm, q, at, 1);
+        }
+        if (resident(subs[sb])) {  // the sub-batch's whole time loop in one launch (LDS: the strip rings; the column phase aliases them)
+            hipLaunchKernelGGL((hadi_sweep_resident<8>), dim3(pl.grid_as), dim3(64 * HADI_STRIP_WAVES(8)), std::max(pl.smem_as, pl.smem_b), q, a, n_last);
+            continue;
         }
         for (int nstep = n_first; nstep <= n_last; nstep++) {
             // P representation: the first step (the caller's initial U need not dominate the payoff) and dividend steps
@@ -1026,6 +1047,15 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     }
 
     c->last_path = describe_streaming_path(c, pl, bp, american, amp, d.scheme, f32);
+    {
+        int nres = 0;
+        for (const auto &sbt : subs) nres += resident(sbt) ? 1 : 0;
+        if (nres == nsub)
+            c->last_path += "; both passes of every step in one launch: hadi_sweep_resident<8> (one block per instance, all column tiles)";
+        else if (nres)
+            c->last_path += "; both passes of every step in one launch for " + std::to_string(nres) +
+                            " sub-batches of one round: hadi_sweep_resident<8> (one block per instance, all column tiles), the others streaming";
+    }
     c->last_nsub = nsub;
     HIP_TRY(c, hipEventRecord(c->ev[1], s));
     // ---- instance-resident launch: up to 8 large European instances, one per XCD, whole time loop in one kernel ----------
@@ -1094,7 +1124,8 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
                                         // streams, a tuning change that flips only the second sub-batch's plan)
             const HadiPlan &q = sbt.pl;
             const int geo[] = {c->col_prefetch, c->cs_strips, c->tile_il, sbt.lane, fork_before, sbt.off, sbt.cnt, q.R, q.ntiles, q.grid_a, (int)q.smem_a, q.use_strip, q.use_pairs, q.RS, q.sblocks, q.grid_as,
-                               (int)q.smem_as, q.ctiles, q.btpw, q.bgroups, q.grid_b, q.block_b, (int)q.smem_b, q.row_seq, q.col_seq, q.W, q.NG, q.PD};
+                               (int)q.smem_as, q.ctiles, q.btpw, q.bgroups, q.grid_b, q.block_b, (int)q.smem_b, q.row_seq, q.col_seq, q.W, q.NG, q.PD,
+                               resident(sbt) ? 1 : 0};
             put(geo, sizeof(geo));
         }
         put(&d.Nmax, sizeof(int)); put(&d.dt0, sizeof(double));
@@ -1641,6 +1672,7 @@ int hadi_set_tuning(hadi_ctx *ctx, const char *key, int value) {
     else if (!std::strcmp(key, "strip")) c->tune.strip = value < 0 ? -1 : (value ? 1 : 0);
     else if (!std::strcmp(key, "debug_fault")) c->debug_fault = value;
     else if (!std::strcmp(key, "team_launch")) { c->team_launch = value < 0 ? -1 : (value ? 1 : 0); c->team_failed = 0; }
+    else if (!std::strcmp(key, "resident_sweep")) c->resident_sweep = value < 0 ? -1 : (value ? 1 : 0);
     else if (!std::strcmp(key, "row_tile")) c->tune.row_tile = value > 0 ? value : 0;
     else if (!std::strcmp(key, "strip_blocks")) c->tune.strip_blocks = value > 0 ? value : 0;
     else if (!std::strcmp(key, "pair_strips")) c->tune.pair_strips = value < 0 ? -1 : (value ? 1 : 0);
@@ -1682,6 +1714,7 @@ int hadi_get_tuning(const hadi_ctx *ctx, const char *key, int *value) {
     else if (!std::strcmp(key, "strip")) *value = c->tune.strip;
     else if (!std::strcmp(key, "debug_fault")) *value = c->debug_fault;
     else if (!std::strcmp(key, "team_launch")) *value = c->team_failed ? -2 : c->team_launch;
+    else if (!std::strcmp(key, "resident_sweep")) *value = c->resident_sweep;
     else if (!std::strcmp(key, "row_tile")) *value = c->tune.row_tile;
     else if (!std::strcmp(key, "strip_blocks")) *value = c->tune.strip_blocks;
     else if (!std::strcmp(key, "pair_strips")) *value = c->tune.pair_strips;

@@ -31,6 +31,7 @@
 #include "hadi_k_row_strip.h"
 #include "hadi_k_col.h"
 #include "hadi_k_team.h"
+#include "hadi_k_resident.h"
 #include "hadi_k_small.h"
 #include "hadi_k_seq.h"
 #include "hadi_k_aux.h"
