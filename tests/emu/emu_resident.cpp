@@ -3,15 +3,16 @@
 // up a batch as emu_solve does and runs its whole time loop in ONE launch of the resident kernel.  Never shipped.
 #include "emu_driver.cpp"
 
-// European Douglas sweep, calls.  Arrays natural layout [n][...]; N_i / dt_i: per-instance step grids (NULL: N and dt for every
-// instance; the launch runs to the largest N_i and every block stops at its own).  The strip geometry is forced to ONE block
+// European Douglas sweep.  Arrays natural layout [n][...]; N_i / dt_i: per-instance step grids (NULL: N and dt for every
+// instance; the launch runs to the largest N_i and every block stops at its own).  strike / put: per-instance strikes and the
+// option type (put != 0: put boundary data K e^{-r_d t}; they fill par8[6] and par8[7] as fill_par of hadi_api.hip does).  The strip geometry is forced to ONE block
 // per instance (tuning "strip" = 1, "strip_blocks" = 1 on top of the emulator's tuning), whatever the batch size: the
 // library's selection rules are tested on the GPU.  Returns 0, 1 (no plan), 3 (the shape is not eligible) or 4 (device error
 // word set).
 extern "C" int emu_solve_resident(int n_inst, int m1, int m2, int N, double dt, double theta, double r_d, double r_f,
                                   const double *par /*[n][4] rho sigma kappa eta*/, const double *vec_s, const double *vec_v,
                                   const double *delta_s, const double *delta_v, double *U, int setup_threads, const int *N_i,
-                                  const double *dt_i, int *P_out) {
+                                  const double *dt_i, int *P_out, const double *strike /*[n], NULL with put = 0*/, int put) {
     HadiTuning tu = g_tune;
     tu.strip = 1;
     tu.strip_blocks = 1;
@@ -23,6 +24,7 @@ extern "C" int emu_solve_resident(int n_inst, int m1, int m2, int N, double dt, 
         pl.row_seq || pl.col_seq)
         return 3;
     if ((N_i || dt_i) && (!N_i || !dt_i)) return 3;
+    if (put && !strike) return 3;
     int Nmax = N;
     if (N_i) {
         Nmax = 0;
@@ -38,6 +40,8 @@ extern "C" int emu_solve_resident(int n_inst, int m1, int m2, int N, double dt, 
         for (int z = 0; z < 4; z++) par8[(size_t)k * 8 + z] = par[(size_t)k * 4 + z];
         par8[(size_t)k * 8 + 4] = dt_i ? dt_i[k] : dt;
         par8[(size_t)k * 8 + 5] = (double)(N_i ? N_i[k] : N);
+        par8[(size_t)k * 8 + 6] = put ? strike[k] : 0.0;
+        par8[(size_t)k * 8 + 7] = put ? 1.0 : 0.0;
     }
     HadiSetupArgs s;
     s.L = L; s.n_inst = n_inst;

@@ -776,8 +776,10 @@ def test_craig_sneyd_on_strips_vs_oracle_ring_and_full_drains(solver, strict_sol
     assert np.array_equal(U, Us)
 
 
-LOAD_CASES = [  # (m1, m2, N, n, variant, tuning, fp32, kernel expected in the description)
-    (512, 256, 20, 256, H.EU, {}, False, "hadi_pass_a_strip<8,EU>"),                    # config 2 as benchmarked
+LOAD_CASES = [  # (m1, m2, N, n, variant, tuning, fp32, kernel expected in the description[, kernel that must NOT be in it])
+    # config 2 on the streaming strip kernel at the headline geometry (it serves every remainder sub-batch, profiled run and pinned
+    # geometry; the default path of this batch is the resident sweep: the last case)
+    (512, 256, 20, 256, H.EU, {"resident_sweep": 0}, False, "hadi_pass_a_strip<8,EU>", "hadi_sweep_resident"),
     (512, 256, 12, 256, H.AM, {}, False, "hadi_pass_a_strip<8,AM-P>"),                  # P representation on strips
     (512, 256, 12, 256, H.AM, {"american_p": 0}, False, "hadi_pass_a_strip<8,AM>"),     # explicit (U, lambda_bar) pair
     (512, 256, 12, 160, H.EU, {}, False, "two streams"),                               # two half-batches side by side
@@ -788,10 +790,18 @@ LOAD_CASES = [  # (m1, m2, N, n, variant, tuning, fp32, kernel expected in the d
     (1024, 512, 8, 64, H.EU, {}, False, "hadi_pass_a_strip<8,EU,double,2>"),            # config 5, fp64 state
     (1024, 512, 8, 64, H.EU, {}, True, "hadi_pass_a_strip<8,EU,float,2>"),              # config 5, fp32 state
     (1024, 512, 6, 64, H.AM, {}, False, "hadi_pass_a_strip<8,AM-P,double,2>"),
+    (512, 256, 20, 256, H.EU, {}, False, "hadi_sweep_resident<8>"),                     # config 2 as benchmarked: the resident sweep
 ]
 
 
-@pytest.mark.parametrize("m1,m2,N,n,variant,tuning,fp32,kernel", LOAD_CASES)
+def _load_key(m1, m2, N, n, variant, tuning, fp32, kernel):
+    return (m1, m2, N, n, variant, tuple(sorted(tuning.items())), fp32, kernel)
+
+
+LOAD_ABSENT = {_load_key(*c[:8]): c[8] for c in LOAD_CASES if len(c) > 8}  # (the optional ninth field)
+
+
+@pytest.mark.parametrize("m1,m2,N,n,variant,tuning,fp32,kernel", [c[:8] for c in LOAD_CASES])
 def test_counted_waits_under_load_equal_full_drains(solver, strict_solver, m1, m2, N, n, variant, tuning, fp32, kernel):
     """test_counted_vmcnt_waits_equal_full_drains (below) compares the two builds on two or three instances -- where every
     load has landed long before it is waited for.  The defect of round 4's first strip corrector only showed with every CU
@@ -800,7 +810,8 @@ def test_counted_waits_under_load_equal_full_drains(solver, strict_solver, m1, m
     strikes = Cm.strikes_for(n)
     grids, U0 = _batch(m1, m2, strikes)
     res = []
-    reset = {"strip": -1, "american_p": 1, "pair_strips": -1}
+    absent = LOAD_ABSENT.get(_load_key(m1, m2, N, n, variant, tuning, fp32, kernel))
+    reset = {"strip": -1, "american_p": 1, "pair_strips": -1, "resident_sweep": -1}
     for sv in (solver, strict_solver):
         for k, v in tuning.items():
             sv.set_tuning(k, v)
@@ -816,6 +827,7 @@ def test_counted_waits_under_load_equal_full_drains(solver, strict_solver, m1, m
                 sv.set_tuning(k, reset[k])
         res.append((U, lam, sv.describe_last_sweep()))
     assert kernel in res[0][2], res[0][2]
+    assert absent is None or absent not in res[0][2], res[0][2]
     assert res[0][2] == res[1][2]
     assert np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])
     assert np.isfinite(res[0][0]).all()
