@@ -22,6 +22,8 @@
  *                                      (src/jacobian_computation.cpp:204, 457, 726, 1031)
  *   hadi_compute_parameter_update   <- compute_parameter_update_on_device + solve_5x5_device
  *                                      (src/jacobian_computation.cpp:20-195)
+ *   hadi_compute_greeks             <- no counterpart: delta, gamma, variance sensitivities, theta and the spot ladder of the
+ *                                      v-row of V_0, from the state the sweep leaves on the device
  *   hadi_make_grid / hadi_rebuild_variance <- Grid::Grid (src/grid.cpp:16-61),
  *                                      GridViews::rebuild_variance_views (src/grid_pod.hpp:25-73)
  *
@@ -57,7 +59,7 @@ enum hadi_status {
     HADI_ERR_INVALID = 1,      /* bad argument (NULL, sizes, variant) */
     HADI_ERR_UNSUPPORTED = 2,  /* grid shape outside what the kernels cover */
     HADI_ERR_HIP = 3,          /* a HIP runtime call failed */
-    HADI_ERR_NOT_ON_GRID = 4,  /* S_0 is not a node of some instance's s-grid */
+    HADI_ERR_NOT_ON_GRID = 4,  /* S_0 is not a node of some instance's s-grid (hadi_compute_greeks: or V_0 of its v-grid) */
     HADI_ERR_NO_DEVICE = 5,    /* no usable GPU: the product has no CPU path */
     HADI_ERR_ALLOC = 6,
     HADI_ERR_INTERNAL = 7      /* a kernel reported a failure through the handle's device error word (e.g. the bounded
@@ -95,6 +97,19 @@ enum hadi_state_precision { HADI_STATE_FP64 = 0, HADI_STATE_FP32 = 1 };
  *   v = 0 and the two top v-rows: the PDE rows / empty rows of A2 exactly as for the call.
  * Needs hadi_problem.strike_i.  Validated by put-call parity against the call path and the semi-analytic Heston price. */
 enum hadi_option_type { HADI_CALL = 0, HADI_PUT = 1 };
+
+/* Columns of hadi_compute_greeks' outputs (one row of 8 per node). */
+enum hadi_greek {
+    HADI_GREEK_PRICE = 0,   /* U(i, j0) */
+    HADI_GREEK_DELTA = 1,   /* dU/ds */
+    HADI_GREEK_GAMMA = 2,   /* d2U/ds2 */
+    HADI_GREEK_DV = 3,      /* dU/dv, the sensitivity to the spot variance (Black-Scholes-style vega = dv * 2 sqrt(v): the caller's) */
+    HADI_GREEK_DVV = 4,     /* d2U/dv2 */
+    HADI_GREEK_DSV = 5,     /* d2U/ds dv */
+    HADI_GREEK_THETA = 6,   /* calendar-time derivative per year */
+    HADI_GREEK_LAMBDA = 7,  /* lambda_bar of the American variants (> 0: exercise region), 0 otherwise */
+    HADI_N_GREEKS = 8
+};
 
 /* One batch of independent option instances = one league of teams in the reference
  * (TeamPolicy(nInstances, AUTO), device_solver.hpp:83-88). */
@@ -277,6 +292,37 @@ int hadi_DO_timestepping(hadi_ctx *ctx, const hadi_problem *p);
 
 int hadi_parallel_DO_solve(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0,
                            double *base_prices /* [n] */);
+
+/* Greeks at (S_0, V_0) and, optionally, the spot ladder of the v-row of V_0 -- NOT a reference feature (the reference returns
+ * prices and forward-difference parameter sensitivities only).  The sweep of hadi_DO_timestepping (p is read exactly as that
+ * entry point reads it: the caller's four grid arrays, variant, dividends, scheme, option type and strikes, per-instance
+ * parameters and (N_i, dt_i), U_0, the initial condition p->U) followed by ONE small kernel on the state and the operator
+ * tables the sweep left in HBM (hadi_greeks_kernel).  p->U and p->lambda_bar are NOT written and no field leaves the device:
+ * the results are n*8 doubles (and n*(m1+1)*8 with the ladder).
+ *   greeks [n][8]        the row of the node i0 = first s-node with |s_i - S_0| < 1e-10, on the v-row j0 = first v-node with
+ *                        |v_j - V_0| < 1e-10; columns: enum hadi_greek
+ *   ladder [n][m1+1][8]  the same 8 columns for every s-node of row j0, or NULL (ladder[k][i0] == greeks[k] bit for bit)
+ * Both follow p->memspace.  Stencils: three-point first and second derivatives on the non-uniform axes -- interior nodes the
+ * reference's beta / delta weights (coeff.hpp), end nodes its one-sided gamma (first node) / alpha (last node) weights; the
+ * second derivative of an end node is its interior neighbour's (one parabola through the three nodes).  All are exact on
+ * quadratics.  dsv is D1_v applied to the rows D1_s U(., j): inside the grid the 9-point product stencil of A0.
+ * theta = -(A0 U + A1 U + A2 U + b e_N + lambda_bar_N)(i, j0): minus the explicit right-hand side F(t_N, U_N) of the scheme,
+ * evaluated from the sweep's own operator tables and boundary vector, e_N = exp(bc_rate dt N), bc_rate = r_f (call data) or
+ * -r_d (put data), with the instance's own parameters and (N, dt).  Two things to know about it:
+ *   - it includes the reference's boundary-vector quirks: the call's b1 entry of v-row j sits at column m1 - j
+ *     (hes_boundary_kernels.hpp:54-58), an INTERIOR node of the ladder -- on 256x128 with V_0 = 0.04 that is i = 217;
+ *   - for American options it is the semi-discrete residual: accurate away from the free boundary, about 0 deep inside the
+ *     exercise region, and O(1) off on the few nodes next to the boundary (on the oracle's field of a 100x50 American put its
+ *     largest value over the exercised ladder nodes is 0.03 .. 0.4 for N = 100 .. 200 and up to 12 for N = 20, its median
+ *     below 1e-6).  No backward difference of the last two time levels is formed.
+ * Errors: everything hadi_DO_timestepping refuses, with the same status (p->V_0_i: HADI_ERR_INVALID); greeks == NULL:
+ * HADI_ERR_INVALID; HADI_STATE_FP32: HADI_ERR_UNSUPPORTED (a gamma stencil on 512x256 has weight sums near 1e2: on a state
+ * rounded to 24 bits it returns noise); S_0 off some instance's s-grid: HADI_ERR_NOT_ON_GRID, as the price pick.  V_0 off some
+ * instance's v-grid is HADI_ERR_NOT_ON_GRID as well -- UNLIKE the price pick of hadi_parallel_DO_solve / hadi_compute_base_prices,
+ * which mirrors the reference and silently reads v-row 0: a Greek taken on the wrong row is not returned silently.
+ * Whenever the call returns an error, the contents of greeks and ladder are unspecified. */
+int hadi_compute_greeks(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0,
+                        double *greeks /* [n][8] */, double *ladder /* [n][m1+1][8] or NULL */);
 
 /* v-grid rebuilt from (V_0, V = 5.0, d = 5.0/500) exactly as every call site of the reference
  * does (jacobian_computation.cpp:253); p->vec_v / p->delta_v are ignored. */

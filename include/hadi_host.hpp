@@ -164,6 +164,22 @@ inline void compute_base_prices_american_dividends(Handle &h, double S_0, double
     detail::check(h, hadi_compute_base_prices_american_dividends(h.ctx, &p, S_0, V_0, base_prices.data()));
 }
 
+// Greeks at (S_0, V_0) and, with `ladder`, the spot ladder of the v-row of V_0 (hadi_compute_greeks; NOT in the reference).
+// greeks: [num_strikes][HADI_N_GREEKS], ladder: [num_strikes][m1+1][HADI_N_GREEKS], columns enum hadi_greek.  workspace.U holds
+// the initial condition and is not modified; U_0 (American variants) defaults to it.
+inline void compute_greeks(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho, double sigma,
+                           double kappa, double eta, int m1, int m2, int /*total_size*/, int N, double theta, double delta_t,
+                           int num_strikes, const GridViews &deviceGrids, const DO_Workspace &workspace,
+                           std::vector<double> &greeks, std::vector<double> *ladder = nullptr, int variant = HADI_EU,
+                           const std::vector<double> *U_0 = nullptr, const Dividends *div = nullptr,
+                           const PutStrikes *put = nullptr) {
+    greeks.resize((size_t)num_strikes * HADI_N_GREEKS);
+    if (ladder) ladder->resize((size_t)num_strikes * (m1 + 1) * HADI_N_GREEKS);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  const_cast<double *>(workspace.U.data()), U_0 ? U_0->data() : nullptr, div, put);
+    detail::check(h, hadi_compute_greeks(h.ctx, &p, S_0, V_0, greeks.data(), ladder ? ladder->data() : nullptr));
+}
+
 // jacobian_computation.cpp:204-364 and the three variants.  J: [num_strikes][5], columns kappa, eta, sigma, rho, v0.
 inline void compute_jacobian(Handle &h, double S_0, double V_0, double, double r_d, double r_f, double rho, double sigma,
                              double kappa, double eta, int m1, int m2, int, int N, double theta, double delta_t,

@@ -6,6 +6,8 @@ The compute runs in hand-written HIP kernels for gfx950 behind the C ABI in incl
 this package only marshals arguments.  There is no CPU fallback.
 """
 from ._native import EU, AM, DIV, AM_DIV, CALL, PUT, HadiError, LIB_PATH, STATE_FP64, STATE_FP32  # noqa: F401
+from ._native import (G_PRICE, G_DELTA, G_GAMMA, G_DV, G_DVV, G_DSV, G_THETA, G_LAMBDA, N_GREEKS,  # noqa: F401
+                      GREEK_NAMES)
 from ._native import SCHEME_DOUGLAS, SCHEME_CRAIG_SNEYD, SCHEME_MCS, SCHEME_HV  # noqa: F401
 from .grid import Grid, GridViewsBatch  # noqa: F401
 from .solver import (HestonADI, DOWorkspace, Dividends, compute_parameter_update,  # noqa: F401
@@ -23,4 +25,5 @@ __all__ = ["EU", "AM", "DIV", "AM_DIV", "CALL", "PUT", "lm_partials_device", "ST
            "shard_range", "calibrate_european", "clamp_parameters", "market", "CalibrationPoint", "calibrate",
            "calibrate_american", "calibrate_dividends", "calibrate_american_dividends",
            "calibrate_european_multi_maturity", "calibrate_american_dividends_multi_maturity",
-           "make_calibration_points", "export_calibration_csv"]
+           "make_calibration_points", "export_calibration_csv", "G_PRICE", "G_DELTA", "G_GAMMA", "G_DV", "G_DVV", "G_DSV",
+           "G_THETA", "G_LAMBDA", "N_GREEKS", "GREEK_NAMES"]

@@ -15,6 +15,10 @@ MEM_HOST, MEM_DEVICE = 0, 1
 SCHEME_DOUGLAS, SCHEME_CRAIG_SNEYD, SCHEME_MCS, SCHEME_HV = 0, 1, 2, 3
 STATE_FP64, STATE_FP32 = 0, 1
 CALL, PUT = 0, 1
+# columns of hadi_compute_greeks' outputs (enum hadi_greek)
+G_PRICE, G_DELTA, G_GAMMA, G_DV, G_DVV, G_DSV, G_THETA, G_LAMBDA = range(8)
+N_GREEKS = 8
+GREEK_NAMES = ("price", "delta", "gamma", "dv", "dvv", "dsv", "theta", "lambda")
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -63,7 +67,7 @@ EXPORTS = [
     "hadi_set_profiling", "hadi_get_timing", "hadi_set_tuning", "hadi_get_tuning", "hadi_device_info", "hadi_describe_last_sweep",
     "hadi_stream", "hadi_wait_stream",
     "hadi_make_grid", "hadi_rebuild_variance", "hadi_find_s_index", "hadi_find_v_index",
-    "hadi_DO_timestepping", "hadi_parallel_DO_solve",
+    "hadi_DO_timestepping", "hadi_parallel_DO_solve", "hadi_compute_greeks",
     "hadi_compute_base_prices", "hadi_compute_base_prices_american",
     "hadi_compute_base_prices_dividends", "hadi_compute_base_prices_american_dividends",
     "hadi_compute_jacobian", "hadi_compute_jacobian_american",
@@ -128,6 +132,7 @@ def _load(LIB_PATH):
     L.hadi_find_v_index.argtypes = [C.c_int, _dp, C.c_double]
     L.hadi_DO_timestepping.argtypes = [C.c_void_p, C.POINTER(Problem)]
     L.hadi_parallel_DO_solve.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_void_p]
+    L.hadi_compute_greeks.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_void_p, C.c_void_p]
     for sfx in ("", "_american", "_dividends", "_american_dividends"):
         getattr(L, "hadi_compute_base_prices" + sfx).argtypes = [
             C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_void_p]

@@ -1417,6 +1417,65 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
     return HADI_OK;
 }
 
+// hadi_compute_greeks: the sweep of hadi_DO_timestepping on the caller's grids, then hadi_greeks_kernel on the packed state the
+// sweep left in the handle (every execution path of run_sweep ends with an explicit U, American sweeps with an explicit
+// lambda_bar as well) and on its operator tables.  No field is unpacked or copied; p->U and p->lambda_bar are not written.
+static_assert(HADI_GK_N == HADI_N_GREEKS && HADI_GK_LAMBDA == HADI_GREEK_LAMBDA && HADI_GK_THETA == HADI_GREEK_THETA, "hadi.h / hadi_k_greeks.h columns");
+int greeks_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double *greeks, double *ladder) {
+    int rc = check_problem(c, p, true, true);
+    if (rc) return rc;
+    if (!greeks) return fail(c, HADI_ERR_INVALID, "greeks missing");
+    if (p->state_precision == HADI_STATE_FP32)
+        return fail(c, HADI_ERR_UNSUPPORTED, "Greeks need the fp64 state: second-derivative stencils have weight sums near 1e2 on 512x256, "
+                                             "which turn a state rounded to 24 bits into noise");
+    DeviceGuard guard(c->device);
+    pin_rewind(c);
+    const int n = p->n_instances, m1 = p->m1, m2 = p->m2;
+    const size_t m = (size_t)(m1 + 1) * (m2 + 1);
+    SweepDesc d;
+    fill_common(p, d);
+    d.n = n; d.n_src = n;
+    fill_par(p, d, 1);
+    if ((rc = to_device(c, p->memspace, p->vec_s, (size_t)n * (m1 + 1), c->g_s, &d.d_vec_s))) return rc;
+    if ((rc = to_device(c, p->memspace, p->delta_s, (size_t)n * m1, c->g_ds, &d.d_delta_s))) return rc;
+    if ((rc = to_device(c, p->memspace, p->vec_v, (size_t)n * (m2 + 1), c->g_v, &d.d_vec_v))) return rc;
+    if ((rc = to_device(c, p->memspace, p->delta_v, (size_t)n * m2, c->g_dv, &d.d_delta_v))) return rc;
+    if ((rc = to_device(c, p->memspace, p->U, n * m, c->natU, &d.d_natU))) return rc;
+    if ((rc = to_device(c, p->memspace, p->U_0, n * m, c->natU0, &d.d_natU0))) return rc;
+    // the buffers the outputs pass through, grown before the sweep: growing one after it would drop the loop it just captured
+    const size_t nlad = (size_t)n * (m1 + 1) * HADI_GK_N;
+    if ((rc = ensure(c, c->prices, (size_t)n * HADI_GK_N * 8)) || (rc = ensure(c, c->status, n * sizeof(int)))) return rc;
+    if (ladder && (rc = ensure(c, c->natOut, nlad * 8))) return rc;
+
+    HadiPlan pl;
+    if ((rc = run_sweep(c, d, pl))) return rc;
+
+    const HadiLayout &L = pl.L;
+    const bool american = p->variant == HADI_AM || p->variant == HADI_AM_DIV;
+    HadiGreeksArgs g;
+    g.L = L; g.n_inst = n; g.american = american ? 1 : 0;
+    g.ntiles = L.B == 1 ? (m1 + HADI_GK_TILE) / HADI_GK_TILE : 1;
+    g.span = L.B == 1 ? HADI_GK_TILE + 2 * HADI_GK_HALO : L.rowp;
+    g.U = ptr<double>(c->U); g.LAM = american ? ptr<double>(c->LAM) : nullptr;
+    g.scoef = ptr<double>(c->scoef); g.b2row = ptr<double>(c->b2row); g.rowc = ptr<double>(c->rowc);
+    g.ipar = ptr<HadiInstPar>(c->ipar);
+    g.vec_s = d.d_vec_s; g.vec_v = d.d_vec_v; g.delta_s = d.d_delta_s; g.delta_v = d.d_delta_v;
+    g.S_0 = S_0; g.V_0 = V_0;
+    g.greeks = ptr<double>(c->prices); g.ladder = ladder ? ptr<double>(c->natOut) : nullptr; g.status = ptr<int>(c->status);
+    hipLaunchKernelGGL(hadi_greeks_kernel, dim3((unsigned)(n * g.ntiles)), dim3(HADI_GK_THREADS), hadi_greeks_smem(g.span), c->stream, g);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = from_device(c, p->memspace, greeks, ptr<double>(c->prices), (size_t)n * HADI_GK_N))) return rc;
+    if (ladder && (rc = from_device(c, p->memspace, ladder, ptr<double>(c->natOut), nlad))) return rc;
+    std::vector<int> hstatus(n);
+    HIP_TRY(c, hipMemcpyAsync(hstatus.data(), c->status.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = finish_timing(c, d, pl))) return rc;
+    for (int k = 0; k < n; k++) {
+        if (hstatus[k] == 1) return fail(c, HADI_ERR_NOT_ON_GRID, "S_0 = %.17g is not a node of instance %d's s-grid", S_0, k);
+        if (hstatus[k]) return fail(c, HADI_ERR_NOT_ON_GRID, "V_0 = %.17g is not a node of instance %d's v-grid", V_0, k);
+    }
+    return HADI_OK;
+}
+
 // compute_jacobian*: the reference runs 6 solves one after the other inside each team
 // (jacobian_computation.cpp:232-363); here they are 6n independent instances of ONE batched sweep:
 // group 0 = base, 1..4 = kappa, eta, sigma, rho + eps, 5 = v-grid rebuilt for V_0 + eps.
@@ -1811,6 +1870,10 @@ int hadi_parallel_DO_solve(hadi_ctx *ctx, const hadi_problem *p, double S_0, dou
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && !base_prices) return fail(c, HADI_ERR_INVALID, "base_prices missing");
     return solve_common(c, p, false, true, S_0, V_0, base_prices);
+}
+
+int hadi_compute_greeks(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double *greeks, double *ladder) {
+    return greeks_common(reinterpret_cast<Ctx *>(ctx), p, S_0, V_0, greeks, ladder);
 }
 
 int hadi_compute_base_prices(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double *base_prices) {

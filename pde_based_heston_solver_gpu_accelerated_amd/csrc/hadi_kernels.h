@@ -35,3 +35,4 @@
 #include "hadi_k_small.h"
 #include "hadi_k_seq.h"
 #include "hadi_k_aux.h"
+#include "hadi_k_greeks.h"

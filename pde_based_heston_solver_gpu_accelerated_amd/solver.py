@@ -316,6 +316,29 @@ class HestonADI:
             return base_prices
         return out
 
+    # ---- Greeks and the spot ladder (hadi_compute_greeks; no reference counterpart) -----------------
+    def compute_greeks(self, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U, S_0, V_0,
+                       variant=EU, U_0=None, dividends=None, per_instance=None, scheme=0, option_type=CALL, strikes=None,
+                       ladder=False):
+        """The sweep of DO_timestepping from the initial condition U (not modified), then price, delta, gamma, dv, dvv, dsv,
+        theta and lambda_bar at (S_0, V_0) from the state on the device: [n][8], columns G_PRICE .. G_LAMBDA (hadi.h, enum
+        hadi_greek).  ladder=True returns the pair ([n][8], [n][m1+1][8]): the same columns for every s-node of the v-row of
+        V_0.  numpy arrays for host inputs, torch tensors for device inputs.  S_0 or V_0 off an instance's grid raises
+        HadiError (status 4)."""
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U=U, U_0=U_0,
+                          dividends=dividends, per_instance=per_instance, scheme=scheme, option_type=option_type,
+                          strikes=strikes)
+        n = grids.Vec_s.shape[0]
+        out, optr = self._out(n, nat.N_GREEKS, U)
+        lad, lptr = None, None
+        if ladder:
+            lad, lptr = self._out(n * (m1 + 1), nat.N_GREEKS, U)
+            lad = lad.reshape(n, m1 + 1, nat.N_GREEKS)
+        rc = self._lib.hadi_compute_greeks(self._h, C.byref(p), float(S_0), float(V_0), optr, lptr)
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return (out, lad) if ladder else out
+
     # ---- compute_base_prices* (src/jacobian_computation.cpp:368, 629, 922, 1232) ---------------
     def _base_prices(self, variant, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N,
                      theta, delta_t, num_strikes, deviceGrids, workspace, U_0=None, dividends=None,
