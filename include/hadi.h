@@ -139,7 +139,20 @@ typedef struct hadi_problem {
     const double *delta_s; /* [n][m1]   */
     const double *delta_v; /* [n][m2]   */
 
-    /* discrete dividends, shared (device_solver.hpp:409-413); host arrays */
+    /* discrete dividends, shared (device_solver.hpp:409-413); host arrays.
+     * Dating is the reference's rule (device_solver.hpp:424-517), mirrored as it stands: the dates are consumed in ARRAY
+     * order by one running index.  At the start of step n = 1..N the dividend under the index is paid if
+     * n*delta_t <= date < (n+1)*delta_t, both products evaluated in fp64 (12 * 0.05 = 0.6000000000000001 > 0.6 decides the
+     * step); after the step the index advances by one if n*delta_t > date -- at most once per step.  Hence: a date earlier
+     * than delta_t is never paid; of two dates inside one step interval the second is skipped; a cluster of dates makes the
+     * index lag behind later ones, which are then skipped too; unsorted dates are not sorted; and two paying steps are
+     * never adjacent (the index leaves a paid date one step later and sees the next date one step after that), so a
+     * schedule with a date in every step interval pays the first one only.  A date in [N*delta_t, (N+1)*delta_t) is paid at
+     * the start of the last step, later ones never.
+     * The jump U(s) <- U(s (1 - percentage) - amount) interpolates linearly between the two nodes around the ex-dividend
+     * spot; at or below 0 a call takes 0 and a put its value at node 0; and when NO node lies above the ex-dividend spot, or
+     * node 0 already does, it takes node 0's value -- so a zero dividend is not the identity at s_max, and neither is a
+     * negative one (the reference's idx == 0 branch). */
     int num_dividends;
     const double *dividend_dates, *dividend_amounts, *dividend_percentages;
 

@@ -298,6 +298,12 @@ extern "C" long long emu_plan_row_idle_ppm(int m1, int m2, int n_inst, int cus) 
     return (long long)(hadi_plan_row_idle(pl, n_inst, cus) * 1e6 + 0.5);
 }
 
+// The host routine that dates the dividends (hadi_plan.h), as the library calls it: flags[n-1] = index paid at the start of step n
+// or -1, `len` >= N entries.
+extern "C" void emu_dividend_steps(int N, double dt, int ndiv, const double *dates, int *flags, int len) {
+    hadi_dividend_steps(N, dt, ndiv, dates, flags, len);
+}
+
 // variant bit0 = american, bit1 = dividends.  Arrays natural layout [n][...].
 // scheme: 0 Douglas, 1 Craig-Sneyd, 2 Douglas with the fp32 state, 3 Douglas with the American P representation, 4 Modified
 // Craig-Sneyd, 5 Hundsdorfer-Verwer.  N_i / dt_i: per-instance time steps and step sizes (NULL: N and dt for every instance);

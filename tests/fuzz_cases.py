@@ -33,16 +33,24 @@ def draw_case(rng, small=False, wide=False):
                 f32=f32, tuning=tuning)
 
 
-def cases(seed, count, small=False, wide=False):
+def cases(seed, count, small=False, wide=False, schedules=False, T=1.0):
+    """schedules: DIV / AM_DIV cases get a dividend schedule of their own in c["divs"] (tests/dividend_schedules.py,
+    random_schedule for the case's N steps of T / N), drawn from a stream seeded by (seed, index) -- NOT from the generator's
+    stream, so the same (seed, index) is the same problem with and without it.  c["divs"] is None otherwise: the fixture's."""
+    if schedules:
+        import dividend_schedules
     rng = random.Random(seed)
     for index in range(count):
         c = draw_case(rng, small, wide)
         c["seed"], c["index"] = seed, index
+        c["divs"] = None
+        if schedules and c["variant"] in (DIV, AM_DIV):
+            c["divs"] = dividend_schedules.random_schedule(random.Random("dividends %d %d" % (seed, index)), c["N"], T / c["N"])
         yield c
 
 
-def case(seed, index, small=False, wide=False):
-    for c in cases(seed, index + 1, small, wide):
+def case(seed, index, small=False, wide=False, schedules=False, T=1.0):
+    for c in cases(seed, index + 1, small, wide, schedules, T):
         pass
     return c
 

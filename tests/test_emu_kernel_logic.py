@@ -35,21 +35,24 @@ def emu():
     return C.CDLL(EMU_SO)
 
 
-def _run(emu, m1, m2, N, strikes, variant, target_waves, r_f=0.0, small=0, scheme=0, put=False, tol=1e-11):
+def _run(emu, m1, m2, N, strikes, variant, target_waves, r_f=0.0, small=0, scheme=0, put=False, tol=1e-11, divs=Cm.DIVS):
     """scheme: 0 Douglas, 1 Craig-Sneyd, 2 Douglas with the state kept in fp32 between the passes, 3 Douglas with the
-    American P representation (no lambda_bar array; explicit pair on step 1 and on dividend steps)."""
+    American P representation (no lambda_bar array; explicit pair on step 1 and on dividend steps).  divs: the dividend
+    schedule (dates, amounts, percentages) of the DIV / AM_DIV variants, for the emulator and for the oracle."""
     n = len(strikes)
     vs, vv, ds, dv, U0 = Cm.oracle_grids(m1, m2, strikes)
     ks = np.array(strikes, dtype=np.float64)
     if put:
         U0 = np.ascontiguousarray(np.tile(np.maximum(ks[:, None] - vs, 0.0), (1, m2 + 1)))
-    p = Cm.oracle_params(m1, m2, N, variant, r_f=r_f, option_type=O.PUT if put else O.CALL, strikes=ks if put else None)
+    p = O.make_params(m1, m2, N, Cm.T / N, Cm.THETA, Cm.R_D, r_f, Cm.RHO, Cm.SIGMA, Cm.KAPPA, Cm.ETA, variant,
+                      divs if variant in (O.DIV, O.AM_DIV) else None, option_type=O.PUT if put else O.CALL, strikes=ks if put else None)
     p.scheme = 1 if scheme == 1 else 0
     p.state_fp32 = 1 if scheme == 2 else 0
     Uo, lamo, _ = O.solve_batch(p, vs, vv, ds, dv, U0, U0, want_lambda=True)
+    assert np.isfinite(Uo).all()
     U, lam = U0.copy(), np.zeros_like(U0)
     par = np.tile(np.array([Cm.RHO, Cm.SIGMA, Cm.KAPPA, Cm.ETA]), (n, 1)).copy()
-    dd = [np.array(x, dtype=np.float64) for x in Cm.DIVS]
+    dd = [np.array(x, dtype=np.float64) for x in divs]
     rc = emu.emu_solve(n, m1, m2, N, C.c_double(Cm.T / N), C.c_double(Cm.THETA), C.c_double(Cm.R_D),
                        C.c_double(r_f), _P(par), variant, _P(vs), _P(vv), _P(ds), _P(dv), _P(U), _P(U0), _P(lam),
                        target_waves, len(dd[0]), _P(dd[0]), _P(dd[1]), _P(dd[2]), 64, small, scheme, _P(ks) if put else None,
