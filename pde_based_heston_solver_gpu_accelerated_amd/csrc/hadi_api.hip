@@ -14,8 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "hadi_kernels.h"
-#include "hadi_plan.h"
+#include "hadi_dispatch.h"
 
 namespace {
 
@@ -244,128 +243,11 @@ struct SweepDesc {
     int debug = 0, debug_step = 1;
 };
 
-template <int B, int G, int NG, int PD>
-void launch_pass_a(const HadiPlan &pl, const HadiSweepArgs &a, int n, hipStream_t s, int mode = 0) {
-    if (mode == 1)
-        hipLaunchKernelGGL((hadi_pass_a<B, G, 4, NG, PD, false, 1>), dim3(pl.grid_a), dim3(64 * pl.W * G * NG), pl.smem_a, s, a, n);
-    else if (mode == 2)
-        hipLaunchKernelGGL((hadi_pass_a<B, G, 4, NG, PD, false, 2>), dim3(pl.grid_a), dim3(64 * pl.W * G * NG), pl.smem_a, s, a, n);
-    else if (a.american)
-        hipLaunchKernelGGL((hadi_pass_a<B, G, 4, NG, PD, true>), dim3(pl.grid_a), dim3(64 * pl.W * G * NG), pl.smem_a, s, a, n);
-    else
-        hipLaunchKernelGGL((hadi_pass_a<B, G, 4, NG, PD, false>), dim3(pl.grid_a), dim3(64 * pl.W * G * NG), pl.smem_a, s, a, n);
-}
-
-// fp32-state row pass: same geometry, the LDS ring holds floats (the coefficient arrays and tables stay double)
-template <int B, int G, int NG, int PD>
-void launch_pass_a_f32(const HadiPlan &pl, const HadiSweepArgs &a, int n, hipStream_t s) {
-    const size_t ring_elems = (size_t)NG * ((PD + 1) * pl.W + 4) * pl.L.rowp;
-    const size_t smem = pl.smem_a - ring_elems * (sizeof(double) - sizeof(float));
-    hipLaunchKernelGGL((hadi_pass_a<B, G, 4, NG, PD, false, 0, float>), dim3(pl.grid_a), dim3(64 * pl.W * G * NG), smem, s, a, n);
-}
-
-// American, P representation (no lambda_bar array): shared-ring kernel with the payoff row behind the tables in LDS
-template <int B, int G, int NG, int PD>
-void launch_pass_a_amp(const HadiPlan &pl, const HadiSweepArgs &a, int n, hipStream_t s) {
-    hipLaunchKernelGGL((hadi_pass_a<B, G, 4, NG, PD, 2>), dim3(pl.grid_a), dim3(64 * pl.W * G * NG),
-                       pl.smem_a + (size_t)pl.L.rowp * sizeof(double), s, a, n);
-}
-
-// Kernels whose dynamic LDS can exceed the 64 KiB default need the limit raised once.
+// Kernels whose dynamic LDS can exceed the 64 KiB default need the limit raised once (hadi_create: every kernel of
+// hadi_for_each_kernel).
 template <class K>
 hipError_t raise_lds_limit(K kernel) {
     return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-template <int B, int G, int NG, int PD>
-hipError_t raise_pass_a() {
-    hipError_t e = raise_lds_limit(hadi_pass_a<B, G, 4, NG, PD, false>);
-    if (e == hipSuccess) e = raise_lds_limit(hadi_pass_a<B, G, 4, NG, PD, false, 1>);
-    if (e == hipSuccess) e = raise_lds_limit(hadi_pass_a<B, G, 4, NG, PD, false, 2>);
-    return e != hipSuccess ? e : raise_lds_limit(hadi_pass_a<B, G, 4, NG, PD, true>);
-}
-template <int B, int G, int NG, int PD, int SCH>
-hipError_t raise_pass_a_sch() {
-    hipError_t e = raise_lds_limit(hadi_pass_a_sch<B, G, 4, NG, PD, 1, SCH>);
-    return e != hipSuccess ? e : raise_lds_limit(hadi_pass_a_sch<B, G, 4, NG, PD, 2, SCH>);
-}
-// the Modified Craig-Sneyd / Hundsdorfer-Verwer row passes of one scheme (shared ring and strips)
-template <int SCH>
-hipError_t raise_sch_lds_limits() {
-    hipError_t e;
-    if ((e = raise_pass_a_sch<1, 1, 1, 2, SCH>()) != hipSuccess) return e;
-    if ((e = raise_pass_a_sch<2, 1, 1, 2, SCH>()) != hipSuccess) return e;
-    if ((e = raise_pass_a_sch<4, 1, 1, 2, SCH>()) != hipSuccess) return e;
-    if ((e = raise_pass_a_sch<8, 1, 1, 1, SCH>()) != hipSuccess) return e;
-    if ((e = raise_pass_a_sch<8, 2, 1, 1, SCH>()) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip_sch<8, 1, 1, SCH>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip_sch<8, 1, 2, SCH>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip_sch<4, 1, 1, SCH>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip_sch<4, 1, 2, SCH>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip_sch<2, 1, 1, SCH>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip_sch<2, 1, 2, SCH>)) != hipSuccess) return e;
-    return raise_lds_limit(hadi_pass_a_strip_sch<8, 2, 2, SCH>);
-}
-hipError_t raise_all_lds_limits() {
-    hipError_t e;
-    if ((e = raise_sch_lds_limits<HADI_SCH_MCS>()) != hipSuccess) return e;
-    if ((e = raise_sch_lds_limits<HADI_SCH_HV>()) != hipSuccess) return e;
-    if ((e = raise_pass_a<1, 1, 1, 2>()) != hipSuccess) return e;
-    if ((e = raise_pass_a<2, 1, 1, 2>()) != hipSuccess) return e;
-    if ((e = raise_pass_a<4, 1, 1, 2>()) != hipSuccess) return e;
-    if ((e = raise_pass_a<8, 1, 1, 1>()) != hipSuccess) return e;
-    if ((e = raise_pass_a<8, 2, 1, 1>()) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<8, false>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<8, true>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<4, false>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<4, true>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<2, false>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<2, true>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<8, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<4, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<2, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_pairs<0>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_pairs<1>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_pairs<2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_team_kernel<8>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_team_kernel<4>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_sweep_resident<8>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_small_seq2_kernel<1>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_small_seq2_kernel<2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_small_seq_kernel<1>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_small_seq_kernel<2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_small_kernel<1, 4, false>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_small_kernel<1, 4, true>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_small_kernel<2, 4, false>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_small_kernel<2, 4, true>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_small_kernel<1, 8, false>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_small_kernel<1, 8, true>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_small_kernel<2, 8, false>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_small_kernel<2, 8, true>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_b<8, false>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_b<8, true>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_b1<16, false>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_b2<16, double, HADI_B2_NPF(8)>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_b2<16, float, HADI_B2_NPF(4)>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_b<8, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_b1<16, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a<1, 1, 4, 1, 2, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a<2, 1, 4, 1, 2, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a<4, 1, 4, 1, 2, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a<8, 1, 4, 1, 1, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a<8, 2, 4, 1, 1, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<8, false, float>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<8, false, float, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<8, false, double, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<8, 1, double, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a_strip<8, 2, double, 2>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_b<8, false, float>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_b1<16, false, float>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a<1, 1, 4, 1, 2, false, 0, float>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a<2, 1, 4, 1, 2, false, 0, float>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a<4, 1, 4, 1, 2, false, 0, float>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a<8, 1, 4, 1, 1, false, 0, float>)) != hipSuccess) return e;
-    if ((e = raise_lds_limit(hadi_pass_a<8, 2, 4, 1, 1, false, 0, float>)) != hipSuccess) return e;
-    return raise_lds_limit(hadi_pass_b1<16, true>);
 }
 
 // ---- run_sweep, part 1: how the batch is cut ---------------------------------------------------------------------------
@@ -462,228 +344,22 @@ int plan_batches(Ctx *c, const SweepDesc &d, HadiPlan &pl, int state_bytes, bool
 }
 
 // ---- run_sweep, part 2: which kernel runs a pass -----------------------------------------------------------------------
-// Everything the choice depends on (the selection rules themselves: hadi_plan.h and DESIGN.md section 4.1).
-struct PassEnv {
-    const HadiPlan &pl;      // launch geometry of THIS sub-batch
-    const HadiLayout &L;
-    int nsb;                 // instances of the sub-batch
-    hipStream_t q;
-    int nstep;
-    bool american, amp, xstep, f32;  // amp: P representation; xstep: this step runs on the explicit (U, lambda_bar) pair
-    int col_prefetch;
-    int cs_strips;                   // Craig-Sneyd row passes on strips where the plan chose strips (tuning key "cs_strips", default on)
-    int scheme;                      // enum hadi_scheme: which predictor / corrector kernels modes 1 / 2 run
-};
-template <int B, int G, int NG, int PD, int SCH>
-void launch_pass_a_sch(const HadiPlan &pl, const HadiSweepArgs &a, int n, hipStream_t s, int mode) {
-    if (mode == 1) hipLaunchKernelGGL((hadi_pass_a_sch<B, G, 4, NG, PD, 1, SCH>), dim3(pl.grid_a), dim3(64 * pl.W * G * NG), pl.smem_a, s, a, n);
-    else hipLaunchKernelGGL((hadi_pass_a_sch<B, G, 4, NG, PD, 2, SCH>), dim3(pl.grid_a), dim3(64 * pl.W * G * NG), pl.smem_a, s, a, n);
-}
-template <int B, int G, int SCH>
-void launch_strip_sch(const HadiPlan &pl, const HadiSweepArgs &a, int n, hipStream_t s, int mode) {
-    const dim3 g(pl.grid_as), b(64 * HADI_STRIP_WAVES(B));
-    if (mode == 1) hipLaunchKernelGGL((hadi_pass_a_strip_sch<B, G, 1, SCH>), g, b, pl.smem_as, s, a, n);
-    else hipLaunchKernelGGL((hadi_pass_a_strip_sch<B, G, 2, SCH>), g, b, pl.smem_as, s, a, n);
-}
-// Predictor (mode 1) / corrector (mode 2) row pass of a Modified Craig-Sneyd or Hundsdorfer-Verwer step: the same choice of
-// strips or shared ring as for Craig-Sneyd (launch_row_pass), on the kernels of the scheme.
-template <int SCH>
-void launch_row_pass_sch(const PassEnv &e, const HadiSweepArgs &ar, int mode) {
-    const HadiPlan &pl = e.pl; const HadiLayout &L = e.L; const int nstep = e.nstep; hipStream_t q = e.q;
-    // (paired strips: the corrector only -- the predictor of those shapes runs on the shared ring, see hadi_pass_a_strip_sch)
-    if (pl.use_strip && !pl.use_pairs && (e.cs_strips == 1 || e.cs_strips == 1 + mode) && !(L.G == 2 && mode == 1)) {
-        if (L.G == 2) hipLaunchKernelGGL((hadi_pass_a_strip_sch<8, 2, 2, SCH>), dim3(pl.grid_as), dim3(64 * HADI_STRIP_WAVES(8)), pl.smem_as, q, ar, nstep);
-        else if (L.B == 8) launch_strip_sch<8, 1, SCH>(pl, ar, nstep, q, mode);
-        else if (L.B == 4) launch_strip_sch<4, 1, SCH>(pl, ar, nstep, q, mode);
-        else launch_strip_sch<2, 1, SCH>(pl, ar, nstep, q, mode);
-        return;
-    }
-    switch (L.B * 10 + L.G) {
-        case 11: launch_pass_a_sch<1, 1, 1, 2, SCH>(pl, ar, nstep, q, mode); break;
-        case 21: launch_pass_a_sch<2, 1, 1, 2, SCH>(pl, ar, nstep, q, mode); break;
-        case 41: launch_pass_a_sch<4, 1, 1, 2, SCH>(pl, ar, nstep, q, mode); break;
-        case 81: launch_pass_a_sch<8, 1, 1, 1, SCH>(pl, ar, nstep, q, mode); break;
-        default: launch_pass_a_sch<8, 2, 1, 1, SCH>(pl, ar, nstep, q, mode); break;
-    }
-}
-// Row pass of one time step.  mode: 0 Douglas, 1 / 2 predictor / corrector of the scheme e.scheme (Craig-Sneyd, MCS, HV).
-void launch_row_pass(const PassEnv &e, const HadiSweepArgs &ar, int mode) {
-    if (mode != 0 && e.scheme == HADI_SCHEME_MCS) return launch_row_pass_sch<HADI_SCH_MCS>(e, ar, mode);
-    if (mode != 0 && e.scheme == HADI_SCHEME_HV) return launch_row_pass_sch<HADI_SCH_HV>(e, ar, mode);
-    const HadiPlan &pl = e.pl; const HadiLayout &L = e.L; const int nsb = e.nsb, nstep = e.nstep; hipStream_t q = e.q;
-    const bool american = e.american, amp = e.amp, xstep = e.xstep, f32 = e.f32;
-    if (pl.row_seq) {  // more than 1024 s-intervals: one lane per v-row, sequential along s
-        const dim3 g((unsigned)(nsb * ((L.nrows + 63) / 64))), b(64);
-        if (american) hipLaunchKernelGGL((hadi_pass_a_seq<1>), g, b, 0, q, ar, nstep);
-        else hipLaunchKernelGGL((hadi_pass_a_seq<0>), g, b, 0, q, ar, nstep);
-        return;
-    }
-    if (pl.use_pairs && pl.use_strip && mode == 0 && !f32) {  // 4 nodes per lane: two strips per wavefront
-        const dim3 g(pl.grid_as), b(64 * HADI_PAIR_WAVES);
-        if (amp && !xstep) hipLaunchKernelGGL((hadi_pass_a_pairs<2>), g, b, pl.smem_pairs_amp, q, ar, nstep);
-        else if (american) hipLaunchKernelGGL((hadi_pass_a_pairs<1>), g, b, pl.smem_pairs_eu, q, ar, nstep);
-        else hipLaunchKernelGGL((hadi_pass_a_pairs<0>), g, b, pl.smem_pairs_eu, q, ar, nstep);
-        return;
-    }
-    if (amp && !xstep && pl.use_strip && mode == 0) {  // P representation on barrier-free strips
-        const dim3 g(pl.grid_as), b(64 * HADI_STRIP_WAVES(L.B));
-        const size_t sm = pl.smem_as + (size_t)L.rowp * sizeof(double);  // + the payoff row
-        if (L.G == 2) {  // paired strips (two wavefronts per row)
-            hipLaunchKernelGGL((hadi_pass_a_strip<8, 2, double, 2>), g, b, sm, q, ar, nstep);
-            return;
-        }
-        switch (L.B) {
-            case 8: hipLaunchKernelGGL((hadi_pass_a_strip<8, 2>), g, b, sm, q, ar, nstep); break;
-            case 4: hipLaunchKernelGGL((hadi_pass_a_strip<4, 2>), g, b, sm, q, ar, nstep); break;
-            default: hipLaunchKernelGGL((hadi_pass_a_strip<2, 2>), g, b, sm, q, ar, nstep); break;
-        }
-        return;
-    }
-    if (amp && !xstep) {
-        switch (L.B * 10 + L.G) {
-            case 11: launch_pass_a_amp<1, 1, 1, 2>(pl, ar, nstep, q); break;
-            case 21: launch_pass_a_amp<2, 1, 1, 2>(pl, ar, nstep, q); break;
-            case 41: launch_pass_a_amp<4, 1, 1, 2>(pl, ar, nstep, q); break;
-            case 81: launch_pass_a_amp<8, 1, 1, 1>(pl, ar, nstep, q); break;
-            default: launch_pass_a_amp<8, 2, 1, 1>(pl, ar, nstep, q); break;
-        }
-        return;
-    }
-    if (f32 && pl.use_strip && L.B == 8 && L.G == 2) {  // fp32 state, 512 < m1 <= 1024: paired strips
-        hipLaunchKernelGGL((hadi_pass_a_strip<8, false, float, 2>), dim3(pl.grid_as), dim3(512), pl.smem_as, q, ar, nstep);
-        return;
-    }
-    if (f32 && pl.use_strip && L.B == 8) {  // fp32 state, 8 nodes per lane, large batch: strips with a ring of floats
-        const size_t smem = (size_t)8 * 4 * L.rowp * sizeof(float) + (size_t)4 * 64 * L.B * sizeof(double);
-        hipLaunchKernelGGL((hadi_pass_a_strip<8, false, float>), dim3(pl.grid_as), dim3(512), smem, q, ar, nstep);
-        return;
-    }
-    if (f32) {  // fp32 state: shared-ring kernel for the other shapes
-        switch (L.B * 10 + L.G) {
-            case 11: launch_pass_a_f32<1, 1, 1, 2>(pl, ar, nstep, q); break;
-            case 21: launch_pass_a_f32<2, 1, 1, 2>(pl, ar, nstep, q); break;
-            case 41: launch_pass_a_f32<4, 1, 1, 2>(pl, ar, nstep, q); break;
-            case 81: launch_pass_a_f32<8, 1, 1, 1>(pl, ar, nstep, q); break;
-            default: launch_pass_a_f32<8, 2, 1, 1>(pl, ar, nstep, q); break;
-        }
-        return;
-    }
-    if (pl.use_strip && mode != 0 && !pl.use_pairs && (e.cs_strips == 1 || e.cs_strips == 1 + mode)) {  // (2 / 3: diagnostics -- only the predictor / only the corrector on strips)  // Craig-Sneyd predictor / corrector on strips (European, fp64)
-        const dim3 g(pl.grid_as), b(64 * HADI_STRIP_WAVES(L.B));
-        if (L.G == 2) {
-            if (mode == 1) hipLaunchKernelGGL((hadi_pass_a_strip<8, 0, double, 2, 1>), g, b, pl.smem_as, q, ar, nstep);
-            else hipLaunchKernelGGL((hadi_pass_a_strip<8, 0, double, 2, 2>), g, b, pl.smem_as, q, ar, nstep);
-            return;
-        }
-        switch (L.B * 4 + mode) {
-            case 33: hipLaunchKernelGGL((hadi_pass_a_strip<8, 0, double, 1, 1>), g, b, pl.smem_as, q, ar, nstep); break;
-            case 34: hipLaunchKernelGGL((hadi_pass_a_strip<8, 0, double, 1, 2>), g, b, pl.smem_as, q, ar, nstep); break;
-            case 17: hipLaunchKernelGGL((hadi_pass_a_strip<4, 0, double, 1, 1>), g, b, pl.smem_as, q, ar, nstep); break;
-            case 18: hipLaunchKernelGGL((hadi_pass_a_strip<4, 0, double, 1, 2>), g, b, pl.smem_as, q, ar, nstep); break;
-            case 9: hipLaunchKernelGGL((hadi_pass_a_strip<2, 0, double, 1, 1>), g, b, pl.smem_as, q, ar, nstep); break;
-            default: hipLaunchKernelGGL((hadi_pass_a_strip<2, 0, double, 1, 2>), g, b, pl.smem_as, q, ar, nstep); break;
-        }
-        return;
-    }
-    if (pl.use_strip && mode == 0 && L.G == 2) {  // paired strips (Douglas step, two wavefronts per row)
-        if (american) hipLaunchKernelGGL((hadi_pass_a_strip<8, 1, double, 2>), dim3(pl.grid_as), dim3(512), pl.smem_as, q, ar, nstep);
-        else hipLaunchKernelGGL((hadi_pass_a_strip<8, false, double, 2>), dim3(pl.grid_as), dim3(512), pl.smem_as, q, ar, nstep);
-        return;
-    }
-    if (pl.use_strip && mode == 0) {  // barrier-free strips (Douglas step, one wavefront per row)
-        const dim3 g(pl.grid_as), b(64 * HADI_STRIP_WAVES(L.B));
-        switch (L.B * 2 + (american ? 1 : 0)) {
-            case 16: hipLaunchKernelGGL((hadi_pass_a_strip<8, false>), g, b, pl.smem_as, q, ar, nstep); break;
-            case 17: hipLaunchKernelGGL((hadi_pass_a_strip<8, true>), g, b, pl.smem_as, q, ar, nstep); break;
-            case 8: hipLaunchKernelGGL((hadi_pass_a_strip<4, false>), g, b, pl.smem_as, q, ar, nstep); break;
-            case 9: hipLaunchKernelGGL((hadi_pass_a_strip<4, true>), g, b, pl.smem_as, q, ar, nstep); break;
-            case 4: hipLaunchKernelGGL((hadi_pass_a_strip<2, false>), g, b, pl.smem_as, q, ar, nstep); break;
-            default: hipLaunchKernelGGL((hadi_pass_a_strip<2, true>), g, b, pl.smem_as, q, ar, nstep); break;
-        }
-        return;
-    }
-    switch (L.B * 10 + L.G) {
-        case 11: launch_pass_a<1, 1, 1, 2>(pl, ar, nstep, q, mode); break;
-        case 21: launch_pass_a<2, 1, 1, 2>(pl, ar, nstep, q, mode); break;
-        case 41: launch_pass_a<4, 1, 1, 2>(pl, ar, nstep, q, mode); break;
-        case 81: launch_pass_a<8, 1, 1, 1>(pl, ar, nstep, q, mode); break;
-        default: launch_pass_a<8, 2, 1, 1>(pl, ar, nstep, q, mode); break;
-    }
-}
-
-// Column pass of one time step.
-void launch_col_pass(const PassEnv &e, const HadiSweepArgs &ar) {
-    const HadiPlan &pl = e.pl; const HadiLayout &L = e.L; const int nsb = e.nsb, nstep = e.nstep; hipStream_t q = e.q;
-    const bool american = e.american, amp = e.amp, xstep = e.xstep, f32 = e.f32;
-    // up to 8 chunks: 512-thread blocks with two register buffers (2 waves per SIMD); 9..16 chunks: the
-    // 1024-thread block leaves 128 VGPRs per lane, which only the single-buffer kernel fits
-    // (measured at 1024x512: 0.250 vs 0.382 ms/launch for the double-buffered code, which spills)
-    const dim3 g(pl.grid_b), b(pl.block_b);
-    if (pl.col_seq) {  // more than 16 chunks of v-rows: one lane per storage column, sequential along v
-        const dim3 gs((unsigned)(nsb * pl.ctiles)), bs(64);
-        if (american) hipLaunchKernelGGL((hadi_pass_b_seq<1>), gs, bs, 0, q, ar, nstep);
-        else hipLaunchKernelGGL((hadi_pass_b_seq<0>), gs, bs, 0, q, ar, nstep);
-        return;
-    }
-    if (amp && !xstep) {
-        if (L.P <= 8) hipLaunchKernelGGL((hadi_pass_b<8, 2>), g, b, pl.smem_b, q, ar, nstep);
-        else hipLaunchKernelGGL((hadi_pass_b1<16, 2>), g, b, pl.smem_b, q, ar, nstep);
-        return;
-    }
-    if (f32) {
-        if (L.P <= 8) hipLaunchKernelGGL((hadi_pass_b<8, false, float>), g, b, pl.smem_b, q, ar, nstep);
-        else if (e.col_prefetch) hipLaunchKernelGGL((hadi_pass_b2<16, float, HADI_B2_NPF(4)>), g, b, pl.smem_b2, q, ar, nstep);
-        else hipLaunchKernelGGL((hadi_pass_b1<16, false, float>), g, b, pl.smem_b, q, ar, nstep);
-        return;
-    }
-    if (L.P <= 8) {
-        if (american) hipLaunchKernelGGL((hadi_pass_b<8, true>), g, b, pl.smem_b, q, ar, nstep);
-        else hipLaunchKernelGGL((hadi_pass_b<8, false>), g, b, pl.smem_b, q, ar, nstep);
-    } else {
-        if (american) hipLaunchKernelGGL((hadi_pass_b1<16, true>), g, b, pl.smem_b, q, ar, nstep);
-        else if (e.col_prefetch) hipLaunchKernelGGL((hadi_pass_b2<16, double, HADI_B2_NPF(8)>), g, b, pl.smem_b2, q, ar, nstep);
-        else hipLaunchKernelGGL((hadi_pass_b1<16, false>), g, b, pl.smem_b, q, ar, nstep);
-    }
+// The choice, the launch geometry and the words are hadi_dispatch.h's (the rules: DESIGN.md section 4.1); this launches it.
+int launch_pass(Ctx *c, const HadiSel &sel, hipStream_t q, const HadiSweepArgs &ar, int nstep) {
+    if (!sel.k) return fail(c, HADI_ERR_INTERNAL, "no kernel for this pass (grid %dx%d)", ar.L.m1, ar.L.m2);
+    hipLaunchKernelGGL((sel.k->fn), dim3(sel.grid), dim3(sel.block), sel.smem, q, ar, nstep);
+    return HADI_OK;
 }
 
 // ---- run_sweep, part 3: the kernels of the streaming path in words (hadi_describe_last_sweep) ------------------------
-std::string describe_streaming_path(const Ctx *c, const HadiPlan &pl, const BatchPlan &bp, bool american, bool amp, int scheme, bool f32) {
-    const bool cs = scheme != HADI_SCHEME_DOUGLAS;
-    const char *sch = scheme == HADI_SCHEME_MCS ? "MCS" : scheme == HADI_SCHEME_HV ? "HV" : "CS";
-    const char *strip_k = scheme == HADI_SCHEME_CRAIG_SNEYD ? "hadi_pass_a_strip" : "hadi_pass_a_strip_sch";
-    const char *ring_k = scheme == HADI_SCHEME_MCS || scheme == HADI_SCHEME_HV ? "hadi_pass_a_sch" : "hadi_pass_a";
-    const HadiLayout &L = pl.L;
+std::string describe_streaming_path(const HadiPassCtx &pc, const BatchPlan &bp) {
     const std::vector<SubBatch> &subs = bp.subs;
     const int nsub = (int)subs.size();
     const bool two_streams = bp.two_streams;
     const int fork_before = bp.fork_before;
-    std::string last_path;
     char buf[384];
-    char rowk[160];
-    if (amp && pl.use_strip && !cs && L.G == 2) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<8,AM-P,double,2> (paired strips of %d rows, no lambda_bar array)", pl.RS);
-    else if (amp && pl.use_strip && !cs) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<%d,AM-P> (strips of %d rows, no lambda_bar array)", L.B, pl.RS);
-    else if (amp) std::snprintf(rowk, sizeof rowk, "hadi_pass_a<%d,%d,%d,%d,%d,AM-P> (tiles of %d rows, no lambda_bar array)", L.B, L.G, pl.W, pl.NG, pl.PD, pl.R);
-    else if (f32 && pl.use_strip && L.B == 8 && L.G == 2) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<8,EU,float,2> (paired strips of %d rows, fp32 state)", pl.RS);
-    else if (f32 && pl.use_strip && L.B == 8) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<8,EU,float> (strips of %d rows, fp32 state)", pl.RS);
-    else if (f32) std::snprintf(rowk, sizeof rowk, "hadi_pass_a<%d,%d,%d,%d,%d,EU,float> (tiles of %d rows, fp32 state)", L.B, L.G, pl.W, pl.NG, pl.PD, pl.R);
-    else if (pl.use_strip && cs && c->cs_strips && !pl.use_pairs && L.G == 2) std::snprintf(rowk, sizeof rowk, "%s<8,EU,double,2,%s> (paired strips of %d rows%s)", strip_k, sch, pl.RS,
-                      scheme == HADI_SCHEME_CRAIG_SNEYD ? "" : "; the predictor on hadi_pass_a_sch");
-    else if (pl.use_strip && cs && c->cs_strips && !pl.use_pairs) std::snprintf(rowk, sizeof rowk, "%s<%d,EU,double,1,%s> (strips of %d rows)", strip_k, L.B, sch, pl.RS);
-    else if (pl.use_strip && !cs && L.G == 2) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<8,%s,double,2> (paired strips of %d rows)", american ? "AM" : "EU", pl.RS);
-    else if (pl.use_strip && !cs) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_strip<%d,%s> (strips of %d rows)", L.B, american ? "AM" : "EU", pl.RS);
-    else std::snprintf(rowk, sizeof rowk, "%s<%d,%d,%d,%d,%d,%s%s%s> (tiles of %d rows)", ring_k, L.B, L.G, pl.W, pl.NG, pl.PD,
-                       american ? "AM" : "EU", cs ? "," : "", cs ? sch : "", pl.R);
-    if (pl.use_pairs && pl.use_strip && !cs && !f32)
-        std::snprintf(rowk, sizeof rowk, "hadi_pass_a_pairs<%s> (two strips of %d rows per wavefront%s)", amp ? "AM-P" : american ? "AM" : "EU", pl.RS,
-                      amp ? ", no lambda_bar array" : "");
-    if (pl.row_seq) std::snprintf(rowk, sizeof rowk, "hadi_pass_a_seq<%s> (one lane per v-row, sequential along s)", american ? "AM" : "EU");
-    if (pl.col_seq)
-        std::snprintf(buf, sizeof buf, "row pass %s; column pass hadi_pass_b_seq<%s> (one lane per column, sequential along v)", rowk, american ? "AM" : "EU");
-    else
-        std::snprintf(buf, sizeof buf, "row pass %s; column pass %s<%d,%s> (%d chunks of %d rows, %d column tiles per block)", rowk,
-                      L.P <= 8 ? "hadi_pass_b" : (!american && c->col_prefetch) ? "hadi_pass_b2" : "hadi_pass_b1", L.P <= 8 ? 8 : 16,
-                      amp ? "AM-P" : american ? "AM" : "EU", L.P, HADI_LC, pl.btpw);
-    last_path = buf;
+    hadi_describe_passes(pc, buf, sizeof buf);
+    std::string last_path = buf;
     if (nsub > 1) {
         bool same = true;
         for (auto &sbt : subs) same = same && sbt.cnt == subs[0].cnt;
@@ -873,8 +549,10 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     // less than HADI_TWO_STREAM_IDLE of them idle -- a block that waited for a second round would wait for a whole time loop.
     // Other sub-batches of the same call (a small remainder) stay on the streaming kernels.  "resident_sweep" = -1 (default):
     // wherever eligible unless the caller pinned the streaming geometry; 1: wherever eligible; 0: never.
-    const bool geo_pinned = c->tune.strip >= 0 || c->tune.row_tile > 0 || c->tune.col_groups > 0 || c->tune.strip_blocks > 0;
-    const bool resident_shape = (c->resident_sweep > 0 || (c->resident_sweep < 0 && !geo_pinned)) && d.scheme == HADI_SCHEME_DOUGLAS &&
+    // (a caller who pins the streaming kernels' geometry -- hadi_set_tuning "strip", "row_tile", "col_groups", "strip_blocks" --
+    // gets those kernels: neither the resident sweep nor, below, the team launch is chosen automatically)
+    const bool pinned = c->tune.strip >= 0 || c->tune.row_tile > 0 || c->tune.col_groups > 0 || c->tune.strip_blocks > 0;
+    const bool resident_shape = (c->resident_sweep > 0 || (c->resident_sweep < 0 && !pinned)) && d.scheme == HADI_SCHEME_DOUGLAS &&
                                 d.variant == HADI_EU && !f32 && L.B == 8 && L.G == 1 && L.P <= 8 && !seq_shape && d.theta > 0.0 &&
                                 d.r_d != d.r_f && !d.debug && !c->debug_fault && !prof;  // (test hooks: the streaming kernels they are for)
     auto resident = [&](const SubBatch &sbt) {
@@ -903,12 +581,10 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
         if (pair_tab && pl.use_strip) {  // paired strips: the pairs' coupling column, once per solve (hadi_strip_step, RSTAB)
             HadiSweepArgs at = a;
             at.U = Ub;  // (any packed fp64 array: the table depends on the matrix only)
-            // (its own LDS size: the fp64 ring of 4 pairs x 3 slots, whatever the state precision of the sweep -- hadi_plan.h)
-            const size_t sm = (size_t)4 * HADI_STRIP_NS(8, 2, 8) * L.rowp * sizeof(double) + ((size_t)4 * 64 * 8 * 2 + (size_t)4 * 16) * sizeof(double);
-            hipLaunchKernelGGL((hadi_pass_a_strip<8, 0, double, 2, 3>), dim3(pl.grid_as), dim3(512), sm, q, at, 1);
+            if ((rc = launch_pass(c, hadi_select_pair_table(pl), q, at, 1))) return rc;
         }
         if (resident(subs[sb])) {  // the sub-batch's whole time loop in one launch (LDS: the strip rings; the column phase aliases them)
-            hipLaunchKernelGGL((hadi_sweep_resident<8>), dim3(pl.grid_as), dim3(64 * HADI_STRIP_WAVES(8)), std::max(pl.smem_as, pl.smem_b), q, a, n_last);
+            if ((rc = launch_pass(c, hadi_select_resident(pl), q, a, n_last))) return rc;
             continue;
         }
         for (int nstep = n_first; nstep <= n_last; nstep++) {
@@ -929,25 +605,24 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
                     hipLaunchKernelGGL(hadi_narrow_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, Ub, reinterpret_cast<float *>(a.U), tot);
             }
             if (prof) HIP_TRY(c, hipEventRecord(c->kev[ev0 + 4 * (nstep - 1) + 0], q));
-            const PassEnv env{pl, L, nsb, q, nstep, american, amp, xstep, f32, c->col_prefetch, c->cs_strips, d.scheme};
-            auto row_pass = [&](const HadiSweepArgs &ar, int mode) { launch_row_pass(env, ar, mode); };
-            auto col_pass = [&](const HadiSweepArgs &ar) { launch_col_pass(env, ar); };
+            const HadiPassCtx pc{pl, nsb, american, amp, xstep, f32, d.scheme, c->cs_strips, c->col_prefetch};
+            auto row_pass = [&](const HadiSweepArgs &ar, int mode) { return launch_pass(c, hadi_select_row_pass(pc, mode), q, ar, nstep); };
+            auto col_pass = [&](const HadiSweepArgs &ar) { return launch_pass(c, hadi_select_col_pass(pc), q, ar, nstep); };
             if (d.debug == 2) {  // diagnostics: one column solve of the packed input (moved to Y), nothing else
                 HIP_TRY(c, hipMemcpyAsync(a.Y, a.U, f32 ? st / 2 : st, hipMemcpyDeviceToDevice, q));
-                col_pass(a);
+                if ((rc = col_pass(a))) return rc;
                 break;
             }
-            row_pass(a, cs ? 1 : 0);
+            if ((rc = row_pass(a, cs ? 1 : 0))) return rc;
             if (d.debug == 1) break;  // diagnostics: Y now holds the right-hand side of the A2 solve
             if (prof) {
                 HIP_TRY(c, hipEventRecord(c->kev[ev0 + 4 * (nstep - 1) + 1], q));
                 HIP_TRY(c, hipEventRecord(c->kev[ev0 + 4 * (nstep - 1) + 2], q));
             }
-            col_pass(cs ? av : a);
+            if ((rc = col_pass(cs ? av : a))) return rc;
             if (prof) HIP_TRY(c, hipEventRecord(c->kev[ev0 + 4 * (nstep - 1) + 3], q));
             if (cs) {  // corrector (profiling events cover the predictor's two passes only)
-                row_pass(av, 2);
-                col_pass(a);
+                if ((rc = row_pass(av, 2)) || (rc = col_pass(a))) return rc;
             }
             if (xstep)
                 hipLaunchKernelGGL(hadi_am_dematerialise_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, nsb, a.ipar, U0b, Ub, LAMb);
@@ -971,14 +646,13 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     };
 
     // ---- small grids: the whole instance fits in LDS -> one launch runs the entire time loop ----------
-    const size_t smem_small = american ? pl.smem_small_am : pl.smem_small_eu;
     // European / dividend sweeps: one wavefront per instance with sequential line solves (hadi_small_seq_kernel) issues about
     // half the instructions per instance and step but runs them on ONE wavefront -- ahead once there are more instances than
     // CUs (50x25, 40 steps, ms block kernel / this one: 256 instances 0.49 / 0.55, 320: 0.67 / 0.60, 512: 0.71 / 0.63, 768: 0.95 /
     // 0.80; 3000 x 50 steps: 3.75 / 2.13), behind below that (a single instance: 10 against 12 us per step).
     // "small_seq" = 1 forces it, 0 forbids it, -1 (default) picks by batch size.
     const bool seq = takes_small_path && !american && (c->small_seq > 0 || (c->small_seq < 0 && d.n > c->cu_count));
-    const size_t smem_seq = (size_t)hadi_small_seq_layout(L.m1, L.nrows).total * sizeof(double);
+    const size_t smem_seq = hadi_small_seq_smem(L);
     // ... and two instances per wavefront for batches of more than 2 and at most 4.5 instances per CU: a wavefront then retires
     // two instances' steps in 1.15x the time of one, but the launch has half the wavefronts -- below 2 per CU the instances are
     // better spread over the CUs, at the 6 per CU that the LDS holds either way the halved instruction count and the halved
@@ -987,6 +661,12 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     const bool seq2 = seq && L.nrows <= 32 && 2 * smem_seq <= (size_t)160 * 1024 &&
                       (c->small_pairs > 0 || (c->small_pairs < 0 && d.n > 2 * c->cu_count && 2 * d.n <= 9 * c->cu_count));
     if (takes_small_path) {
+        // wavefronts per instance: 4 when the batch fills the GPU (throughput), 8 for small batches (latency of the
+        // dependent per-step phases; more waves share the rows of the row pass)
+        // (measured, 50x25 grid: 1 instance x 100 steps 1.27 -> 1.04 ms with 8; 3000 instances x 50 steps 4.19 -> 4.58 ms)
+        const int sw = c->tune.small_waves ? c->tune.small_waves : (d.n <= 2 * c->cu_count ? 8 : 4);
+        const HadiSel sel = hadi_select_small(pl, d.n, seq2 ? 2 : seq ? 1 : 0, sw, american);
+        if (!sel.k) return fail(c, HADI_ERR_INTERNAL, "no small-grid kernel for grid %dx%d", d.m1, d.m2);
         {
             char buf[192];
             if (seq2)
@@ -995,7 +675,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
                 std::snprintf(buf, sizeof buf, "hadi_small_seq_kernel<%d>: whole time loop in one launch, one wavefront per instance, lines solved sequentially in LDS (%zu B)", L.B, smem_seq);
             else
                 std::snprintf(buf, sizeof buf, "hadi_small_kernel<%d,%d,%s>: whole time loop in one launch, instance resident in LDS (%zu B)", L.B,
-                              (c->tune.small_waves ? c->tune.small_waves : (d.n <= 2 * c->cu_count ? 8 : 4)) == 8 ? 8 : 4, american ? "AM" : "EU", smem_small);
+                              sel.k->G, american ? "AM" : "EU", sel.smem);
             c->last_path = buf;
         }
         HadiSmallArgs sm;
@@ -1016,37 +696,13 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
             sm.div_flag = ptr<int>(c->div_flag); sm.div_amounts = ptr<double>(c->div_amt); sm.div_pcts = ptr<double>(c->div_pct);
         }
         HIP_TRY(c, hipEventRecord(c->ev[1], s));
-        // wavefronts per instance: 4 when the batch fills the GPU (throughput), 8 for small batches (latency of the
-        // dependent per-step phases; more waves share the rows of the row pass)
-        // (measured, 50x25 grid: 1 instance x 100 steps 1.27 -> 1.04 ms with 8; 3000 instances x 50 steps 4.19 -> 4.58 ms)
-        const int sw = c->tune.small_waves ? c->tune.small_waves : (d.n <= 2 * c->cu_count ? 8 : 4);
-        if (seq2) {
-            if (L.B == 1) hipLaunchKernelGGL((hadi_small_seq2_kernel<1>), dim3((d.n + 1) / 2), dim3(64), 2 * smem_seq, s, a, sm);
-            else hipLaunchKernelGGL((hadi_small_seq2_kernel<2>), dim3((d.n + 1) / 2), dim3(64), 2 * smem_seq, s, a, sm);
-        } else if (seq) {
-            if (L.B == 1) hipLaunchKernelGGL((hadi_small_seq_kernel<1>), dim3(d.n), dim3(64), smem_seq, s, a, sm);
-            else hipLaunchKernelGGL((hadi_small_seq_kernel<2>), dim3(d.n), dim3(64), smem_seq, s, a, sm);
-        } else if (sw == 8) {
-            if (L.B == 1) {
-                if (american) hipLaunchKernelGGL((hadi_small_kernel<1, 8, true>), dim3(d.n), dim3(512), smem_small, s, a, sm);
-                else hipLaunchKernelGGL((hadi_small_kernel<1, 8, false>), dim3(d.n), dim3(512), smem_small, s, a, sm);
-            } else {
-                if (american) hipLaunchKernelGGL((hadi_small_kernel<2, 8, true>), dim3(d.n), dim3(512), smem_small, s, a, sm);
-                else hipLaunchKernelGGL((hadi_small_kernel<2, 8, false>), dim3(d.n), dim3(512), smem_small, s, a, sm);
-            }
-        } else if (L.B == 1) {
-            if (american) hipLaunchKernelGGL((hadi_small_kernel<1, 4, true>), dim3(d.n), dim3(256), smem_small, s, a, sm);
-            else hipLaunchKernelGGL((hadi_small_kernel<1, 4, false>), dim3(d.n), dim3(256), smem_small, s, a, sm);
-        } else {
-            if (american) hipLaunchKernelGGL((hadi_small_kernel<2, 4, true>), dim3(d.n), dim3(256), smem_small, s, a, sm);
-            else hipLaunchKernelGGL((hadi_small_kernel<2, 4, false>), dim3(d.n), dim3(256), smem_small, s, a, sm);
-        }
+        hipLaunchKernelGGL((sel.k->loop), dim3(sel.grid), dim3(sel.block), sel.smem, s, a, sm);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipEventRecord(c->ev[2], s));
         return HADI_OK;
     }
 
-    c->last_path = describe_streaming_path(c, pl, bp, american, amp, d.scheme, f32);
+    c->last_path = describe_streaming_path(HadiPassCtx{pl, d.n, american, amp, false, f32, d.scheme, c->cs_strips, c->col_prefetch}, bp);
     {
         int nres = 0;
         for (const auto &sbt : subs) nres += resident(sbt) ? 1 : 0;
@@ -1064,9 +720,6 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     // recorded by the kernel, checked here, and the batch is solved again on the streaming path below.
     const bool team_shape = d.n <= 8 && L.G == 1 && (L.B == 8 || L.B == 4) && L.P <= 8 && !seq_shape && (d.variant == HADI_EU || d.variant == HADI_DIV) && !cs && !f32 &&
                             !d.debug && !prof && d.theta > 0.0 && d.r_d != d.r_f && c->cu_count == 256;
-    // (a caller who pins the streaming kernels' geometry -- hadi_set_tuning "strip", "row_tile", "col_groups", "strip_blocks" --
-    // gets those kernels)
-    const bool pinned = c->tune.strip >= 0 || c->tune.row_tile > 0 || c->tune.col_groups > 0 || c->tune.strip_blocks > 0;
     if (team_shape && (c->team_launch > 0 || (c->team_launch < 0 && !c->team_failed && !pinned))) {
         if ((rc = ensure(c, c->team, 512 * sizeof(int)))) return rc;
         HIP_TRY(c, hipMemsetAsync(c->team.p, 0, 512 * sizeof(int), s));
@@ -1076,8 +729,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
         ta.div_amounts = have_div ? ptr<double>(c->div_amt) : nullptr; ta.div_pcts = have_div ? ptr<double>(c->div_pct) : nullptr;
         ta.vec_s = d.d_vec_s;
         ta.stamps = reinterpret_cast<unsigned long long *>(ptr<int>(c->team) + 384);
-        const size_t smem = ((size_t)4 * 64 * L.B + hadi_pb_mf_doubles(L.P) + (size_t)L.P * HADI_LC * HADI_PBW +
-                             (have_div ? (size_t)(L.m1 + 2) + (size_t)8 * L.rowp : 0)) * sizeof(double) + 64;
+        const size_t smem = hadi_team_smem(L, have_div);
         if (L.B == 8) hipLaunchKernelGGL((hadi_team_kernel<8>), dim3(c->cu_count), dim3(512), smem, s, a, ta);
         else hipLaunchKernelGGL((hadi_team_kernel<4>), dim3(c->cu_count), dim3(512), smem, s, a, ta);
         HIP_TRY(c, hipGetLastError());
@@ -1178,7 +830,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     return HADI_OK;
 }
 
-int finish_timing(Ctx *c, const SweepDesc &d, const HadiPlan &pl) {
+int finish_timing(Ctx *c, const SweepDesc &d) {
     hipStream_t s = c->stream;
     HIP_TRY(c, hipEventRecord(c->ev[3], s));
     HIP_TRY(c, hipStreamSynchronize(s));
@@ -1203,7 +855,6 @@ int finish_timing(Ctx *c, const SweepDesc &d, const HadiPlan &pl) {
         t.pass_a_launches = (long long)d.Nmax * c->last_nsub;
         t.pass_b_launches = (long long)d.Nmax * c->last_nsub;
     }
-    (void)pl;
     if (deverr)
         return fail(c, HADI_ERR_INTERNAL, "device-side failure 0x%x during the sweep%s: the results of this call are invalid", deverr,
                     (deverr & HADI_DEVERR_RENDEZVOUS) ? " (a pair rendezvous of a two-wavefront row ran out of polls)" : "");
@@ -1411,7 +1062,7 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
         HIP_TRY(c, hipMemcpyAsync(hstatus.data(), c->status.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(c, hipGetLastError());
-    if ((rc = finish_timing(c, d, pl))) return rc;
+    if ((rc = finish_timing(c, d))) return rc;
     for (int k = 0; k < (int)hstatus.size(); k++)
         if (hstatus[k]) return fail(c, HADI_ERR_NOT_ON_GRID, "S_0 = %.17g is not a node of instance %d's s-grid", S_0, k);
     return HADI_OK;
@@ -1468,7 +1119,7 @@ int greeks_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double 
     if (ladder && (rc = from_device(c, p->memspace, ladder, ptr<double>(c->natOut), nlad))) return rc;
     std::vector<int> hstatus(n);
     HIP_TRY(c, hipMemcpyAsync(hstatus.data(), c->status.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = finish_timing(c, d, pl))) return rc;
+    if ((rc = finish_timing(c, d))) return rc;
     for (int k = 0; k < n; k++) {
         if (hstatus[k] == 1) return fail(c, HADI_ERR_NOT_ON_GRID, "S_0 = %.17g is not a node of instance %d's s-grid", S_0, k);
         if (hstatus[k]) return fail(c, HADI_ERR_NOT_ON_GRID, "V_0 = %.17g is not a node of instance %d's v-grid", V_0, k);
@@ -1576,7 +1227,7 @@ int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, doubl
     if (!hs) { hs_fallback.resize(n); hs = hs_fallback.data(); }
     HIP_TRY(c, hipMemcpyAsync(hs, c->status.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipGetLastError());
-    if ((rc = finish_timing(c, d, pl))) return rc;
+    if ((rc = finish_timing(c, d))) return rc;
     for (int k = 0; k < n0; k++)
         if (hs[k]) return fail(c, HADI_ERR_NOT_ON_GRID, "S_0 = %.17g is not a node of instance %d's s-grid", S_0, k);
     return HADI_OK;
@@ -1675,7 +1326,7 @@ int hadi_create(hadi_ctx **out, int device_id) {
     ok = ok && hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->join_ev, hipEventDisableTiming) == hipSuccess;
-    ok = ok && raise_all_lds_limits() == hipSuccess;
+    hadi_for_each_kernel([&](auto kernel) { ok = ok && raise_lds_limit(kernel) == hipSuccess; });
     for (auto &e : c->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->wait_ev, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipHostMalloc(reinterpret_cast<void **>(&c->err_host), 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;

@@ -2,12 +2,12 @@
 // under the host-thread wave emulator so tests can compare its logic with the oracle without a GPU.
 // Never shipped, never linked into libhadi; see wave_emu.h.
 #define HADI_EMU 1
-#include "hadi_kernels.h"
-#include "hadi_plan.h"
+#include "hadi_dispatch.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -45,183 +45,46 @@ extern "C" int emu_set_tuning(const char *key, int value) {
     return 0;
 }
 
-template <int B, int G, int NG, int PD>
-static void run_pass_a(const HadiPlan &pl, const HadiSweepArgs &a, int n, int mode) {
-    const unsigned nt = 64 * pl.W * G * NG;
-    if (mode == 1) emu::launch(pl.grid_a, nt, [&]() { hadi_pass_a<B, G, 4, NG, PD, false, 1>(a, n); }, pl.smem_a);
-    else if (mode == 2) emu::launch(pl.grid_a, nt, [&]() { hadi_pass_a<B, G, 4, NG, PD, false, 2>(a, n); }, pl.smem_a);
-    else if (a.american) emu::launch(pl.grid_a, nt, [&]() { hadi_pass_a<B, G, 4, NG, PD, true>(a, n); }, pl.smem_a);
-    else emu::launch(pl.grid_a, nt, [&]() { hadi_pass_a<B, G, 4, NG, PD, false>(a, n); }, pl.smem_a);
-}
-
-// Modified Craig-Sneyd / Hundsdorfer-Verwer predictor (mode 1) and corrector (mode 2): same choice as launch_row_pass_sch
-template <int B, int G, int NG, int PD, int SCH>
-static void run_pass_a_sch(const HadiPlan &pl, const HadiSweepArgs &a, int n, int mode) {
-    const unsigned nt = 64 * pl.W * G * NG;
-    if (mode == 1) emu::launch(pl.grid_a, nt, [&]() { hadi_pass_a_sch<B, G, 4, NG, PD, 1, SCH>(a, n); }, pl.smem_a);
-    else emu::launch(pl.grid_a, nt, [&]() { hadi_pass_a_sch<B, G, 4, NG, PD, 2, SCH>(a, n); }, pl.smem_a);
-}
-template <int B, int G, int SCH>
-static void run_strip_sch(const HadiPlan &pl, const HadiSweepArgs &a, int n, int mode) {
-    const unsigned nt = 64 * HADI_STRIP_WAVES(B);
-    if (mode == 1) emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip_sch<B, G, 1, SCH>(a, n); }, pl.smem_as);
-    else emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip_sch<B, G, 2, SCH>(a, n); }, pl.smem_as);
-}
-template <int SCH>
-static int run_row_pass_sch(const HadiPlan &pl, const HadiSweepArgs &a, int n, int mode) {
-    // (paired strips: the corrector only -- the predictor of those shapes runs on the shared ring)
-    if (pl.use_strip && !pl.use_pairs && (g_cs_strips == 1 || g_cs_strips == 1 + mode) && !(pl.L.G == 2 && mode == 1)) {
-        if (pl.L.G == 2) emu::launch(pl.grid_as, 64 * HADI_STRIP_WAVES(8), [&]() { hadi_pass_a_strip_sch<8, 2, 2, SCH>(a, n); }, pl.smem_as);
-        else if (pl.L.B == 8) run_strip_sch<8, 1, SCH>(pl, a, n, mode);
-        else if (pl.L.B == 4) run_strip_sch<4, 1, SCH>(pl, a, n, mode);
-        else run_strip_sch<2, 1, SCH>(pl, a, n, mode);
-        return 0;
-    }
-    switch (pl.L.B * 10 + pl.L.G) {
-        case 11: run_pass_a_sch<1, 1, 1, 2, SCH>(pl, a, n, mode); break;
-        case 21: run_pass_a_sch<2, 1, 1, 2, SCH>(pl, a, n, mode); break;
-        case 41: run_pass_a_sch<4, 1, 1, 2, SCH>(pl, a, n, mode); break;
-        case 81: run_pass_a_sch<8, 1, 1, 1, SCH>(pl, a, n, mode); break;
-        case 82: run_pass_a_sch<8, 2, 1, 1, SCH>(pl, a, n, mode); break;
-        default: return 2;
-    }
+// The library's own dispatch (csrc/hadi_dispatch.h): select as hadi_api.hip does, then run the kernel on the emulator.
+// Returns 2 where the table holds no kernel for the pass.
+static int run_pass(const HadiSel &sel, const HadiSweepArgs &a, int n) {
+    if (!sel.k) return 2;
+    emu::launch(sel.grid, sel.block, [&]() { sel.k->fn(a, n); }, sel.smem);
     return 0;
 }
 
-// sch: 0 Douglas / Craig-Sneyd, HADI_SCH_MCS, HADI_SCH_HV (modes 1 / 2 only)
-static int run_row_pass(const HadiPlan &pl, const HadiSweepArgs &a, int n, int mode, int sch = 0) {
-    if (mode != 0 && sch == HADI_SCH_MCS) return run_row_pass_sch<HADI_SCH_MCS>(pl, a, n, mode);
-    if (mode != 0 && sch == HADI_SCH_HV) return run_row_pass_sch<HADI_SCH_HV>(pl, a, n, mode);
-    if (pl.row_seq) {  // same choice as hadi_api.hip
-        if (mode) return 2;
-        const unsigned g = a.n_inst * ((pl.L.nrows + 63) / 64);
-        if (a.american) emu::launch(g, 64, [&]() { hadi_pass_a_seq<1>(a, n); });
-        else emu::launch(g, 64, [&]() { hadi_pass_a_seq<0>(a, n); });
-        return 0;
+// The selection alone, for tests/test_kernel_selection.py.  in[16]: m1, m2, instances, target_waves, "strip", "pair_strips",
+// no_strips (the caller's theta = 0 or r_d = r_f: run_sweep clears use_strip), american, amp, xstep, f32, scheme (enum
+// hadi_scheme), "cs_strips", "col_prefetch", mode, what (0 the row pass, 1 the column pass, 2 entry in[0] of the table of
+// instantiations whatever the other inputs).  o[11]: table index, family, B, G, amer, mode, sch, f32, grid, block, LDS
+// bytes; name: the kernel as the description spells it (what = 2: as the source spells it); desc: the description of the
+// sub-batch.  Returns 0, 1 (no plan), 2 (no kernel); what = 2: the number of table entries.
+extern "C" int emu_select(const int *in, long long *o, char *name, char *desc, int cap) {
+    int count;
+    const HadiKernel *tab = hadi_kernel_table(&count);
+    auto put = [&](const HadiKernel *k) {
+        const long long v[8] = {k - tab, k->family, k->B, k->G, k->amer, k->mode, k->sch, k->f32};
+        std::copy(v, v + 8, o);
+    };
+    if (in[15] == 2) {
+        if (in[0] < 0 || in[0] >= count) return count;
+        put(tab + in[0]);
+        std::snprintf(name, cap, "%s", tab[in[0]].id);
+        return count;
     }
-    if (pl.use_pairs && pl.use_strip && mode == 0) {  // two strips per wavefront (4 nodes per lane)
-        if (a.american) emu::launch(pl.grid_as, 64 * HADI_PAIR_WAVES, [&]() { hadi_pass_a_pairs<1>(a, n); }, pl.smem_pairs_eu);
-        else emu::launch(pl.grid_as, 64 * HADI_PAIR_WAVES, [&]() { hadi_pass_a_pairs<0>(a, n); }, pl.smem_pairs_eu);
-        return 0;
-    }
-    if (pl.use_strip && mode != 0 && !pl.use_pairs && (g_cs_strips == 1 || g_cs_strips == 1 + mode)) {  // Craig-Sneyd on strips: same choice as hadi_api.hip
-        const unsigned nt = 64 * HADI_STRIP_WAVES(pl.L.B);
-        if (pl.L.G == 2) {
-            if (mode == 1) emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip<8, 0, double, 2, 1>(a, n); }, pl.smem_as);
-            else emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip<8, 0, double, 2, 2>(a, n); }, pl.smem_as);
-            return 0;
-        }
-        switch (pl.L.B * 4 + mode) {
-            case 33: emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip<8, 0, double, 1, 1>(a, n); }, pl.smem_as); break;
-            case 34: emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip<8, 0, double, 1, 2>(a, n); }, pl.smem_as); break;
-            case 17: emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip<4, 0, double, 1, 1>(a, n); }, pl.smem_as); break;
-            case 18: emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip<4, 0, double, 1, 2>(a, n); }, pl.smem_as); break;
-            case 9: emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip<2, 0, double, 1, 1>(a, n); }, pl.smem_as); break;
-            default: emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip<2, 0, double, 1, 2>(a, n); }, pl.smem_as); break;
-        }
-        return 0;
-    }
-    if (pl.use_strip && mode == 0 && pl.L.G == 2) {  // paired strips
-        if (a.american) emu::launch(pl.grid_as, 512, [&]() { hadi_pass_a_strip<8, 1, double, 2>(a, n); }, pl.smem_as);
-        else emu::launch(pl.grid_as, 512, [&]() { hadi_pass_a_strip<8, false, double, 2>(a, n); }, pl.smem_as);
-        return 0;
-    }
-    if (pl.use_strip && mode == 0 && pl.L.G == 1) {  // same choice as hadi_api.hip
-        switch (pl.L.B * 2 + (a.american ? 1 : 0)) {
-            case 16: emu::launch(pl.grid_as, 512, [&]() { hadi_pass_a_strip<8, false>(a, n); }, pl.smem_as); break;
-            case 17: emu::launch(pl.grid_as, 512, [&]() { hadi_pass_a_strip<8, true>(a, n); }, pl.smem_as); break;
-            case 8: emu::launch(pl.grid_as, 64 * HADI_STRIP_WAVES(4), [&]() { hadi_pass_a_strip<4, false>(a, n); }, pl.smem_as); break;
-            case 9: emu::launch(pl.grid_as, 64 * HADI_STRIP_WAVES(4), [&]() { hadi_pass_a_strip<4, true>(a, n); }, pl.smem_as); break;
-            case 4: emu::launch(pl.grid_as, 64 * HADI_STRIP_WAVES(2), [&]() { hadi_pass_a_strip<2, false>(a, n); }, pl.smem_as); break;
-            default: emu::launch(pl.grid_as, 64 * HADI_STRIP_WAVES(2), [&]() { hadi_pass_a_strip<2, true>(a, n); }, pl.smem_as); break;
-        }
-        return 0;
-    }
-    switch (pl.L.B * 10 + pl.L.G) {
-        case 11: run_pass_a<1, 1, 1, 2>(pl, a, n, mode); break;
-        case 21: run_pass_a<2, 1, 1, 2>(pl, a, n, mode); break;
-        case 41: run_pass_a<4, 1, 1, 2>(pl, a, n, mode); break;
-        case 81: run_pass_a<8, 1, 1, 1>(pl, a, n, mode); break;
-        case 82: run_pass_a<8, 2, 1, 1>(pl, a, n, mode); break;
-        default: return 2;
-    }
+    HadiTuning tu;
+    tu.strip = in[4]; tu.pair_strips = in[5];
+    HadiPlan pl;
+    if (hadi_make_plan(in[0], in[1], in[2], in[3], &pl, tu, in[10] ? 4 : 8)) return 1;
+    if (in[6]) pl.use_strip = 0;
+    const HadiPassCtx pc{pl, in[2], in[7] != 0, in[8] != 0, in[9] != 0, in[10] != 0, in[11], in[12], in[13]};
+    const HadiSel sel = in[15] ? hadi_select_col_pass(pc) : hadi_select_row_pass(pc, in[14]);
+    if (!sel.k) return 2;
+    put(sel.k);
+    o[8] = sel.grid; o[9] = sel.block; o[10] = (long long)sel.smem;
+    hadi_kernel_name(*sel.k, pl, name, cap);
+    hadi_describe_passes(pc, desc, cap);
     return 0;
-}
-
-// fp32-state sweep (scheme == 2 in emu_solve): same choices as hadi_api.hip
-template <int B, int G, int NG, int PD>
-static void run_pass_a_f32(const HadiPlan &pl, const HadiSweepArgs &a, int n) {
-    const size_t ring_elems = (size_t)NG * ((PD + 1) * pl.W + 4) * pl.L.rowp;
-    emu::launch(pl.grid_a, 64 * pl.W * G * NG, [&]() { hadi_pass_a<B, G, 4, NG, PD, false, 0, float>(a, n); },
-                pl.smem_a - ring_elems * (sizeof(double) - sizeof(float)));
-}
-static int run_sweep_f32(const HadiPlan &pl, const HadiSweepArgs &a, int n) {
-    if (pl.use_strip && pl.L.B == 8 && pl.L.G == 2) {
-        emu::launch(pl.grid_as, 512, [&]() { hadi_pass_a_strip<8, false, float, 2>(a, n); }, pl.smem_as);
-    } else if (pl.use_strip && pl.L.B == 8) {
-        emu::launch(pl.grid_as, 512, [&]() { hadi_pass_a_strip<8, false, float>(a, n); },
-                    (size_t)8 * 4 * pl.L.rowp * sizeof(float) + (size_t)4 * 64 * pl.L.B * sizeof(double));
-    } else switch (pl.L.B * 10 + pl.L.G) {
-        case 11: run_pass_a_f32<1, 1, 1, 2>(pl, a, n); break;
-        case 21: run_pass_a_f32<2, 1, 1, 2>(pl, a, n); break;
-        case 41: run_pass_a_f32<4, 1, 1, 2>(pl, a, n); break;
-        case 81: run_pass_a_f32<8, 1, 1, 1>(pl, a, n); break;
-        case 82: run_pass_a_f32<8, 2, 1, 1>(pl, a, n); break;
-        default: return 2;
-    }
-    if (pl.L.P <= 8) emu::launch(pl.grid_b, pl.block_b, [&]() { hadi_pass_b<8, false, float>(a, n); }, pl.smem_b);
-    else if (g_col_prefetch) emu::launch(pl.grid_b, pl.block_b, [&]() { hadi_pass_b2<16, float, HADI_B2_NPF(4)>(a, n); }, pl.smem_b2);
-    else emu::launch(pl.grid_b, pl.block_b, [&]() { hadi_pass_b1<16, false, float>(a, n); }, pl.smem_b);
-    return 0;
-}
-
-// American, P representation (scheme == 3 in emu_solve): same kernels as hadi_api.hip picks
-template <int B, int G, int NG, int PD>
-static void run_pass_a_amp(const HadiPlan &pl, const HadiSweepArgs &a, int n) {
-    emu::launch(pl.grid_a, 64 * pl.W * G * NG, [&]() { hadi_pass_a<B, G, 4, NG, PD, 2>(a, n); },
-                pl.smem_a + (size_t)pl.L.rowp * sizeof(double));
-}
-static int run_sweep_amp(const HadiPlan &pl, const HadiSweepArgs &a, int n) {
-    if (pl.use_pairs && pl.use_strip) {
-        emu::launch(pl.grid_as, 64 * HADI_PAIR_WAVES, [&]() { hadi_pass_a_pairs<2>(a, n); }, pl.smem_pairs_amp);
-    } else if (pl.use_strip && pl.L.G == 2) {  // paired strips
-        emu::launch(pl.grid_as, 512, [&]() { hadi_pass_a_strip<8, 2, double, 2>(a, n); }, pl.smem_as + (size_t)pl.L.rowp * sizeof(double));
-    } else if (pl.use_strip && pl.L.G == 1) {  // same choice as hadi_api.hip
-        const unsigned nt = 64 * HADI_STRIP_WAVES(pl.L.B);
-        const size_t sm = pl.smem_as + (size_t)pl.L.rowp * sizeof(double);
-        switch (pl.L.B) {
-            case 8: emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip<8, 2>(a, n); }, sm); break;
-            case 4: emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip<4, 2>(a, n); }, sm); break;
-            default: emu::launch(pl.grid_as, nt, [&]() { hadi_pass_a_strip<2, 2>(a, n); }, sm); break;
-        }
-    } else switch (pl.L.B * 10 + pl.L.G) {
-        case 11: run_pass_a_amp<1, 1, 1, 2>(pl, a, n); break;
-        case 21: run_pass_a_amp<2, 1, 1, 2>(pl, a, n); break;
-        case 41: run_pass_a_amp<4, 1, 1, 2>(pl, a, n); break;
-        case 81: run_pass_a_amp<8, 1, 1, 1>(pl, a, n); break;
-        case 82: run_pass_a_amp<8, 2, 1, 1>(pl, a, n); break;
-        default: return 2;
-    }
-    if (pl.L.P <= 8) emu::launch(pl.grid_b, pl.block_b, [&]() { hadi_pass_b<8, 2>(a, n); }, pl.smem_b);
-    else emu::launch(pl.grid_b, pl.block_b, [&]() { hadi_pass_b1<16, 2>(a, n); }, pl.smem_b);
-    return 0;
-}
-
-static void run_col_pass(const HadiPlan &pl, const HadiSweepArgs &a, int n) {
-    if (pl.col_seq) {  // same choice as hadi_api.hip
-        const unsigned g = a.n_inst * pl.ctiles;
-        if (a.american) emu::launch(g, 64, [&]() { hadi_pass_b_seq<1>(a, n); });
-        else emu::launch(g, 64, [&]() { hadi_pass_b_seq<0>(a, n); });
-        return;
-    }
-    if (pl.L.P <= 8) {  // same choice as hadi_api.hip
-        if (a.american) emu::launch(pl.grid_b, pl.block_b, [&]() { hadi_pass_b<8, true>(a, n); }, pl.smem_b);
-        else emu::launch(pl.grid_b, pl.block_b, [&]() { hadi_pass_b<8, false>(a, n); }, pl.smem_b);
-    } else {
-        if (a.american) emu::launch(pl.grid_b, pl.block_b, [&]() { hadi_pass_b1<16, true>(a, n); }, pl.smem_b);
-        else if (g_col_prefetch) emu::launch(pl.grid_b, pl.block_b, [&]() { hadi_pass_b2<16, double, HADI_B2_NPF(8)>(a, n); }, pl.smem_b2);
-        else emu::launch(pl.grid_b, pl.block_b, [&]() { hadi_pass_b1<16, false>(a, n); }, pl.smem_b);
-    }
 }
 
 extern "C" int emu_plan(int m1, int m2, int n_inst, int target_waves, int *out /*B,rowp,P,R,ntiles,ctiles*/) {
@@ -321,13 +184,13 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
     const HadiLayout &L = pl.L;
     const int american = variant & 1, dividend = (variant >> 1) & 1;
     const size_t st = (size_t)L.inst_stride * n_inst;
-    const int sch = scheme == 4 ? HADI_SCH_MCS : scheme == 5 ? HADI_SCH_HV : 0;
-    const bool cs = scheme == 1 || sch, f32 = scheme == 2, amp = scheme == 3;
+    const int hscheme = scheme == 1 ? 1 : scheme == 4 ? 2 : scheme == 5 ? 3 : 0;  // enum hadi_scheme
+    const bool cs = hscheme != 0, f32 = scheme == 2, amp = scheme == 3;
     if (scheme < 0 || scheme > 5) return 3;
     if (amp && !american) return 3;
     if (f32 && (american || dividend)) return 3;
     if (cs && (american || dividend || put_strikes)) return 3;  // (the library's predictor-corrector schemes: European calls)
-    if (sch && !(theta > 0.0)) return 3;
+    if (hscheme >= 2 && !(theta > 0.0)) return 3;
     if ((N_i || dt_i) && (!N_i || !dt_i || dividend)) return 3;  // (per-instance step grids: no per-instance dividend tables here)
     int Nmax = N;
     if (N_i) {
@@ -389,59 +252,32 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
         const int nb = g_team_blocks;
         ta.form = team.data(); ta.bar = team.data() + 64; ta.nb = nb; ta.N = Nmax; ta.stamps = nullptr;
         ta.div_flag = dividend ? flags.data() : nullptr; ta.flag_stride = 0; ta.div_amounts = damounts; ta.div_pcts = dpcts; ta.vec_s = vec_s;
-        const size_t smem = ((size_t)4 * 64 * L.B + hadi_pb_mf_doubles(L.P) + (size_t)L.P * HADI_LC * HADI_PBW +
-                             (dividend ? (size_t)(L.m1 + 2) + (size_t)8 * L.rowp : 0)) * sizeof(double) + 64;
+        const size_t smem = hadi_team_smem(L, dividend != 0);
         if (L.B == 8) emu::launch(8 * nb, 512, [&]() { hadi_team_kernel<8>(a, ta); }, smem, nb > 1);
         else emu::launch(8 * nb, 512, [&]() { hadi_team_kernel<4>(a, ta); }, smem, nb > 1);
         emu::launch(8, 64, [&]() { hadi_unpack_kernel(L, n_inst, dU.data(), U); });
         return g_err ? 4 : 0;
     }
-    const size_t smem_small = american ? pl.smem_small_am : pl.smem_small_eu;
-    if (use_small && !cs && !f32 && smem_small > 0) {
+    if (use_small && !cs && !f32 && (american ? pl.smem_small_am : pl.smem_small_eu) > 0) {
         HadiSmallArgs sm;
         sm.div_flag = dividend ? flags.data() : nullptr; sm.flag_stride = 0; sm.div_amounts = damounts; sm.div_pcts = dpcts;
         sm.vec_s = vec_s; sm.Nmax = Nmax; sm.order = nullptr;
-        if (use_small == 5 && !american && pl.L.nrows <= 32) {  // ... two instances per wavefront
-            const size_t smem_seq = (size_t)hadi_small_seq_layout(pl.L.m1, pl.L.nrows).total * sizeof(double);
-            if (pl.L.B == 1) emu::launch((n_inst + 1) / 2, 64, [&]() { hadi_small_seq2_kernel<1>(a, sm); }, 2 * smem_seq);
-            else emu::launch((n_inst + 1) / 2, 64, [&]() { hadi_small_seq2_kernel<2>(a, sm); }, 2 * smem_seq);
-        } else if (use_small == 3 && !american) {  // one wavefront per instance, sequential line solves (European / dividends)
-            const size_t smem_seq = (size_t)hadi_small_seq_layout(pl.L.m1, pl.L.nrows).total * sizeof(double);
-            if (pl.L.B == 1) emu::launch(n_inst, 64, [&]() { hadi_small_seq_kernel<1>(a, sm); }, smem_seq);
-            else emu::launch(n_inst, 64, [&]() { hadi_small_seq_kernel<2>(a, sm); }, smem_seq);
-        } else if (use_small == 2) {  // 8 wavefronts per instance (what hadi_api.hip picks for small batches)
-            if (L.B == 1) {
-                if (american) emu::launch(n_inst, 512, [&]() { hadi_small_kernel<1, 8, true>(a, sm); }, smem_small);
-                else emu::launch(n_inst, 512, [&]() { hadi_small_kernel<1, 8, false>(a, sm); }, smem_small);
-            } else {
-                if (american) emu::launch(n_inst, 512, [&]() { hadi_small_kernel<2, 8, true>(a, sm); }, smem_small);
-                else emu::launch(n_inst, 512, [&]() { hadi_small_kernel<2, 8, false>(a, sm); }, smem_small);
-            }
-        } else if (L.B == 1) {
-            if (american) emu::launch(n_inst, 256, [&]() { hadi_small_kernel<1, 4, true>(a, sm); }, smem_small);
-            else emu::launch(n_inst, 256, [&]() { hadi_small_kernel<1, 4, false>(a, sm); }, smem_small);
-        } else {
-            if (american) emu::launch(n_inst, 256, [&]() { hadi_small_kernel<2, 4, true>(a, sm); }, smem_small);
-            else emu::launch(n_inst, 256, [&]() { hadi_small_kernel<2, 4, false>(a, sm); }, smem_small);
-        }
+        // use_small 5: two instances per wavefront; 3: one wavefront per instance, sequential line solves (both European /
+        // dividends); 2: 8 wavefronts per instance (what hadi_api.hip picks for small batches); else 4
+        const int kind = (use_small == 5 && !american && pl.L.nrows <= 32) ? 2 : (use_small == 3 && !american) ? 1 : 0;
+        const HadiSel sel = hadi_select_small(pl, n_inst, kind, use_small == 2 ? 8 : 4, american != 0);
+        if (!sel.k) return 2;
+        emu::launch(sel.grid, sel.block, [&]() { sel.k->loop(a, sm); }, sel.smem);
         emu::launch(8, 64, [&]() { hadi_unpack_kernel(L, n_inst, dU.data(), U); });
         if (american && lam_out) emu::launch(8, 64, [&]() { hadi_unpack_kernel(L, n_inst, dLAM.data(), lam_out); });
         return 0;
     }
-    if (pair_tab)  // (before any sweep of the streaming path, as hadi_api.hip does at the start of a sub-batch's time loop)
-        emu::launch(pl.grid_as, 512, [&]() { hadi_pass_a_strip<8, 0, double, 2, 3>(a, 1); },
-                    (size_t)4 * HADI_STRIP_NS(8, 2, 8) * pl.L.rowp * sizeof(double) + ((size_t)4 * 64 * 8 * 2 + (size_t)4 * 16) * sizeof(double));
+    if (pair_tab && run_pass(hadi_select_pair_table(pl), a, 1)) return 2;  // (before any sweep of the streaming path, as hadi_api.hip does at the start of a sub-batch's time loop)
+    std::vector<float> fU(f32 ? st : 0), fY(f32 ? st : 0, 0.0f);
     if (f32) {  // round the packed state to float, sweep on float arrays, widen again
-        std::vector<float> fU(st), fY(st, 0.0f);
         emu::launch(8, 64, [&]() { hadi_narrow_kernel(L, dU.data(), fU.data(), st); });
-        HadiSweepArgs af = a;
-        af.U = reinterpret_cast<double *>(fU.data());
-        af.Y = reinterpret_cast<double *>(fY.data());
-        for (int n = 1; n <= Nmax; n++)
-            if (run_sweep_f32(pl, af, n)) return 2;
-        emu::launch(8, 64, [&]() { hadi_widen_kernel(L, fU.data(), dU.data(), st); });
-        emu::launch(8, 64, [&]() { hadi_unpack_kernel(L, n_inst, dU.data(), U); });
-        return 0;
+        a.U = reinterpret_cast<double *>(fU.data());
+        a.Y = reinterpret_cast<double *>(fY.data());
     }
     // per-instance step grids: an instance that has taken its last step gets NaN in its slices of the arrays the row passes write
     // (Y, R1, C2); a later row pass that still worked on it would overwrite them, a later column pass would carry the NaN into U
@@ -456,22 +292,20 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
         const bool xstep = amp && (n == 1 || (dividend && flags[n - 1] >= 0));  // explicit (U, lambda_bar) step, as in hadi_api.hip
         if (xstep && n > 1)
             emu::launch(8, 64, [&]() { hadi_am_materialise_kernel(L, n_inst, ipar.data(), dU0.data(), dU.data(), dLAM.data(), pl.pos_m1); });
-        if (amp && !xstep) {
-            if (run_sweep_amp(pl, a, n)) return 2;
-            poison_finished(n);
-            continue;
-        }
         if (dividend && flags[n - 1] >= 0) {  // device_solver.hpp:426-517 (host builds the step table, kernel applies)
             dUT = dU;
             emu::launch(8, 64, [&]() {
                 hadi_dividend_kernel(L, n_inst, ipar.data(), vec_s, dUT.data(), dU.data(), flags.data(), 0, n, damounts, dpcts);
             });
         }
-        if (run_row_pass(pl, a, n, cs ? 1 : 0, sch)) return 2;
-        run_col_pass(pl, cs ? av : a, n);
-        if (cs) {
-            run_row_pass(pl, av, n, 2, sch);
-            run_col_pass(pl, a, n);
+        const HadiPassCtx pc{pl, n_inst, american != 0, amp, xstep, f32, hscheme, g_cs_strips, g_col_prefetch};
+        const HadiSel col = hadi_select_col_pass(pc);
+        if (col.k && col.k->family == HADI_F_COL_SEQ && (f32 || amp)) return 2;
+        for (int mode = cs ? 1 : 0; mode <= (cs ? 2 : 0); mode++) {  // (predictor: V = Y2 out of U; corrector: U out of V)
+            const HadiSel row = hadi_select_row_pass(pc, mode);
+            // (the library never launches the sequential passes but for Douglas sweeps with the fp64 state: run_sweep refuses)
+            if (row.k && row.k->family == HADI_F_ROW_SEQ && (mode || f32 || amp)) return 2;
+            if (run_pass(row, mode == 2 ? av : a, n) || run_pass(col, mode == 1 ? av : a, n)) return 2;
         }
         if (xstep)
             emu::launch(8, 64, [&]() { hadi_am_dematerialise_kernel(L, n_inst, ipar.data(), dU0.data(), dU.data(), dLAM.data()); });
@@ -485,6 +319,7 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
     }
     if (amp)
         emu::launch(8, 64, [&]() { hadi_am_materialise_kernel(L, n_inst, ipar.data(), dU0.data(), dU.data(), dLAM.data(), pl.pos_m1); });
+    if (f32) emu::launch(8, 64, [&]() { hadi_widen_kernel(L, fU.data(), dU.data(), st); });
     emu::launch(8, 64, [&]() { hadi_unpack_kernel(L, n_inst, dU.data(), U); });
     if (american && lam_out) emu::launch(8, 64, [&]() { hadi_unpack_kernel(L, n_inst, dLAM.data(), lam_out); });
     return 0;

@@ -59,7 +59,7 @@ extern "C" int emu_solve_resident(int n_inst, int m1, int m2, int N, double dt, 
     a.ipar = ipar.data(); a.L = L; a.n_inst = n_inst; a.R = pl.R; a.ntiles = pl.ntiles; a.ctiles = pl.ctiles; a.btpw = pl.btpw;
     a.bgroups = pl.bgroups; a.tile_il = g_tile_il; a.american = 0; a.pos_m1 = pl.pos_m1; a.RS = pl.RS; a.sblocks = pl.sblocks;
     a.err = &g_err; a.debug = 0;
-    emu::launch(pl.grid_as, 64 * HADI_STRIP_WAVES(8), [&]() { hadi_sweep_resident<8>(a, Nmax); }, std::max(pl.smem_as, pl.smem_b));
+    if (run_pass(hadi_select_resident(pl), a, Nmax)) return 3;
     emu::launch(8, 64, [&]() { hadi_unpack_kernel(L, n_inst, dU.data(), U); });
     return g_err ? 4 : 0;
 }
