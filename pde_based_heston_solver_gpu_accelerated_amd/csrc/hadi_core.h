@@ -202,6 +202,12 @@ struct HadiTables {
 #define HADI_STRIP_NS_NARROW 4
 #endif
 #define HADI_STRIP_NS(B, G, ES) ((G) == 2 ? ((ES) == 8 ? 3 : 4) : ((B) <= 4 ? HADI_STRIP_NS_NARROW : 4))
+// Resident sweep (hadi_k_resident.h): the column phase's RT (4 P x MP doubles) lies behind the strip kernel's 8 rings and 4
+// s-coefficient arrays, in LDS no ring aliases.  Offset in doubles, and the launch's dynamic LDS bytes.
+HADI_HD inline size_t hadi_resident_rt_offset(const HadiLayout &L) { return (size_t)8 * HADI_STRIP_NS(8, 1, 8) * L.rowp + (size_t)4 * 64 * 8; }
+HADI_HD inline size_t hadi_resident_smem(const HadiLayout &L) {
+    return (hadi_resident_rt_offset(L) + (size_t)4 * L.P * hadi_pb_mp(L.P)) * sizeof(double);
+}
 enum { RC_V = 0, RC_WM = 1, RC_WZ = 2, RC_WP = 3, RC_L2 = 4, RC_L1 = 5, RC_M = 6, RC_U1 = 7, RC_U2 = 8,
        RC_B1VAL = 9, RC_B1COL = 10, RC_VTH = 11 /* theta dt v */, RC_LAST = 12,
        // the A0 v-weights divided by -theta dt (r_d - r_f): the strip kernels keep -theta dt (r_d - r_f) s beta_s in place of

@@ -211,9 +211,14 @@ static inline HadiSel hadi_select_pair_table(const HadiPlan &pl) {
     return hadi_sel(HADI_F_STRIP, 8, 2, 0, 3, 0, 0, pl.grid_as, 512,
                     (size_t)4 * HADI_STRIP_NS(8, 2, 8) * pl.L.rowp * sizeof(double) + ((size_t)4 * 64 * 8 * 2 + (size_t)4 * 16) * sizeof(double));
 }
-// Resident sweep: one block per instance (LDS: the strip rings; the column phase aliases them).
+// Resident sweep: one block per instance (LDS: the strip rings and coefficient arrays, RT behind them; the column phase's
+// exchange values and product alias the rings).
 static inline HadiSel hadi_select_resident(const HadiPlan &pl) {
-    return hadi_sel(HADI_F_RESIDENT, 8, 1, 0, 0, 0, 0, pl.grid_as, 64 * HADI_STRIP_WAVES(8), pl.smem_as > pl.smem_b ? pl.smem_as : pl.smem_b);
+    size_t smem = hadi_resident_smem(pl.L);  // (above the column pass's own smem_b: that layout fits the first three rings)
+#if defined(HADI_STAMPS) && HADI_STAMPS == 5
+    smem = 163840;  // (diagnostic build: the stamps' sums live in the last KiB)
+#endif
+    return hadi_sel(HADI_F_RESIDENT, 8, 1, 0, 0, 0, 0, pl.grid_as, 64 * HADI_STRIP_WAVES(8), smem);
 }
 // Instance-resident launch (hadi_team_kernel<8 | 4>): dynamic LDS bytes.
 static inline size_t hadi_team_smem(const HadiLayout &L, bool have_div) {

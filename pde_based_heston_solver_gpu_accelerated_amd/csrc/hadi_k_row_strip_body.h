@@ -156,8 +156,19 @@
     // LDS stores follow below (two dependent memory round trips of the prologue become one)
     constexpr int NCOPY = (4 * 64 * B * G) / (64 * NWV);
     static_assert(NCOPY * 64 * NWV == 4 * 64 * B * G, "coefficient arrays: whole rounds of the block");
+    // Resident sweep (HADI_BODY_RESTAGE, set by hadi_resident_row_phase alone): the arrays do not depend on the step and nothing
+    // aliases them between two row phases of a launch, so only the block's first step loads, scales and stores them.
+#if defined(HADI_BODY_RESTAGE)
+    const bool restage = (HADI_BODY_RESTAGE);  // (block-uniform)
+#else
+    constexpr bool restage = true;
+#endif
     double sc_tmp[NCOPY];
-    {
+#if defined(HADI_BODY_RESTAGE)
+#pragma unroll
+    for (int q = 0; q < NCOPY; q++) sc_tmp[q] = 0.0;
+#endif
+    if (restage) {
         const double *__restrict__ sc = a.scoef + (size_t)inst * 4 * 64 * B * G;
 #pragma unroll
         for (int q = 0; q < NCOPY; q++) sc_tmp[q] = sc[threadIdx.x + q * 64 * NWV];
@@ -176,7 +187,7 @@
     c.e_nm1 = hadi_uniform_d(exp(ip.bc_rate * ip.dt * (n - 1)));  // device_solver.hpp:238
     c.e_n = hadi_uniform_d(exp(ip.bc_rate * ip.dt * n));          // device_solver.hpp:246
     if constexpr (AMER == 2) c.inv_dt = hadi_uniform_d(1.0 / ip.dt);
-    {   // s-coefficient arrays to LDS; the two beta arrays scaled by -theta dt (r_d - r_f) on the way (hadi_strip_step)
+    if (restage) {  // s-coefficient arrays to LDS; the two beta arrays scaled by -theta dt (r_d - r_f) on the way (hadi_strip_step)
         const double mq = -(ip.thdt * ip.q);
 #pragma unroll
         for (int q = 0; q < NCOPY; q++) {
@@ -203,6 +214,9 @@
 #endif
     }
     __syncthreads();  // ... and nobody's first fetch of the loop lands in a slot its partner is still reading
+#if defined(HADI_BODY_RESTAGE)
+    HADI_RES_STAMP(0);  // row prologue
+#endif
     if (!has_strip) return;
     // 8 nodes per lane, European fp64 (the headline kernel): two of the four arrays fit the registers left over (224 -> 250
     // VGPRs, no spill): 8 of the 16 coefficient reads per row step less on the LDS pipe, +0.7 % on 512x256 x256 (three
