@@ -74,7 +74,8 @@ enum hadi_memspace { HADI_MEM_HOST = 0, HADI_MEM_DEVICE = 1 };
  * for every theta (Douglas is first order with the mixed-derivative term); the usual choices are theta = 1/3 for MCS and
  * theta = 1/2 + sqrt(3)/6 for HV.  MCS at theta = 1/2 is Craig-Sneyd.  All three predictor-corrector schemes: European
  * variant, call boundary data, fp64 state, m1 <= 1024 and m2 <= 527 (HADI_ERR_UNSUPPORTED otherwise); MCS and HV also
- * need theta > 0. */
+ * need theta > 0.  Grids that fit in LDS (m1 <= 128, m2 <= 32) run the whole time loop of such a sweep in one launch, one
+ * wavefront per instance (hadi_small_sch_kernel; tuning key "small_sch" says when). */
 enum hadi_scheme { HADI_SCHEME_DOUGLAS = 0, HADI_SCHEME_CRAIG_SNEYD = 1, HADI_SCHEME_MCS = 2, HADI_SCHEME_HV = 3 };
 /* Precision of the state arrays BETWEEN the two directional passes.  FP64 is what the reference computes in.  FP32
  * ("mixed-precision fp32 ADI sweep with fp64 tridiag pivots", BASELINE.json config 5): U and the A2 right-hand side are
@@ -202,6 +203,15 @@ int hadi_get_timing(const hadi_ctx *ctx, hadi_timing *out);
  *   "small_seq"   ... European / dividend sweeps of such grids on the one-wavefront-per-instance kernel that solves the
  *                 lines sequentially, one per lane: -1 automatic (default: batches of more instances than CUs), 0 never
  *                 (the block-per-instance kernel, which the American sweeps always use), 1 always
+ *   "small_sch"   Craig-Sneyd / MCS / HV sweeps of grids with m1 <= 128 and m2 <= 32 on the LDS-resident kernel that runs the
+ *                 whole time loop in one launch, one wavefront per instance (hadi_small_sch_kernel; needs "small_grid", no
+ *                 profiling): -1 automatic (default), 0 never (the streaming kernels), 1 wherever the grid is admitted.
+ *                 Automatic: batches of more instances than CUs, on grids of which a CU's 160 KiB of LDS hold at least three
+ *                 instances (four fields of (m2 + 1) x ((m1 + 3) | 1) doubles each plus ~4 KB of tables: 50x25 yes, 64x32 and
+ *                 100x30 no), unless the caller pinned the streaming geometry ("strip", "row_tile", "col_groups",
+ *                 "strip_blocks", or "cs_strips" = 0).  Measured on 50x25, 257 ... 3000 instances: 2.0 - 2.6x the streaming
+ *                 kernels; on 100x30 x500 (one instance per CU) 0.79x, which is why such grids stay streaming
+ *                 (profiles/r08_small_sch_ab.txt)
  *   "graph"       hipGraph replay of the time loop for small batches (default 1).  The handle caches up to 8 captured loops,
  *                 keyed by everything their nodes bake in: the launch geometry of every sub-batch, the scheme, variant and
  *                 precision, the steps that carry a dividend, and every device address the loop uses (the library's buffers --

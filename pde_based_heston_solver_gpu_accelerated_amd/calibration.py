@@ -51,10 +51,15 @@ class _WS:  # minimal DO_Workspace: the launchers read the initial condition fro
     pass
 
 
-def _launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, grids, U_0, dividends, points):
-    """Two closures (params -> (J, base)), (params -> trial prices) over the launcher pair of the variant."""
+def _launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, grids, U_0, dividends, points, scheme=0):
+    """Two closures (params -> (J, base)), (params -> trial prices) over the launcher pair of the variant.  `scheme` (0 Douglas,
+    1 Craig-Sneyd, 2 Modified Craig-Sneyd, 3 Hundsdorfer-Verwer) goes to every call of the European pairs; 0 calls the
+    launchers without it, as before the schemes existed."""
     n_loc = grids.Vec_s.shape[0]
     total_size = (m1 + 1) * (m2 + 1)
+    if scheme and variant != EU:
+        raise ValueError("scheme %r: the predictor-corrector schemes price European options only (variant %r)" % (scheme, variant))
+    sch = {"scheme": scheme} if scheme else {}
     if variant in (DIV, AM_DIV) and dividends is None:
         raise ValueError("this variant needs a dividend schedule")
 
@@ -67,11 +72,11 @@ def _launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, grids, U_0, 
         if variant == EU:
             def jac(k, e, s, r, v, eps):
                 return solver.compute_jacobian_multi_maturity(S_0, v, r_d, r_f, r, s, k, e, m1, m2, total_size, theta,
-                                                              points, n_loc, grids, U_0, eps=eps)
+                                                              points, n_loc, grids, U_0, eps=eps, **sch)
 
             def base(k, e, s, r, v):
                 return solver.compute_base_prices_multi_maturity(S_0, v, r_d, r_f, r, s, k, e, m1, m2, total_size,
-                                                                 theta, points, n_loc, grids, workspace())
+                                                                 theta, points, n_loc, grids, workspace(), **sch)
         elif variant == AM_DIV:
             def jac(k, e, s, r, v, eps):
                 return solver.compute_jacobian_multi_maturity_american_dividends(
@@ -89,8 +94,8 @@ def _launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, grids, U_0, 
     delta_t = T / N
     head = lambda k, e, s, r, v: (S_0, v, T, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t, n_loc, grids)
     if variant == EU:
-        jac = lambda k, e, s, r, v, eps: solver.compute_jacobian(*head(k, e, s, r, v), U_0, eps=eps)
-        base = lambda k, e, s, r, v: solver.compute_base_prices(*head(k, e, s, r, v), workspace())
+        jac = lambda k, e, s, r, v, eps: solver.compute_jacobian(*head(k, e, s, r, v), U_0, eps=eps, **sch)
+        base = lambda k, e, s, r, v: solver.compute_base_prices(*head(k, e, s, r, v), workspace(), **sch)
     elif variant == AM:
         jac = lambda k, e, s, r, v, eps: solver.compute_jacobian_american(*head(k, e, s, r, v), U_0, eps=eps)
         base = lambda k, e, s, r, v: solver.compute_base_prices_american(*head(k, e, s, r, v), U_0, workspace())
@@ -109,9 +114,12 @@ def _launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, grids, U_0, 
 
 def calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0,
               market_prices, dividends=None, calibration_points=None, max_iter=20, tol=0.1, delta_tol=None, eps=1e-6,
-              lam=0.01, comm=None, lm_partials=_solver.lm_partials, lm_solve=_solver.lm_solve):
+              lam=0.01, comm=None, lm_partials=_solver.lm_partials, lm_solve=_solver.lm_solve, scheme=0):
     """The LM loop shared by all drivers (heston_calibration.cpp:204-417).  `grids`, `U_0`, `market_prices` (and
     `calibration_points` for the multi-maturity drivers, which then ignore T and N) are this rank's shard.
+    `scheme`: the time stepper of every Jacobian and trial-price solve of the loop (0 Douglas, 1 Craig-Sneyd, 2 Modified
+    Craig-Sneyd, 3 Hundsdorfer-Verwer), European variant only (ValueError otherwise, before any solve); `theta` is the scheme's:
+    the usual pairs are 1/3 for MCS and 1/2 + sqrt(3)/6 for HV, which are second order in time where Douglas is first.
     Stops when ||delta||_2 < delta_tol (default: tol) or sum r^2 < tol.  Returns a dict with the calibrated
     parameters, final error, iteration count, PDE-solve count, the last computed model prices and the trajectory."""
     comm = comm or Communicator()
@@ -119,7 +127,7 @@ def calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1
     delta_tol = tol if delta_tol is None else delta_tol
     market = np.asarray(market_prices, dtype=np.float64)
     jac, base_fn = _launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, grids, U_0, dividends,
-                              calibration_points)
+                              calibration_points, scheme=scheme)
     cur = (kappa, eta, sigma, rho, V_0)
     final_error, iteration_count, converged = 100.0, 0, False
     history = []
@@ -185,9 +193,10 @@ def calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1
 
 
 def calibrate_european(solver, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0,
-                       market_prices, max_iter=15, tol=0.1, **kw):
+                       market_prices, max_iter=15, tol=0.1, scheme=0, **kw):
+    """scheme / theta: see calibrate (e.g. scheme=2, theta=1/3: Modified Craig-Sneyd)."""
     return calibrate(solver, EU, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0,
-                     market_prices, max_iter=max_iter, tol=tol, **kw)
+                     market_prices, max_iter=max_iter, tol=tol, scheme=scheme, **kw)
 
 
 def calibrate_american(solver, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0,
@@ -215,12 +224,13 @@ def multi_maturity_tolerances(n_points):
 
 def calibrate_european_multi_maturity(solver, S_0, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, theta,
                                       calibration_points, grids, U_0, market_prices, max_iter=15, tol=None,
-                                      delta_tol=None, n_total=None, **kw):
-    """`n_total` = global number of calibration points (defaults to this rank's, i.e. single rank)."""
+                                      delta_tol=None, n_total=None, scheme=0, **kw):
+    """`n_total` = global number of calibration points (defaults to this rank's, i.e. single rank).  scheme / theta: see
+    calibrate."""
     t, dtol = multi_maturity_tolerances(n_total or len(calibration_points))
     return calibrate(solver, EU, S_0, None, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, None, theta, grids, U_0,
                      market_prices, calibration_points=calibration_points, max_iter=max_iter,
-                     tol=t if tol is None else tol, delta_tol=dtol if delta_tol is None else delta_tol, **kw)
+                     tol=t if tol is None else tol, delta_tol=dtol if delta_tol is None else delta_tol, scheme=scheme, **kw)
 
 
 def calibrate_american_dividends_multi_maturity(solver, S_0, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, theta,

@@ -56,6 +56,7 @@ struct Ctx {
     int use_amp = 1;    // American sweeps without the lambda_bar array when the payoff depends on s only
     int device_vgrid = 1;  // compute_base_prices / compute_jacobian: v-grids rebuilt per instance on the device
     int sub_batch = 1;     // large batches run sub-batch by sub-batch (run_sweep)
+    int small_sch = -1;    // predictor-corrector schemes on the one-wavefront-per-instance LDS kernel (hadi_small_sch_kernel): -1 by batch size, 0 never, 1 wherever admitted
     int small_pairs = -1;  // small-grid sequential kernel with two instances per wavefront: -1 by batch size, 0 never, 1 always
     // Two measured alternatives of the column pass, both opt-in (round 4; neither moves the 16-chunk pass by more than +-2 %:
     // profiles/r04_colpass_ab.txt): the blocks of an instance take their full column tiles interleaved (hadi_pb_tiles), and
@@ -406,7 +407,21 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     const bool cs = d.scheme != HADI_SCHEME_DOUGLAS;  // a predictor-corrector scheme (CS, MCS, HV): R1 / C2 carry-over, V = Y2
     const bool f32 = d.prec == HADI_STATE_FP32;  // European Douglas (with or without dividends) only (validated)
     if (f32 && ((rc = ensure(c, c->Uf, st / 2)) || (rc = ensure(c, c->Yf, st / 2)))) return rc;
-    if (cs && ((rc = ensure(c, c->V, st)) || (rc = ensure(c, c->R1, st)) || (rc = ensure(c, c->C2, st)))) return rc;
+    // (a caller who pins the streaming kernels' geometry -- hadi_set_tuning "strip", "row_tile", "col_groups", "strip_blocks" --
+    // gets those kernels: no whole-loop kernel is chosen automatically)
+    const bool pinned = c->tune.strip >= 0 || c->tune.row_tile > 0 || c->tune.col_groups > 0 || c->tune.strip_blocks > 0;
+    // Predictor-corrector sweeps of grids that fit in LDS (m1 <= 128, m2 <= 32): the whole time loop in one launch, one
+    // wavefront per instance (hadi_small_sch_kernel).  "small_sch" = 1: wherever admitted; 0: never; -1 (default): batches of
+    // more instances than CUs (the rule of "small_seq") on grids of which a CU's LDS holds at least three instances, unless the
+    // caller pinned the streaming geometry or "cs_strips" = 0.  Measured (profiles/r08_small_sch_ab.txt, MCS / HV, ms per step,
+    // streaming -> this kernel): 50x25 (three per CU) x257 0.040 -> 0.020, x500 0.057 -> 0.021, x1024 0.082 -> 0.041, x3000
+    // 0.210 -> 0.100; 100x30 (one per CU: one wavefront on each CU) x500 0.064 -> 0.081, so such grids stay streaming.
+    const size_t smem_sch = hadi_small_sch_smem(L);
+    const bool small_sch = cs && c->use_small && !c->profiling && !d.debug && !c->debug_fault && !f32 && d.variant == HADI_EU &&
+                           !seq_shape && hadi_small_sch_admits(L) &&
+                           (c->small_sch > 0 || (c->small_sch < 0 && d.n > c->cu_count && 3 * smem_sch <= (size_t)160 * 1024 &&
+                                                 !pinned && c->cs_strips != 0));
+    if (cs && !small_sch && ((rc = ensure(c, c->V, st)) || (rc = ensure(c, c->R1, st)) || (rc = ensure(c, c->C2, st)))) return rc;
     if (pl.row_seq && (rc = ensure(c, c->R1, st))) return rc;  // (hadi_pass_a_seq parks the Thomas multipliers there)
     const bool pair_tab = L.G == 2 && !cs && !pl.row_seq;  // paired strips (Douglas steps) take the pairs' coupling column from a table built once per solve
     if (pair_tab && (rc = ensure(c, c->rs_tab, (size_t)d.n * L.nrows * 128 * 8))) return rc;
@@ -505,12 +520,12 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     a.tile_il = c->tile_il;
     a.RS = pl.RS; a.sblocks = pl.sblocks;
     a.err = c->err_dev; a.debug = c->debug_fault;
-    a.R1 = (cs || pl.row_seq) ? ptr<double>(c->R1) : nullptr;
-    a.C2 = cs ? ptr<double>(c->C2) : nullptr;
+    a.R1 = ((cs && !small_sch) || pl.row_seq) ? ptr<double>(c->R1) : nullptr;  // (hadi_small_sch_kernel keeps V, R1, C2 in LDS)
+    a.C2 = (cs && !small_sch) ? ptr<double>(c->C2) : nullptr;
     a.rs_tab = pair_tab ? ptr<double>(c->rs_tab) : nullptr;
     // Craig-Sneyd: the predictor's column pass writes V (= Y2), the corrector's row pass reads V
     HadiSweepArgs av = a;
-    if (cs) av.U = ptr<double>(c->V);
+    if (cs && !small_sch) av.U = ptr<double>(c->V);
 
     const bool prof = c->profiling != 0 && !d.debug;
     if (prof) {
@@ -549,9 +564,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     // less than HADI_TWO_STREAM_IDLE of them idle -- a block that waited for a second round would wait for a whole time loop.
     // Other sub-batches of the same call (a small remainder) stay on the streaming kernels.  "resident_sweep" = -1 (default):
     // wherever eligible unless the caller pinned the streaming geometry; 1: wherever eligible; 0: never.
-    // (a caller who pins the streaming kernels' geometry -- hadi_set_tuning "strip", "row_tile", "col_groups", "strip_blocks" --
-    // gets those kernels: neither the resident sweep nor, below, the team launch is chosen automatically)
-    const bool pinned = c->tune.strip >= 0 || c->tune.row_tile > 0 || c->tune.col_groups > 0 || c->tune.strip_blocks > 0;
+    // (`pinned`, above: neither the resident sweep nor, below, the team launch is chosen automatically)
     const bool resident_shape = (c->resident_sweep > 0 || (c->resident_sweep < 0 && !pinned)) && d.scheme == HADI_SCHEME_DOUGLAS &&
                                 d.variant == HADI_EU && !f32 && L.B == 8 && L.G == 1 && L.P <= 8 && !seq_shape && d.theta > 0.0 &&
                                 d.r_d != d.r_f && !d.debug && !c->debug_fault && !prof;  // (test hooks: the streaming kernels they are for)
@@ -660,6 +673,43 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     // 6.68 -> 6.98).  "small_pairs" = 1 forces it, 0 forbids it, -1 (default) picks by batch size.  Needs nrows <= 32.
     const bool seq2 = seq && L.nrows <= 32 && 2 * smem_seq <= (size_t)160 * 1024 &&
                       (c->small_pairs > 0 || (c->small_pairs < 0 && d.n > 2 * c->cu_count && 2 * d.n <= 9 * c->cu_count));
+    // The whole-loop kernels' second argument block: dividend tables and, for batches of mixed maturities, the dispatch order.
+    auto small_args = [&](HadiSmallArgs &sm) -> int {
+        sm.div_flag = nullptr; sm.div_amounts = nullptr; sm.div_pcts = nullptr; sm.vec_s = d.d_vec_s; sm.Nmax = d.Nmax;
+        sm.order = nullptr;
+        if (!d.uniform_steps) {  // longest-processing-time-first dispatch order
+            std::vector<int> order(d.n);
+            for (int k = 0; k < d.n; k++) order[k] = k;
+            std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+                return d.par8[(size_t)x * 8 + 5] > d.par8[(size_t)y * 8 + 5];
+            });
+            if ((rc = ensure(c, c->order, sizeof(int) * n))) return rc;
+            if ((rc = stage_to_device(c, c->order.p, order.data(), sizeof(int) * n))) return rc;
+            sm.order = ptr<int>(c->order);
+        }
+        sm.flag_stride = flag_stride;
+        if (have_div) {
+            sm.div_flag = ptr<int>(c->div_flag); sm.div_amounts = ptr<double>(c->div_amt); sm.div_pcts = ptr<double>(c->div_pct);
+        }
+        return HADI_OK;
+    };
+    if (small_sch) {
+        const int sch = d.scheme == HADI_SCHEME_MCS ? HADI_SCH_MCS : d.scheme == HADI_SCHEME_HV ? HADI_SCH_HV : HADI_SCH_CS;
+        const HadiLoopFn fn = hadi_small_sch_fn(L.B, sch);
+        if (!fn) return fail(c, HADI_ERR_INTERNAL, "no small-grid kernel of scheme %d for grid %dx%d", d.scheme, d.m1, d.m2);
+        const size_t smem = smem_sch;
+        char buf[256];
+        std::snprintf(buf, sizeof buf, "hadi_small_sch_kernel<%d,%s>: whole time loop in one launch, one wavefront per instance, predictor and corrector lines solved sequentially in LDS (%zu B)",
+                      L.B, sch == HADI_SCH_MCS ? "MCS" : sch == HADI_SCH_HV ? "HV" : "CS", smem);
+        c->last_path = buf;
+        HadiSmallArgs sm;
+        if ((rc = small_args(sm))) return rc;
+        HIP_TRY(c, hipEventRecord(c->ev[1], s));
+        hipLaunchKernelGGL(fn, dim3(d.n), dim3(64), smem, s, a, sm);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->ev[2], s));
+        return HADI_OK;
+    }
     if (takes_small_path) {
         // wavefronts per instance: 4 when the batch fills the GPU (throughput), 8 for small batches (latency of the
         // dependent per-step phases; more waves share the rows of the row pass)
@@ -679,22 +729,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
             c->last_path = buf;
         }
         HadiSmallArgs sm;
-        sm.div_flag = nullptr; sm.div_amounts = nullptr; sm.div_pcts = nullptr; sm.vec_s = d.d_vec_s; sm.Nmax = d.Nmax;
-        sm.order = nullptr;
-        if (!d.uniform_steps) {  // longest-processing-time-first dispatch order
-            std::vector<int> order(d.n);
-            for (int k = 0; k < d.n; k++) order[k] = k;
-            std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
-                return d.par8[(size_t)x * 8 + 5] > d.par8[(size_t)y * 8 + 5];
-            });
-            if ((rc = ensure(c, c->order, sizeof(int) * n))) return rc;
-            if ((rc = stage_to_device(c, c->order.p, order.data(), sizeof(int) * n))) return rc;
-            sm.order = ptr<int>(c->order);
-        }
-        sm.flag_stride = flag_stride;
-        if (have_div) {
-            sm.div_flag = ptr<int>(c->div_flag); sm.div_amounts = ptr<double>(c->div_amt); sm.div_pcts = ptr<double>(c->div_pct);
-        }
+        if ((rc = small_args(sm))) return rc;
         HIP_TRY(c, hipEventRecord(c->ev[1], s));
         hipLaunchKernelGGL((sel.k->loop), dim3(sel.grid), dim3(sel.block), sel.smem, s, a, sm);
         HIP_TRY(c, hipGetLastError());
@@ -1370,6 +1405,7 @@ int hadi_set_tuning(hadi_ctx *ctx, const char *key, int value) {
     if (!std::strcmp(key, "graph")) c->use_graph = value ? 1 : 0;
     else if (!std::strcmp(key, "small_grid")) c->use_small = value ? 1 : 0;
     else if (!std::strcmp(key, "small_seq")) c->small_seq = value < 0 ? -1 : (value ? 1 : 0);
+    else if (!std::strcmp(key, "small_sch")) c->small_sch = value < 0 ? -1 : (value ? 1 : 0);
     else if (!std::strcmp(key, "american_p")) c->use_amp = value ? 1 : 0;
     else if (!std::strcmp(key, "device_vgrid")) c->device_vgrid = value ? 1 : 0;
     else if (!std::strcmp(key, "sub_batch")) c->sub_batch = value ? 1 : 0;
@@ -1412,6 +1448,7 @@ int hadi_get_tuning(const hadi_ctx *ctx, const char *key, int *value) {
     if (!std::strcmp(key, "graph")) *value = c->use_graph;
     else if (!std::strcmp(key, "small_grid")) *value = c->use_small;
     else if (!std::strcmp(key, "small_seq")) *value = c->small_seq;
+    else if (!std::strcmp(key, "small_sch")) *value = c->small_sch;
     else if (!std::strcmp(key, "american_p")) *value = c->use_amp;
     else if (!std::strcmp(key, "device_vgrid")) *value = c->device_vgrid;
     else if (!std::strcmp(key, "sub_batch")) *value = c->sub_batch;

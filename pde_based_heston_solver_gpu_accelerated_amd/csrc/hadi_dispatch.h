@@ -106,8 +106,26 @@ static inline const HadiKernel *hadi_kernel_table(int *count) {
 #undef HADI_K_STRIP_SCH
 #undef HADI_K_STRIP
 
-// Calls f with the address of every kernel of the table and of the two instance-resident team kernels (their own argument
-// block).  hadi_create raises the dynamic-LDS limit of each: no kernel that needs more than the default can be left out.
+// The LDS-resident whole-loop kernels of the predictor-corrector schemes (hadi_k_small_sch.h), launched from run_sweep
+// outside the table as the team and Greeks kernels are.  B: 1 or 2 nodes per lane of the packed layout; sch: HADI_SCH_*.
+// Null where no such instantiation exists: an error for the caller, never a fallback.
+static inline HadiLoopFn hadi_small_sch_fn(int B, int sch) {
+    if (B == 1) return sch == HADI_SCH_CS ? hadi_small_sch_kernel<1, HADI_SCH_CS> : sch == HADI_SCH_MCS ? hadi_small_sch_kernel<1, HADI_SCH_MCS> :
+                       sch == HADI_SCH_HV ? hadi_small_sch_kernel<1, HADI_SCH_HV> : (HadiLoopFn) nullptr;
+    if (B == 2) return sch == HADI_SCH_CS ? hadi_small_sch_kernel<2, HADI_SCH_CS> : sch == HADI_SCH_MCS ? hadi_small_sch_kernel<2, HADI_SCH_MCS> :
+                       sch == HADI_SCH_HV ? hadi_small_sch_kernel<2, HADI_SCH_HV> : (HadiLoopFn) nullptr;
+    return nullptr;
+}
+// Its admission (the grid alone: what run_sweep adds is the call's) and its dynamic LDS bytes: m1 <= 128, m2 <= 32 and the
+// kernel's own layout within the CU's 160 KiB.
+static inline size_t hadi_small_sch_smem(const HadiLayout &L) { return (size_t)hadi_small_sch_layout(L.m1, L.nrows).total * sizeof(double); }
+static inline bool hadi_small_sch_admits(const HadiLayout &L) {
+    return L.G == 1 && L.B <= 2 && L.P == 1 && hadi_small_sch_smem(L) <= (size_t)160 * 1024;
+}
+
+// Calls f with the address of every kernel of the table, of the two instance-resident team kernels (their own argument
+// block) and of the predictor-corrector schemes' LDS-resident kernels (hadi_small_sch_fn).  hadi_create raises the
+// dynamic-LDS limit of each: no kernel that needs more than the default can be left out.
 template <class F>
 static void hadi_for_each_kernel(F f) {
     int n;
@@ -118,6 +136,8 @@ static void hadi_for_each_kernel(F f) {
     }
     f(hadi_team_kernel<8>);
     f(hadi_team_kernel<4>);
+    for (int B = 1; B <= 2; B++)
+        for (int sch = HADI_SCH_CS; sch <= HADI_SCH_HV; sch++) f(hadi_small_sch_fn(B, sch));
 }
 
 // A selected kernel and its launch geometry.  k is null when the table holds no such instantiation: an error, never a fallback.

@@ -106,7 +106,7 @@ class HestonADI:
         self._lib.hadi_set_profiling(self._h, 1 if enabled else 0)
 
     def set_tuning(self, key, value):
-        """Execution-path switch (hadi.h: 'small_grid', 'small_seq', 'graph', 'american_p', 'strip', 'row_tile', 'col_groups',
+        """Execution-path switch (hadi.h: 'small_grid', 'small_seq', 'small_sch', 'graph', 'american_p', 'strip', 'row_tile', 'col_groups',
         'small_waves', 'device_vgrid'); results agree to round-off."""
         rc = self._lib.hadi_set_tuning(self._h, key.encode(), int(value))
         if rc != nat.HADI_OK:
@@ -342,7 +342,7 @@ class HestonADI:
     # ---- compute_base_prices* (src/jacobian_computation.cpp:368, 629, 922, 1232) ---------------
     def _base_prices(self, variant, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N,
                      theta, delta_t, num_strikes, deviceGrids, workspace, U_0=None, dividends=None,
-                     per_instance=None):
+                     per_instance=None, scheme=0):
         option_type, strikes = self._option(per_instance)
         if total_size != (m1 + 1) * (m2 + 1):
             raise ValueError("total_size != (m1+1)*(m2+1)")
@@ -350,7 +350,8 @@ class HestonADI:
             raise ValueError("num_strikes does not match the grid batch")
         p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
                           U=workspace.U, U_0=U_0, lambda_bar=None, dividends=dividends,
-                          per_instance=per_instance, need_vgrid=False, option_type=option_type, strikes=strikes)
+                          per_instance=per_instance, need_vgrid=False, scheme=scheme, option_type=option_type,
+                          strikes=strikes)
         out, optr = self._out(num_strikes, 1, workspace.U)
         rc = self._lib.hadi_compute_base_prices(self._h, C.byref(p), float(S_0), float(V_0), optr)
         if rc != nat.HADI_OK:
@@ -358,9 +359,11 @@ class HestonADI:
         return out
 
     def compute_base_prices(self, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta,
-                            delta_t, num_strikes, deviceGrids, workspace, per_instance=None):
+                            delta_t, num_strikes, deviceGrids, workspace, per_instance=None, scheme=0):
+        """scheme: the time stepper of every solve (0 Douglas, 1 Craig-Sneyd, 2 Modified Craig-Sneyd, 3 Hundsdorfer-Verwer; see
+        DO_timestepping).  The European launchers take it; the library refuses the schemes for the other variants."""
         return self._base_prices(EU, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta,
-                                 delta_t, num_strikes, deviceGrids, workspace, per_instance=per_instance)
+                                 delta_t, num_strikes, deviceGrids, workspace, per_instance=per_instance, scheme=scheme)
 
     def compute_base_prices_american(self, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N,
                                      theta, delta_t, num_strikes, deviceGrids, U_0, workspace, per_instance=None):
@@ -383,13 +386,13 @@ class HestonADI:
 
     # ---- compute_jacobian* (src/jacobian_computation.cpp:204, 457, 726, 1031) ------------------
     def _jacobian(self, variant, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta,
-                  delta_t, num_strikes, deviceGrids, U_0, eps, dividends=None, per_instance=None):
+                  delta_t, num_strikes, deviceGrids, U_0, eps, dividends=None, per_instance=None, scheme=0):
         if total_size != (m1 + 1) * (m2 + 1):
             raise ValueError("total_size != (m1+1)*(m2+1)")
         option_type, strikes = self._option(per_instance)
         p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
                           U=None, U_0=U_0, dividends=dividends, per_instance=per_instance, need_vgrid=False,
-                          option_type=option_type, strikes=strikes)
+                          scheme=scheme, option_type=option_type, strikes=strikes)
         J, jptr = self._out(num_strikes, 5, U_0)
         base, bptr = self._out(num_strikes, 1, U_0)
         rc = self._lib.hadi_compute_jacobian(self._h, C.byref(p), float(S_0), float(V_0), float(eps), jptr, bptr)
@@ -398,10 +401,10 @@ class HestonADI:
         return J, base
 
     def compute_jacobian(self, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta,
-                         delta_t, num_strikes, deviceGrids, U_0, eps=1e-6, per_instance=None):
-        """Returns (J [n][5] with columns kappa, eta, sigma, rho, v0; base_prices [n])."""
+                         delta_t, num_strikes, deviceGrids, U_0, eps=1e-6, per_instance=None, scheme=0):
+        """Returns (J [n][5] with columns kappa, eta, sigma, rho, v0; base_prices [n]).  scheme: as compute_base_prices."""
         return self._jacobian(EU, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta,
-                              delta_t, num_strikes, deviceGrids, U_0, eps, per_instance=per_instance)
+                              delta_t, num_strikes, deviceGrids, U_0, eps, per_instance=per_instance, scheme=scheme)
 
     def compute_jacobian_american(self, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N,
                                   theta, delta_t, num_strikes, deviceGrids, U_0, eps=1e-6, per_instance=None):
@@ -434,16 +437,16 @@ class HestonADI:
         return {"N_i": N_i, "delta_t_i": dt_i}, int(N_i.max()) if len(N_i) else 1, float(dt_i[0]) if len(dt_i) else 1.0
 
     def compute_jacobian_multi_maturity(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, theta,
-                                        calibration_points, total_calibration_size, deviceGrids, U_0, eps=1e-6):
+                                        calibration_points, total_calibration_size, deviceGrids, U_0, eps=1e-6, scheme=0):
         per, N, dt = self._steps(calibration_points, total_calibration_size)
         return self._jacobian(EU, S_0, V_0, None, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, dt,
-                              total_calibration_size, deviceGrids, U_0, eps, per_instance=per)
+                              total_calibration_size, deviceGrids, U_0, eps, per_instance=per, scheme=scheme)
 
     def compute_base_prices_multi_maturity(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, theta,
-                                           calibration_points, total_calibration_size, deviceGrids, workspace):
+                                           calibration_points, total_calibration_size, deviceGrids, workspace, scheme=0):
         per, N, dt = self._steps(calibration_points, total_calibration_size)
         return self._base_prices(EU, S_0, V_0, None, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta,
-                                 dt, total_calibration_size, deviceGrids, workspace, per_instance=per)
+                                 dt, total_calibration_size, deviceGrids, workspace, per_instance=per, scheme=scheme)
 
     def compute_jacobian_multi_maturity_american_dividends(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2,
                                                            total_size, theta, calibration_points,
