@@ -77,6 +77,44 @@ def well_conditioned_strikes(m1, n):
     return out
 
 
+# ---- batches whose instances carry DIFFERENT v-grids ("mixed v-grids") ------------------------------
+# Two fixed, ordered candidate lists of (V, V_0, d) for Grid(m1, 8K, S_0, K, K/5, m2, V, V_0, d).
+# Free V_0: ten V_0 (the fields and the V_0_i launchers); the field batches also walk the (V, d) pairs below, so that the
+# first few instances of a batch already differ in all three.  MIXED_V0S alone (V = 5, d = 0.01) is what V_0_i cycles through.
+MIXED_V0S = (0.04, 0.09, 0.0225, 0.0123, 0.25, 0.16, 0.0625, 0.36, 0.01, 0.49)
+# Common V_0: the calls that take ONE scalar V_0 (Greeks, parallel_DO_solve) need it as a node of every grid -- build_v inserts
+# it -- so only (V, d) moves, and with them the row of V_0.
+MIXED_VD = ((5.0, 0.01), (4.0, 0.02), (3.0, 0.015), (6.0, 0.01), (5.0, 0.05), (4.0, 0.008), (8.0, 0.02), (2.5, 0.01))
+MIXED_MIN = 4  # distinct candidates that must obey the 30x rule at every m2 a test uses (a condition, asserted)
+
+
+def mixed_vgrid_candidates(m2, same_v0=None, vary_vd=True):
+    """The (V, V_0, d) of the list that obey the 30x rule on m2 intervals, in list order; at least MIXED_MIN of them, asserted.
+    same_v0: the common-V_0 list; None: the free-V_0 list (vary_vd=False: V = 5, d = 0.01 throughout, the grids of V_0_i)."""
+    if same_v0 is not None:
+        cand = [(V, same_v0, d) for V, d in MIXED_VD]
+    else:
+        cand = [MIXED_VD[j % len(MIXED_VD)][:1] + (v0,) + MIXED_VD[j % len(MIXED_VD)][1:] if vary_vd else (5.0, v0, 0.01)
+                for j, v0 in enumerate(MIXED_V0S)]
+    ok = [c for c in cand if interval_ratios(O.rebuild_variance(m2, c[1], V=c[0], d=c[2])[1])[0] <= COND_MAX]
+    assert len(ok) >= MIXED_MIN, "only %d of %d v-grid candidates obey the 30x rule at m2 = %d" % (len(ok), len(cand), m2)
+    return ok
+
+
+def mixed_vgrid_batch(m1, m2, n, same_v0=None):
+    """(strikes, grids, v0s): n well-conditioned strikes, instance k on the v-grid of candidate k % len of
+    mixed_vgrid_candidates(m2, same_v0) -- so neighbours in the batch never share a v-grid -- and V_0 of each instance.
+    The 30x rule is asserted on the finished batch."""
+    import pde_based_heston_solver_gpu_accelerated_amd as H
+    cand = mixed_vgrid_candidates(m2, same_v0)
+    strikes = well_conditioned_strikes(m1, n)
+    pick = [cand[k % len(cand)] for k in range(n)]
+    grids = H.GridViewsBatch([H.Grid(m1, 8 * K, S_0, K, K / 5, m2, V, v0, d) for K, (V, v0, d) in zip(strikes, pick)])
+    assert_well_conditioned(grids.Delta_s, grids.Delta_v)
+    assert n < 2 or len({g.tobytes() for g in grids.Vec_v}) >= min(n, MIXED_MIN)
+    return strikes, grids, [c[1] for c in pick]
+
+
 def v0_for(m2):
     """V_0 of a well-conditioned v-grid with m2 intervals: the canonical 0.04 unless its grid breaks the 30x rule."""
     return V_0_ALT if m2 in (3, 33, 56, 66, 99, 132) else V_0
