@@ -157,7 +157,8 @@ inline int hadi_make_plan(int m1, int m2, int n_inst, int target_waves, HadiPlan
     }
     // Paired strips (512 < m1 <= 1024, hadi_pass_a_strip<8, EU, T, 2>): 4 pairs of wavefronts per block, one strip per pair.
     // Same round model as above; a paired row step costs more than a single-wavefront one (second right-hand side in the
-    // cyclic reduction, the pair rendezvous).  The caller keeps American and Craig-Sneyd sweeps on the shared ring.
+    // cyclic reduction, the pair rendezvous).  American sweeps (explicit pair and P representation) and the correctors of the
+    // predictor-corrector schemes run on them too (hadi_dispatch.h; tests/test_gpu_regimes.py asserts the names).
     if (L.B == 8 && L.G == 2) {
         const int spb = HADI_STRIP_WAVES(L.B) / 2, ns = state_bytes == 8 ? 3 : 4;
         const int cus = target_waves / 8 > 0 ? target_waves / 8 : 1;

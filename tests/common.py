@@ -115,6 +115,14 @@ def mixed_vgrid_batch(m1, m2, n, same_v0=None):
     return strikes, grids, [c[1] for c in pick]
 
 
+def spot_scaled_grids(grids, k):
+    """A copy of a GridViewsBatch with the spot axis (Vec_s, Delta_s) times 2^k -- exact in fp64; everything else shared."""
+    import copy
+    g = copy.copy(grids)
+    g.Vec_s, g.Delta_s = grids.Vec_s * 2.0 ** k, grids.Delta_s * 2.0 ** k
+    return g
+
+
 def v0_for(m2):
     """V_0 of a well-conditioned v-grid with m2 intervals: the canonical 0.04 unless its grid breaks the 30x rule."""
     return V_0_ALT if m2 in (3, 33, 56, 66, 99, 132) else V_0

@@ -245,6 +245,7 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
     if (use_small == 4) {  // instance-resident launch (hadi_team_kernel) with teams of ONE block: the emulator runs the blocks of a
                            // grid one after the other, so the team barrier is trivially met; indexing and arithmetic are real
         if (american || cs || f32 || n_inst > 8 || L.G != 1 || (L.B != 8 && L.B != 4) || L.P > 8) return 3;
+        if (!(theta > 0.0) || r_d == r_f) return 3;  // as hadi_api.hip (team_shape): the team kernel's row step is the strips'
         std::vector<int> team(512, 0);
         HadiTeamArgs ta;
         // "team_blocks" > 1: teams of several blocks, all blocks of the grid running at once (the team barrier, the formation
