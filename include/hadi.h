@@ -24,6 +24,8 @@
  *                                      (src/jacobian_computation.cpp:20-195)
  *   hadi_compute_greeks             <- no counterpart: delta, gamma, variance sensitivities, theta and the spot ladder of the
  *                                      v-row of V_0, from the state the sweep leaves on the device
+ *   hadi_maturity_ladder, hadi_compute_{base_prices,jacobian}_ladder <- no counterpart: the price node after chosen steps of ONE sweep
+ *                                      (a whole maturity ladder per strike on a shared delta_t)
  *   hadi_make_grid / hadi_rebuild_variance <- Grid::Grid (src/grid.cpp:16-61),
  *                                      GridViews::rebuild_variance_views (src/grid_pod.hpp:25-73)
  *
@@ -214,7 +216,7 @@ int hadi_get_timing(const hadi_ctx *ctx, hadi_timing *out);
  *                 (profiles/r08_small_sch_ab.txt)
  *   "graph"       hipGraph replay of the time loop for small batches (default 1).  The handle caches up to 8 captured loops,
  *                 keyed by everything their nodes bake in: the launch geometry of every sub-batch, the scheme, variant and
- *                 precision, the steps that carry a dividend, and every device address the loop uses (the library's buffers --
+ *                 precision, the steps that carry a dividend, the snapshot steps of a ladder call, and every device address the loop uses (the library's buffers --
  *                 rs_tab and the fp64 packed U of an fp32-state sweep among them -- and the caller's s-grid).  Whenever a call
  *                 frees a buffer to grow it, the whole cache is dropped first, so a replay never touches freed memory.
  *                 Read-only counters, cumulative over the handle's life (hadi_get_tuning only; hadi_set_tuning returns
@@ -346,6 +348,36 @@ int hadi_parallel_DO_solve(hadi_ctx *ctx, const hadi_problem *p, double S_0, dou
  * Whenever the call returns an error, the contents of greeks and ladder are unspecified. */
 int hadi_compute_greeks(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0,
                         double *greeks /* [n][8] */, double *ladder /* [n][m1+1][8] or NULL */);
+
+/* Maturity ladder -- NOT a reference feature.  A sweep of N steps passes through the solution of every shorter time to maturity
+ * n dt; these three calls return the price node after each of the steps snap_steps[0 .. n_snap) of ONE sweep, where a call per
+ * maturity would run sum(snap_steps) steps.  By definition snapshot q is what the same call with N = snap_steps[q] returns, bit for
+ * bit on the same execution path: the dividend dating only looks backwards, the carry-over arrays of CS / MCS / HV come from earlier
+ * steps and the boundary time factor depends on n dt only.  This is NOT the reference's multi-maturity convention (N_m = max(20,
+ * int(20 T_m)), dt_m = T_m / N_m): a ladder shares one dt.  For the dividend variants the dates are read on the sweep's clock, as in
+ * a single call: all maturities of the ladder share the one schedule.
+ *   snap_steps  host array, strictly increasing, every entry in 1 .. p->N, 1 <= n_snap <= p->N; the last need not be N
+ *   prices      [n][n_snap];  J [n][n_snap][5], base_prices [n][n_snap] (the 6n-group layout of hadi_compute_jacobian inside);
+ *               all follow p->memspace
+ * hadi_maturity_ladder reads p as hadi_compute_greeks does (the caller's four grids, variant, dividends, scheme, option type and
+ * strikes, per-instance parameters, U_0, the initial p->U); hadi_compute_base_prices_ladder / hadi_compute_jacobian_ladder rebuild
+ * the v-grid and honour V_0_i exactly as hadi_compute_base_prices / hadi_compute_jacobian do, the variant from p->variant.  p->U
+ * and p->lambda_bar are not written.  delta_t_i is allowed (every instance its own ladder in time on the shared step indices).  The
+ * node is the price pick's: first s-node within 1e-10 of S_0, v-row 0 if V_0 is off the v-grid; a small kernel locates it before
+ * the sweep (hadi_locate_kernel).  The LDS-resident whole-loop kernels copy the node's value out inside their time loop; the
+ * streaming kernels are followed by a hadi_snap_kernel on snapshot steps.  A ladder call runs American sweeps on the explicit
+ * (U, lambda_bar) pair and never takes hadi_sweep_resident or hadi_team_kernel: those batches run the streaming kernels, as under profiling.
+ * Errors: N_i != NULL, a bad snap_steps or a NULL output: HADI_ERR_INVALID; HADI_STATE_FP32: HADI_ERR_UNSUPPORTED; S_0 off some
+ * instance's s-grid: HADI_ERR_NOT_ON_GRID; everything else the underlying entry point refuses keeps its status.  One more:
+ * call boundary data with r_f != 0 is HADI_ERR_UNSUPPORTED -- the call's boundary vector carries exp(-r_f dt (N - 1))
+ * (hes_boundary_kernels.hpp:56), so the tables depend on N and the intermediate states are not the shorter sweeps' results; puts
+ * (whose boundary factor is exp(-r_d dt n)) and calls with r_f = 0 have the property exactly. */
+int hadi_maturity_ladder(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, int n_snap, const int *snap_steps,
+                         double *prices /* [n][n_snap] */);
+int hadi_compute_base_prices_ladder(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, int n_snap, const int *snap_steps,
+                                    double *prices /* [n][n_snap] */);
+int hadi_compute_jacobian_ladder(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, int n_snap,
+                                 const int *snap_steps, double *J /* [n][n_snap][5] */, double *base_prices /* [n][n_snap] */);
 
 /* v-grid rebuilt from (V_0, V = 5.0, d = 5.0/500) exactly as every call site of the reference
  * does (jacobian_computation.cpp:253); p->vec_v / p->delta_v are ignored. */

@@ -180,6 +180,47 @@ inline void compute_greeks(Handle &h, double S_0, double V_0, double /*T*/, doub
     detail::check(h, hadi_compute_greeks(h.ctx, &p, S_0, V_0, greeks.data(), ladder ? ladder->data() : nullptr));
 }
 
+// Maturity ladder (hadi_maturity_ladder and its two launchers; NOT in the reference): the price node after each of the steps
+// snap_steps (strictly increasing, within 1..N) of ONE N-step sweep -- prices: [num_strikes][snap_steps.size()], entry q what
+// the same call with N = snap_steps[q] returns.  workspace.U holds the initial condition and is not modified.
+inline void maturity_ladder(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho, double sigma,
+                            double kappa, double eta, int m1, int m2, int /*total_size*/, int N, double theta, double delta_t,
+                            int num_strikes, const GridViews &deviceGrids, const DO_Workspace &workspace,
+                            const std::vector<int> &snap_steps, std::vector<double> &prices, int variant = HADI_EU,
+                            const std::vector<double> *U_0 = nullptr, const Dividends *div = nullptr,
+                            const PutStrikes *put = nullptr) {
+    prices.resize((size_t)num_strikes * snap_steps.size());
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  const_cast<double *>(workspace.U.data()), U_0 ? U_0->data() : nullptr, div, put);
+    detail::check(h, hadi_maturity_ladder(h.ctx, &p, S_0, V_0, (int)snap_steps.size(), snap_steps.data(), prices.data()));
+}
+// ... with the v-grid rebuilt for V_0, as compute_base_prices does
+inline void compute_base_prices_ladder(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho,
+                                       double sigma, double kappa, double eta, int m1, int m2, int /*total_size*/, int N,
+                                       double theta, double delta_t, int num_strikes, const GridViews &deviceGrids,
+                                       const DO_Workspace &workspace, const std::vector<int> &snap_steps,
+                                       std::vector<double> &prices, int variant = HADI_EU, const std::vector<double> *U_0 = nullptr,
+                                       const Dividends *div = nullptr, const PutStrikes *put = nullptr) {
+    prices.resize((size_t)num_strikes * snap_steps.size());
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  const_cast<double *>(workspace.U.data()), U_0 ? U_0->data() : nullptr, div, put);
+    detail::check(h, hadi_compute_base_prices_ladder(h.ctx, &p, S_0, V_0, (int)snap_steps.size(), snap_steps.data(), prices.data()));
+}
+// J: [num_strikes][snap_steps.size()][5], base_prices: [num_strikes][snap_steps.size()]
+inline void compute_jacobian_ladder(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho, double sigma,
+                                    double kappa, double eta, int m1, int m2, int /*total_size*/, int N, double theta,
+                                    double delta_t, int num_strikes, const GridViews &deviceGrids, const std::vector<double> &U_0,
+                                    const std::vector<int> &snap_steps, std::vector<double> &J, std::vector<double> &base_prices,
+                                    double eps = 1e-6, int variant = HADI_EU, const Dividends *div = nullptr,
+                                    const PutStrikes *put = nullptr) {
+    J.resize((size_t)num_strikes * snap_steps.size() * 5);
+    base_prices.resize((size_t)num_strikes * snap_steps.size());
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  nullptr, U_0.data(), div, put);
+    detail::check(h, hadi_compute_jacobian_ladder(h.ctx, &p, S_0, V_0, eps, (int)snap_steps.size(), snap_steps.data(), J.data(),
+                                                  base_prices.data()));
+}
+
 // jacobian_computation.cpp:204-364 and the three variants.  J: [num_strikes][5], columns kappa, eta, sigma, rho, v0.
 inline void compute_jacobian(Handle &h, double S_0, double V_0, double, double r_d, double r_f, double rho, double sigma,
                              double kappa, double eta, int m1, int m2, int, int N, double theta, double delta_t,

@@ -15,8 +15,8 @@ from .solver import (HestonADI, DOWorkspace, Dividends, compute_parameter_update
 from .distributed import Communicator, shard_range  # noqa: F401
 from .calibration import (CalibrationPoint, calibrate, calibrate_american, calibrate_american_dividends,  # noqa: F401
                           calibrate_american_dividends_multi_maturity, calibrate_dividends, calibrate_european,
-                          calibrate_european_multi_maturity, clamp_parameters, export_calibration_csv,
-                          make_calibration_points)
+                          calibrate_european_maturity_ladder, calibrate_european_multi_maturity, clamp_parameters,
+                          export_calibration_csv, make_calibration_points, make_ladder_points)
 from . import market  # noqa: F401
 
 __all__ = ["EU", "AM", "DIV", "AM_DIV", "CALL", "PUT", "lm_partials_device", "STATE_FP64", "STATE_FP32", "SCHEME_DOUGLAS",
@@ -25,5 +25,6 @@ __all__ = ["EU", "AM", "DIV", "AM_DIV", "CALL", "PUT", "lm_partials_device", "ST
            "shard_range", "calibrate_european", "clamp_parameters", "market", "CalibrationPoint", "calibrate",
            "calibrate_american", "calibrate_dividends", "calibrate_american_dividends",
            "calibrate_european_multi_maturity", "calibrate_american_dividends_multi_maturity",
-           "make_calibration_points", "export_calibration_csv", "G_PRICE", "G_DELTA", "G_GAMMA", "G_DV", "G_DVV", "G_DSV",
+           "make_calibration_points", "export_calibration_csv", "make_ladder_points", "calibrate_european_maturity_ladder",
+           "G_PRICE", "G_DELTA", "G_GAMMA", "G_DV", "G_DVV", "G_DSV",
            "G_THETA", "G_LAMBDA", "N_GREEKS", "GREEK_NAMES"]

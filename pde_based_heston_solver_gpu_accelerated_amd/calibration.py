@@ -9,6 +9,7 @@ normal equations are all-reduced (31 doubles per iteration, 1 double for the tri
     calibrate_american_dividends                test_calibration_american_dividends                :1588-2160
     calibrate_european_multi_maturity           test_calibration_european_multi_maturity           :2428-2933
     calibrate_american_dividends_multi_maturity test_calibration_american_divident_multi_maturity  :3245-3820
+    calibrate_european_maturity_ladder          no counterpart: all maturities of a strike from ONE sweep on a shared delta_t
 
 `solver` is anything with the mirrored launchers of solver.HestonADI (`compute_jacobian*`, `compute_base_prices*`).
 """
@@ -40,6 +41,29 @@ def make_calibration_points(strikes, maturities, steps_per_year=20, min_steps=20
         for s, K in enumerate(strikes):
             pts.append(CalibrationPoint(float(K), float(T_m), N_m, dt_m, m * len(strikes) + s))
     return pts
+
+
+def make_ladder_points(strikes, maturities, delta_t):
+    """The points of a maturity ladder, flat and strike-fastest like make_calibration_points (global_index = m * len(strikes) +
+    s), but on ONE delta_t: time_steps = T_m / delta_t.  Raises ValueError unless every maturity is a whole number (>= 1) of
+    steps of delta_t, to within 1e-9 steps, and the maturities are strictly increasing.  This is NOT the reference's convention
+    (N_m = max(20, int(20 T_m)), dt_m = T_m / N_m): the maturities of a ladder share the step, so one sweep per strike passes
+    through all of them."""
+    if not (delta_t > 0 and math.isfinite(delta_t)):
+        raise ValueError("delta_t must be positive")
+    steps = []
+    for T_m in maturities:
+        x = T_m / delta_t
+        n = int(round(x))
+        if n < 1 or abs(x - n) > 1e-9:
+            raise ValueError("maturity %r is %.12g steps of delta_t = %r: not a whole number of steps" % (T_m, x, delta_t))
+        if steps and n <= steps[-1]:
+            raise ValueError("the maturities of a ladder must be strictly increasing (%r after %d steps)" % (T_m, steps[-1]))
+        steps.append(n)
+    if not steps:
+        raise ValueError("no maturities")
+    return [CalibrationPoint(float(K), float(T_m), n, float(delta_t), m * len(strikes) + s)
+            for m, (T_m, n) in enumerate(zip(maturities, steps)) for s, K in enumerate(strikes)]
 
 
 def clamp_parameters(kappa, eta, sigma, rho, v0):
@@ -114,20 +138,22 @@ def _launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, grids, U_0, 
 
 def calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0,
               market_prices, dividends=None, calibration_points=None, max_iter=20, tol=0.1, delta_tol=None, eps=1e-6,
-              lam=0.01, comm=None, lm_partials=_solver.lm_partials, lm_solve=_solver.lm_solve, scheme=0):
+              lam=0.01, comm=None, lm_partials=_solver.lm_partials, lm_solve=_solver.lm_solve, scheme=0, launchers=None):
     """The LM loop shared by all drivers (heston_calibration.cpp:204-417).  `grids`, `U_0`, `market_prices` (and
     `calibration_points` for the multi-maturity drivers, which then ignore T and N) are this rank's shard.
     `scheme`: the time stepper of every Jacobian and trial-price solve of the loop (0 Douglas, 1 Craig-Sneyd, 2 Modified
     Craig-Sneyd, 3 Hundsdorfer-Verwer), European variant only (ValueError otherwise, before any solve); `theta` is the scheme's:
     the usual pairs are 1/3 for MCS and 1/2 + sqrt(3)/6 for HV, which are second order in time where Douglas is first.
+    `launchers`: the pair of closures _launchers would build, for drivers whose instruments are not one instance each (the
+    maturity ladder); market_prices then follow the closures' order.
     Stops when ||delta||_2 < delta_tol (default: tol) or sum r^2 < tol.  Returns a dict with the calibrated
     parameters, final error, iteration count, PDE-solve count, the last computed model prices and the trajectory."""
     comm = comm or Communicator()
     n_loc = grids.Vec_s.shape[0]
     delta_tol = tol if delta_tol is None else delta_tol
     market = np.asarray(market_prices, dtype=np.float64)
-    jac, base_fn = _launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, grids, U_0, dividends,
-                              calibration_points, scheme=scheme)
+    jac, base_fn = launchers or _launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, grids, U_0, dividends,
+                                           calibration_points, scheme=scheme)
     cur = (kappa, eta, sigma, rho, V_0)
     final_error, iteration_count, converged = 100.0, 0, False
     history = []
@@ -231,6 +257,63 @@ def calibrate_european_multi_maturity(solver, S_0, r_d, r_f, kappa, eta, sigma, 
     return calibrate(solver, EU, S_0, None, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, None, theta, grids, U_0,
                      market_prices, calibration_points=calibration_points, max_iter=max_iter,
                      tol=t if tol is None else tol, delta_tol=dtol if delta_tol is None else delta_tol, scheme=scheme, **kw)
+
+
+def _ladder_launchers(solver, S_0, r_d, r_f, m1, m2, theta, delta_t, snap_steps, grids, U_0, scheme=0):
+    """The closures of calibrate() over the ladder launchers: one instance per strike, residual rows in the order
+    m * len(strikes) + s of the multi-maturity drivers (the launchers return [strike][maturity])."""
+    n_s = grids.Vec_s.shape[0]
+    total_size = (m1 + 1) * (m2 + 1)
+    N = int(snap_steps[-1])
+    sch = {"scheme": scheme} if scheme else {}
+
+    def by_maturity(x):  # [n_s][n_m][...] -> [n_m * n_s][...], numpy or torch
+        y = x.transpose(0, 1) if hasattr(x, "detach") else np.swapaxes(x, 0, 1)
+        y = y.contiguous() if hasattr(y, "contiguous") else np.ascontiguousarray(y)
+        return y.reshape((-1,) + tuple(x.shape[2:]))
+
+    def jac(k, e, s, r, v, eps):
+        J, base = solver.compute_jacobian_ladder(S_0, v, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t, n_s, grids,
+                                                 U_0, snap_steps, eps=eps, **sch)
+        return by_maturity(J), by_maturity(base)
+
+    def base(k, e, s, r, v):
+        ws = _WS()
+        ws.U = _clone(U_0)
+        return by_maturity(solver.compute_base_prices_ladder(S_0, v, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t,
+                                                             n_s, grids, ws, snap_steps, **sch))
+
+    return jac, base
+
+
+def calibrate_european_maturity_ladder(solver, S_0, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, theta, strikes, maturities,
+                                       delta_t, grids, U_0, market_prices, max_iter=15, tol=None, delta_tol=None, n_total=None,
+                                       scheme=0, **kw):
+    """calibrate_european_multi_maturity on a maturity ladder: `grids` / `U_0` hold ONE instance per strike (this rank's
+    strikes), every maturity is a whole number of steps of the shared delta_t (make_ladder_points raises otherwise), and each LM
+    iteration runs max(n_m) steps per strike and parameter group where the per-maturity batch runs sum(n_m).  market_prices:
+    [len(maturities) * len(strikes)] in the order m * len(strikes) + s, as the residuals.  Same discretisation as
+    calibrate_european_multi_maturity fed make_ladder_points -- the prices agree bit for bit on the same execution path, so the
+    LM iterates are the same.  r_f must be 0 (the library refuses a ladder of calls otherwise, hadi.h).  `pde_solves` counts the
+    sweeps actually run (one per strike and group).  scheme / theta: see calibrate.
+    Measured on one MI355X (profiles/ladder_ab.txt), Jacobian / base prices of the per-maturity launchers
+    -> the ladder's, ms per call: it was faster on every surface measured -- 50x25 with 10 evenly spaced maturities (10 .. 100
+    steps), 500 strikes 16.2 -> 3.5 / 3.2 -> 1.2 and 50 strikes 2.0 -> 1.2 / 1.29 -> 1.03 (there the per-maturity batch was
+    filling idle CUs: 1.2 - 1.7x where sum n_k / max n_k is 5.5); 256x128 with 64 strikes x 8 maturities 41.8 -> 8.4 / 10.2 ->
+    3.1.  Smaller surfaces than 50 strikes were not measured."""
+    pts = make_ladder_points(strikes, maturities, delta_t)
+    n_s, n_m = len(strikes), len(maturities)
+    if grids.Vec_s.shape[0] != n_s:
+        raise ValueError("a maturity ladder takes one grid per strike (%d grids, %d strikes)" % (grids.Vec_s.shape[0], n_s))
+    market = np.asarray(market_prices, dtype=np.float64).reshape(-1)
+    if market.size != n_s * n_m:
+        raise ValueError("market_prices must hold len(maturities) * len(strikes) prices, maturity by maturity")
+    snap_steps = [pts[m * n_s].time_steps for m in range(n_m)]
+    t, dtol = multi_maturity_tolerances(n_total or len(pts))
+    launch = _ladder_launchers(solver, S_0, r_d, r_f, m1, m2, theta, delta_t, snap_steps, grids, U_0, scheme=scheme)
+    return calibrate(solver, EU, S_0, None, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, None, theta, grids, U_0, market,
+                     max_iter=max_iter, tol=t if tol is None else tol, delta_tol=dtol if delta_tol is None else delta_tol,
+                     scheme=scheme, launchers=launch, **kw)
 
 
 def calibrate_american_dividends_multi_maturity(solver, S_0, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, theta,

@@ -75,6 +75,7 @@ struct Ctx {
     DevBuf div_flag, div_amt, div_pct;
     DevBuf pay_mis;  // American: per-instance payoff-shape flags (hadi_payoff_shape_kernel)
     DevBuf order;    // small-grid path: dispatch order of the instances (multi-maturity batches)
+    DevBuf snap_steps, snap_node, snap_out;  // maturity ladder: the snapshot steps, the instances' price nodes, the snapshots [n][n_snap]
     // Sticky device error word: one int in host-pinned, device-visible memory.  Kernels OR a HADI_DEVERR_* code into it
     // (system-scope atomic, only ever on a failure path); finish_timing reads it after the stream synchronisation every
     // entry point ends with -- no copy, no extra launch -- and turns a non-zero word into HADI_ERR_INTERNAL.
@@ -242,6 +243,12 @@ struct SweepDesc {
     const double *div_dates = nullptr, *div_amounts = nullptr, *div_pcts = nullptr;
     // diagnostics (hadi_debug_*): 1 = only the row pass of step debug_step, 2 = only one column solve of the packed input
     int debug = 0, debug_step = 1;
+    // maturity ladder (hadi_maturity_ladder and its launchers): n_snap > 0 = the value of the price node of (S_0, V_0 or v0_i) after
+    // each of the steps snap_steps[0 .. n_snap) (host array, strictly increasing, within 1 .. Nmax) goes to Ctx::snap_out
+    int n_snap = 0;
+    const int *snap_steps = nullptr;
+    double S_0 = 0, V_0 = 0;
+    const double *d_v0_i = nullptr;  // device [n] or null: per-instance V_0 of the node's v-row
 };
 
 // Kernels whose dynamic LDS can exceed the 64 KiB default need the limit raised once (hadi_create: every kernel of
@@ -435,6 +442,17 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     if ((rc = ensure(c, c->rwork, pl.n_rwork * n * 8))) return rc;
     if ((rc = ensure(c, c->ipar, sizeof(HadiInstPar) * n))) return rc;
     if ((rc = ensure(c, c->par8, 8 * 8 * n))) return rc;
+    // A ladder call: its buffers are grown here, before anything is captured (a grown buffer drops the graph cache); its American
+    // sweeps run on the explicit (U, lambda_bar) pair (P does not hold U between steps), and it never takes the resident sweep or
+    // the team launch -- those sub-batches run the streaming kernels, as under profiling.
+    const bool ladder = d.n_snap > 0 && !d.debug;
+    std::vector<int> snap_q(d.Nmax + 2, -1);  // step -> snapshot index
+    if (ladder) {
+        if ((rc = ensure(c, c->snap_steps, sizeof(int) * d.n_snap)) || (rc = ensure(c, c->snap_node, sizeof(int) * n)) ||
+            (rc = ensure(c, c->snap_out, 8 * n * d.n_snap)) || (rc = ensure(c, c->status, sizeof(int) * n)))
+            return rc;
+        for (int q = 0; q < d.n_snap; q++) snap_q[d.snap_steps[q]] = q;
+    }
 
     hipStream_t s = c->stream;
     HIP_TRY(c, hipEventRecord(c->ev[0], s));
@@ -476,6 +494,11 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     sa.a2i = ptr<double>(c->a2i); sa.pb = ptr<double>(c->pb); sa.rinv = ptr<double>(c->rinv);
     sa.rwork = ptr<double>(c->rwork); sa.ipar = ptr<HadiInstPar>(c->ipar);
     hipLaunchKernelGGL(hadi_setup_kernel, dim3(d.n), dim3(256), 0, s, sa);
+    if (ladder) {
+        if ((rc = stage_to_device(c, c->snap_steps.p, d.snap_steps, sizeof(int) * d.n_snap))) return rc;
+        hipLaunchKernelGGL(hadi_locate_kernel, dim3((d.n + 63) / 64), dim3(64), 0, s, L, d.n, d.d_vec_s, d.d_vec_v, d.S_0, d.d_v0_i, d.V_0,
+                           ptr<int>(c->snap_node), ptr<int>(c->status));
+    }
 
     const size_t tot = (size_t)L.inst_stride * d.n;
     hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src, d.d_natU, ptr<double>(c->U));
@@ -491,7 +514,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     // One small device-to-host copy per solve decides it.
     bool amp = false;
     const bool takes_small_path = c->use_small && !c->profiling && !cs && !f32 && !d.debug && (american ? pl.smem_small_am : pl.smem_small_eu) > 0;
-    if (american && c->use_amp && !cs && !takes_small_path && !d.debug && !seq_shape) {
+    if (american && c->use_amp && !cs && !takes_small_path && !d.debug && !seq_shape && !ladder) {
         std::vector<int> mis(d.n);
         HIP_TRY(c, hipMemcpyAsync(mis.data(), c->pay_mis.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
@@ -567,7 +590,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     // (`pinned`, above: neither the resident sweep nor, below, the team launch is chosen automatically)
     const bool resident_shape = (c->resident_sweep > 0 || (c->resident_sweep < 0 && !pinned)) && d.scheme == HADI_SCHEME_DOUGLAS &&
                                 d.variant == HADI_EU && !f32 && L.B == 8 && L.G == 1 && L.P <= 8 && !seq_shape && d.theta > 0.0 &&
-                                d.r_d != d.r_f && !d.debug && !c->debug_fault && !prof;  // (test hooks: the streaming kernels they are for)
+                                d.r_d != d.r_f && !d.debug && !c->debug_fault && !prof && !ladder;  // (test hooks: the streaming kernels they are for)
     auto resident = [&](const SubBatch &sbt) {
         return resident_shape && sbt.pl.use_strip && !sbt.pl.use_pairs && sbt.pl.sblocks == 1 && sbt.cnt <= c->cu_count &&
                hadi_plan_row_idle(sbt.pl, sbt.cnt, c->cu_count) < HADI_TWO_STREAM_IDLE;
@@ -637,6 +660,9 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
             if (cs) {  // corrector (profiling events cover the predictor's two passes only)
                 if ((rc = row_pass(av, 2)) || (rc = col_pass(a))) return rc;
             }
+            if (ladder && snap_q[nstep] >= 0)  // (U is explicit here: a ladder call never runs in the P representation)
+                hipLaunchKernelGGL(hadi_snap_kernel, dim3((nsb + 63) / 64), dim3(64), 0, q, L, nsb, Ub, ptr<int>(c->snap_node) + o,
+                                   ptr<double>(c->snap_out) + (size_t)o * d.n_snap, d.n_snap, snap_q[nstep]);
             if (xstep)
                 hipLaunchKernelGGL(hadi_am_dematerialise_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, nsb, a.ipar, U0b, Ub, LAMb);
         }
@@ -691,8 +717,15 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
         if (have_div) {
             sm.div_flag = ptr<int>(c->div_flag); sm.div_amounts = ptr<double>(c->div_amt); sm.div_pcts = ptr<double>(c->div_pct);
         }
+        if (ladder) {
+            sm.snap_steps = ptr<int>(c->snap_steps); sm.n_snap = d.n_snap;
+            sm.snap_node = ptr<int>(c->snap_node); sm.snap_out = ptr<double>(c->snap_out);
+        }
         return HADI_OK;
     };
+    // what hadi_describe_last_sweep adds for a ladder call
+    const std::string ladder_loop = ladder ? "; maturity ladder: " + std::to_string(d.n_snap) + " snapshots copied inside the time loop" : "";
+    const std::string ladder_stream = ladder ? "; maturity ladder: " + std::to_string(d.n_snap) + " snapshots, hadi_snap_kernel after each snapshot step" : "";
     if (small_sch) {
         const int sch = d.scheme == HADI_SCHEME_MCS ? HADI_SCH_MCS : d.scheme == HADI_SCHEME_HV ? HADI_SCH_HV : HADI_SCH_CS;
         const HadiLoopFn fn = hadi_small_sch_fn(L.B, sch);
@@ -701,7 +734,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
         char buf[256];
         std::snprintf(buf, sizeof buf, "hadi_small_sch_kernel<%d,%s>: whole time loop in one launch, one wavefront per instance, predictor and corrector lines solved sequentially in LDS (%zu B)",
                       L.B, sch == HADI_SCH_MCS ? "MCS" : sch == HADI_SCH_HV ? "HV" : "CS", smem);
-        c->last_path = buf;
+        c->last_path = buf + ladder_loop;
         HadiSmallArgs sm;
         if ((rc = small_args(sm))) return rc;
         HIP_TRY(c, hipEventRecord(c->ev[1], s));
@@ -726,7 +759,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
             else
                 std::snprintf(buf, sizeof buf, "hadi_small_kernel<%d,%d,%s>: whole time loop in one launch, instance resident in LDS (%zu B)", L.B,
                               sel.k->G, american ? "AM" : "EU", sel.smem);
-            c->last_path = buf;
+            c->last_path = buf + ladder_loop;
         }
         HadiSmallArgs sm;
         if ((rc = small_args(sm))) return rc;
@@ -746,6 +779,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
         else if (nres)
             c->last_path += "; both passes of every step in one launch for " + std::to_string(nres) +
                             " sub-batches of one round: hadi_sweep_resident<8> (one block per instance, all column tiles), the others streaming";
+        c->last_path += ladder_stream;
     }
     c->last_nsub = nsub;
     HIP_TRY(c, hipEventRecord(c->ev[1], s));
@@ -755,7 +789,7 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     // recorded by the kernel, checked here, and the batch is solved again on the streaming path below.
     const bool team_shape = d.n <= 8 && L.G == 1 && (L.B == 8 || L.B == 4) && L.P <= 8 && !seq_shape && (d.variant == HADI_EU || d.variant == HADI_DIV) && !cs && !f32 &&
                             !d.debug && !prof && d.theta > 0.0 && d.r_d != d.r_f && c->cu_count == 256;
-    if (team_shape && (c->team_launch > 0 || (c->team_launch < 0 && !c->team_failed && !pinned))) {
+    if (team_shape && !ladder && (c->team_launch > 0 || (c->team_launch < 0 && !c->team_failed && !pinned))) {
         if ((rc = ensure(c, c->team, 512 * sizeof(int)))) return rc;
         HIP_TRY(c, hipMemsetAsync(c->team.p, 0, 512 * sizeof(int), s));
         HadiTeamArgs ta;
@@ -817,6 +851,12 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
         }
         put(&d.Nmax, sizeof(int)); put(&d.dt0, sizeof(double));
         put(&d.variant, sizeof(int));
+        if (ladder) {  // the snapshot launches sit behind the steps of the list, with these addresses
+            const void *lad[] = {c->snap_node.p, c->snap_out.p};
+            put(lad, sizeof(lad));
+            put(&d.n_snap, sizeof(int));
+            put(d.snap_steps, sizeof(int) * d.n_snap);
+        }
         if (have_div) {  // amounts / percentages / per-instance tables are re-uploaded every call; the node list
                          // only depends on which steps carry a dividend launch
             put(&flag_stride, sizeof(int));
@@ -964,6 +1004,24 @@ int check_problem(Ctx *c, const hadi_problem *p, bool need_U, bool need_vgrid) {
     return HADI_OK;
 }
 
+// What the ladder entry points ask beyond check_problem (which has passed).  The definition -- snapshot q is what the same call
+// with N = snap_steps[q] returns -- needs every table of the sweep to be independent of N.  One is not: the call's boundary
+// vector carries exp(-r_f dt (N - 1)) (hes_boundary_kernels.hpp:56, mirrored by hadi_setup_instance), so with call data and
+// r_f != 0 the state after n steps of an N-step sweep is NOT the n-step solve, and the ladder refuses such a problem.
+int check_ladder(Ctx *c, const hadi_problem *p, int n_snap, const int *snap_steps, const void *out) {
+    if (!out) return fail(c, HADI_ERR_INVALID, "ladder output missing");
+    if (p->N_i) return fail(c, HADI_ERR_INVALID, "a maturity ladder shares the step indices: N_i must be NULL (delta_t_i is allowed)");
+    if (!snap_steps || n_snap < 1 || n_snap > p->N) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
+    for (int q = 0; q < n_snap; q++)
+        if (snap_steps[q] < 1 || snap_steps[q] > p->N || (q && snap_steps[q] <= snap_steps[q - 1]))
+            return fail(c, HADI_ERR_INVALID, "snap_steps must be strictly increasing within 1..N (entry %d is %d)", q, snap_steps[q]);
+    if (p->state_precision == HADI_STATE_FP32) return fail(c, HADI_ERR_UNSUPPORTED, "the maturity ladder needs the fp64 state");
+    if (p->option_type == HADI_CALL && p->r_f != 0.0)
+        return fail(c, HADI_ERR_UNSUPPORTED, "call boundary data carry exp(-r_f dt (N - 1)): with r_f != 0 the intermediate states of a "
+                                             "sweep are not the shorter sweeps' results, so there is no ladder");
+    return HADI_OK;
+}
+
 // Fills the per-instance parameter rows for `groups` copies of the caller's batch.
 void fill_par(const hadi_problem *p, SweepDesc &d, int groups) {
     const int n0 = p->n_instances;
@@ -1012,10 +1070,14 @@ int rebuild_v_device(Ctx *c, int n, int m2, const std::vector<double> &v0i) {
 
 // Shared driver of hadi_DO_timestepping / hadi_parallel_DO_solve / hadi_compute_base_prices* and the diagnostics
 // (debug != 0: p->U is input only, the pass's result goes to debug_out).
+// Ladder (n_snap > 0; hadi_maturity_ladder, hadi_compute_base_prices_ladder): prices_out is [n][n_snap], the snapshots the sweep
+// took on the way; p->U and p->lambda_bar are not written.
 int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, double S_0, double V_0, double *prices_out,
-                 int debug = 0, int debug_step = 1, double *debug_out = nullptr) {
+                 int debug = 0, int debug_step = 1, double *debug_out = nullptr, int n_snap = 0, const int *snap_steps = nullptr) {
     int rc = check_problem(c, p, true, !rebuild_v);
     if (rc) return rc;
+    const bool ladder = n_snap > 0 || snap_steps;
+    if (ladder && (rc = check_ladder(c, p, n_snap, snap_steps, prices_out))) return rc;
     if (debug && !debug_out) return fail(c, HADI_ERR_INVALID, "output array missing");
     if (debug && (p->scheme != HADI_SCHEME_DOUGLAS || p->state_precision != HADI_STATE_FP64))
         return fail(c, HADI_ERR_UNSUPPORTED, "diagnostics cover fp64 Douglas steps");
@@ -1064,9 +1126,24 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
     // the buffers the outputs pass through, grown before the sweep: growing one after it would drop the loop it just captured
     if (p->memspace != HADI_MEM_DEVICE && (rc = ensure(c, c->natOut, n * m * 8))) return rc;
     if (pick && ((rc = ensure(c, c->prices, n * 8)) || (rc = ensure(c, c->status, n * sizeof(int))))) return rc;
+    if (ladder) {
+        d.n_snap = n_snap; d.snap_steps = snap_steps; d.S_0 = S_0; d.V_0 = V_0;
+        d.d_v0_i = per_inst_v0 ? ptr<double>(c->v0_i) : nullptr;
+    }
 
     HadiPlan pl;
     if ((rc = run_sweep(c, d, pl))) return rc;
+
+    if (ladder) {  // the snapshots and the locate step's status words are all that leaves the device
+        if ((rc = from_device(c, p->memspace, prices_out, ptr<double>(c->snap_out), (size_t)n * n_snap))) return rc;
+        std::vector<int> hs(n);
+        HIP_TRY(c, hipMemcpyAsync(hs.data(), c->status.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipGetLastError());
+        if ((rc = finish_timing(c, d))) return rc;
+        for (int k = 0; k < n; k++)
+            if (hs[k]) return fail(c, HADI_ERR_NOT_ON_GRID, "S_0 = %.17g is not a node of instance %d's s-grid", S_0, k);
+        return HADI_OK;
+    }
 
     // solution back to the caller's U (natural layout); diagnostics: the pass's result to debug_out, U untouched
     double *const host_dst = debug ? debug_out : p->U;
@@ -1165,9 +1242,13 @@ int greeks_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double 
 // compute_jacobian*: the reference runs 6 solves one after the other inside each team
 // (jacobian_computation.cpp:232-363); here they are 6n independent instances of ONE batched sweep:
 // group 0 = base, 1..4 = kappa, eta, sigma, rho + eps, 5 = v-grid rebuilt for V_0 + eps.
-int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double eps, double *J, double *base_prices) {
+// Ladder (n_snap > 0; hadi_compute_jacobian_ladder): J [n][n_snap][5] and base_prices [n][n_snap] from the snapshots of the 6n solves.
+int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double eps, double *J, double *base_prices,
+                    int n_snap = 0, const int *snap_steps = nullptr) {
     int rc = check_problem(c, p, false, false);
     if (rc) return rc;
+    const bool ladder = n_snap > 0 || snap_steps;
+    if (ladder && (rc = check_ladder(c, p, n_snap, snap_steps, (J && base_prices) ? J : nullptr))) return rc;
     DeviceGuard guard(c->device);
     pin_rewind(c);
     if (!p->U_0) return fail(c, HADI_ERR_INVALID, "U_0 (initial condition) is required for the Jacobian");
@@ -1191,7 +1272,7 @@ int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, doubl
     const double *src_s, *src_ds;
     // (natOut stages delta_s here and takes J and the base prices after the sweep; prices / status: the pick.  All grown before
     // the sweep: growing one after it would drop the loop it just captured)
-    if ((rc = ensure(c, c->natOut, (size_t)n0 * std::max(m1, 6) * 8)) || (rc = ensure(c, c->prices, n * 8)) ||
+    if ((rc = ensure(c, c->natOut, (size_t)n0 * std::max(m1, 6 * std::max(n_snap, 1)) * 8)) || (rc = ensure(c, c->prices, n * 8)) ||
         (rc = ensure(c, c->status, n * sizeof(int))))
         return rc;
     if ((rc = to_device(c, p->memspace, p->vec_s, (size_t)n0 * (m1 + 1), c->natU, &src_s))) return rc;
@@ -1240,22 +1321,31 @@ int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, doubl
     // every solve starts from U_0 (jacobian_computation.cpp:307-309); payoff for American = U_0 too
     if ((rc = to_device(c, p->memspace, p->U_0, n0 * m, c->natU0, &d.d_natU))) return rc;
     d.d_natU0 = d.d_natU;
+    if (ladder) {
+        d.n_snap = n_snap; d.snap_steps = snap_steps; d.S_0 = S_0; d.V_0 = V_0; d.d_v0_i = ptr<double>(c->v0_i);
+    }
 
     HadiPlan pl;
     if ((rc = run_sweep(c, d, pl))) return rc;
-    hipLaunchKernelGGL(hadi_pick_kernel, dim3((n + 63) / 64), dim3(64), 0, s, pl.L, n, d.d_vec_s, d.d_vec_v,
-                       ptr<double>(c->U), S_0, ptr<double>(c->v0_i), V_0, ptr<double>(c->prices), 1, ptr<int>(c->status));
+    if (!ladder)
+        hipLaunchKernelGGL(hadi_pick_kernel, dim3((n + 63) / 64), dim3(64), 0, s, pl.L, n, d.d_vec_s, d.d_vec_v,
+                           ptr<double>(c->U), S_0, ptr<double>(c->v0_i), V_0, ptr<double>(c->prices), 1, ptr<int>(c->status));
     // J(k, param) = (pert - base) / eps on the device (jacobian_computation.cpp:329,360): with HADI_MEM_DEVICE the rows
     // never leave HBM (hadi_lm_partials_device reduces them there); only the n status words come back
     double *dJ = J, *db = base_prices;
     if (p->memspace == HADI_MEM_HOST) {
         dJ = ptr<double>(c->natOut);
-        db = dJ + (size_t)n0 * 5;
+        db = dJ + (size_t)n0 * 5 * std::max(n_snap, 1);
     }
-    hipLaunchKernelGGL(hadi_jacobian_rows_kernel, dim3((n0 + 255) / 256), dim3(256), 0, s, n0, ptr<double>(c->prices), eps, dJ, db);
+    const size_t nrow = (size_t)n0 * std::max(n_snap, 1);  // rows of J
+    if (ladder)
+        hipLaunchKernelGGL(hadi_jacobian_ladder_rows_kernel, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, s, n0, n_snap,
+                           ptr<double>(c->snap_out), eps, dJ, db);
+    else
+        hipLaunchKernelGGL(hadi_jacobian_rows_kernel, dim3((n0 + 255) / 256), dim3(256), 0, s, n0, ptr<double>(c->prices), eps, dJ, db);
     if (p->memspace == HADI_MEM_HOST) {
-        HIP_TRY(c, hipMemcpyAsync(J, dJ, (size_t)n0 * 5 * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(base_prices, db, (size_t)n0 * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(J, dJ, nrow * 5 * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(base_prices, db, nrow * 8, hipMemcpyDeviceToHost, s));
     }
     std::vector<int> hs_fallback;
     int *hs = static_cast<int *>(pin_alloc(c, (size_t)n * sizeof(int)));  // (pinned: the copy does not block the host)
@@ -1283,7 +1373,7 @@ void release_handle(Ctx *c) {
                       &c->rinv, &c->rwork, &c->ipar, &c->par8, &c->g_s, &c->g_v, &c->g_ds, &c->g_dv, &c->src_v,
                       &c->src_dv, &c->sel_a, &c->sel_b, &c->v0_i, &c->natU, &c->natU0, &c->natOut, &c->prices,
                       &c->status, &c->div_flag, &c->div_amt, &c->div_pct, &c->V, &c->R1, &c->C2, &c->pay_mis, &c->Uf, &c->Yf,
-                      &c->order, &c->lm31, &c->team, &c->rs_tab};
+                      &c->order, &c->lm31, &c->team, &c->rs_tab, &c->snap_steps, &c->snap_node, &c->snap_out};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &g : c->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
@@ -1610,6 +1700,27 @@ int hadi_debug_rcp(hadi_ctx *ctx, int n, const double *x, double *out) {
 int hadi_compute_jacobian(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, double *J,
                           double *base_prices) {
     return jacobian_common(reinterpret_cast<Ctx *>(ctx), p, S_0, V_0, eps, J, base_prices);
+}
+
+// ---- maturity ladder: the sweep's intermediate states at the price node --------------------------------
+int hadi_maturity_ladder(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, int n_snap, const int *snap_steps, double *prices) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
+    return solve_common(c, p, false, true, S_0, V_0, prices, 0, 1, nullptr, n_snap, snap_steps);
+}
+
+int hadi_compute_base_prices_ladder(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, int n_snap, const int *snap_steps,
+                                    double *prices) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
+    return solve_common(c, p, true, true, S_0, V_0, prices, 0, 1, nullptr, n_snap, snap_steps);
+}
+
+int hadi_compute_jacobian_ladder(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, int n_snap,
+                                 const int *snap_steps, double *J, double *base_prices) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
+    return jacobian_common(c, p, S_0, V_0, eps, J, base_prices, n_snap, snap_steps);
 }
 
 HADI_VARIANT_WRAPPERS(american, HADI_AM)

@@ -300,6 +300,49 @@ __global__ void __launch_bounds__(64) hadi_pick_kernel(HadiLayout L, int n_inst,
     prices[(size_t)inst * price_stride] = U[(size_t)inst * L.inst_stride + (size_t)iv * L.rowp + hadi_pos(L, is)];
 }
 
+// ------------------------------------------------------------------------------------------------
+// Maturity ladder (hadi_maturity_ladder): the price node, located BEFORE the sweep by hadi_pick_kernel's own rule -- first
+// s-node with |s_i - S_0| < 1e-10, first v-node with |v_j - V_0| < 1e-10 (row 0 if none).  node[inst] = the packed offset
+// row * rowp + slot of the node inside the instance's state, or -1 (status[inst] = 1) if S_0 is off its s-grid.
+__global__ void __launch_bounds__(64) hadi_locate_kernel(HadiLayout L, int n_inst, const double *__restrict__ vec_s,
+                                                         const double *__restrict__ vec_v, double S_0,
+                                                         const double *__restrict__ V0_i, double V_0, int *__restrict__ node,
+                                                         int *__restrict__ status) {
+    const int inst = blockIdx.x * blockDim.x + threadIdx.x;
+    if (inst >= n_inst) return;
+    const double *s = vec_s + (size_t)inst * (L.m1 + 1);
+    const double *v = vec_v + (size_t)inst * (L.m2 + 1);
+    const double v0 = V0_i ? V0_i[inst] : V_0;
+    int is = -1, iv = 0;
+    for (int i = 0; i <= L.m1; i++)
+        if (fabs(s[i] - S_0) < 1e-10) { is = i; break; }
+    for (int j = 0; j <= L.m2; j++)
+        if (fabs(v[j] - v0) < 1e-10) { iv = j; break; }
+    status[inst] = is < 0 ? 1 : 0;
+    node[inst] = is < 0 ? -1 : iv * L.rowp + hadi_pos(L, is);
+}
+
+// Streaming path of a ladder call: snapshot q of every instance of a sub-batch, after the last pass of step snap_steps[q].
+// U, node and out are the sub-batch's own (already offset); out[inst * n_snap + q].
+__global__ void __launch_bounds__(64) hadi_snap_kernel(HadiLayout L, int n_inst, const double *__restrict__ U,
+                                                       const int *__restrict__ node, double *__restrict__ out, int n_snap, int q) {
+    const int inst = blockIdx.x * blockDim.x + threadIdx.x;
+    if (inst >= n_inst) return;
+    const int off = node[inst];
+    out[(size_t)inst * n_snap + q] = off >= 0 ? U[(size_t)inst * L.inst_stride + off] : nan("");
+}
+
+// hadi_jacobian_rows_kernel for a ladder: prices [6 n0][n_snap] -> J [n0][n_snap][5], base [n0][n_snap].
+__global__ void __launch_bounds__(256) hadi_jacobian_ladder_rows_kernel(int n0, int n_snap, const double *__restrict__ prices,
+                                                                        double eps, double *__restrict__ J,
+                                                                        double *__restrict__ base) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n0 * n_snap) return;
+    const double b = prices[e];
+    base[e] = b;
+    for (int g = 1; g <= 5; g++) J[(size_t)e * 5 + (g - 1)] = (prices[(size_t)g * n0 * n_snap + e] - b) / eps;
+}
+
 // J(k, param) = (perturbed price - base price) / eps from the 6 n0 prices of a flattened Jacobian sweep (groups: base, kappa,
 // eta, sigma, rho, v0), jacobian_computation.cpp:329,360.
 __global__ void __launch_bounds__(256) hadi_jacobian_rows_kernel(int n0, const double *__restrict__ prices, double eps,

@@ -19,7 +19,33 @@ struct HadiSmallArgs {
     const double *vec_s;        // [n_inst][m1+1] (dividend interpolation)
     int Nmax;
     const int *order;           // block b solves instance order[b] (longest time loops first), nullptr = identity
+    // Maturity ladder (hadi_maturity_ladder; 0 / nullptr = none): after step snap_steps[q] (strictly increasing, device array)
+    // the value of node snap_node[inst] -- the packed offset row * rowp + slot that hadi_locate_kernel wrote, -1 if S_0 is off the
+    // instance's s-grid -- goes to snap_out[inst * n_snap + q]
+    const int *snap_steps = nullptr;
+    int n_snap = 0;
+    const int *snap_node = nullptr;
+    double *snap_out = nullptr;
 };
+
+// The ladder's running cursor of a whole-loop kernel: wave-uniform (kernel arguments and the step counter only).  `next` is the
+// step of the next snapshot, 0 when none is left (no step is numbered 0).
+struct HadiSnapCursor {
+    int q, next;
+};
+HADI_HD inline HadiSnapCursor hadi_snap_begin(const HadiSmallArgs &sm) {
+    return HadiSnapCursor{0, sm.n_snap > 0 ? sm.snap_steps[0] : 0};
+}
+HADI_HD inline void hadi_snap_advance(const HadiSmallArgs &sm, HadiSnapCursor &sc) {
+    sc.q++;
+    sc.next = sc.q < sm.n_snap ? sm.snap_steps[sc.q] : 0;
+}
+// The node's offset in an LDS field kept in natural order with pitch PL (the sequential kernels), from the packed offset
+HADI_HD inline int hadi_snap_natural(const HadiLayout &L, int node, int PL) {
+    if (node < 0) return -1;
+    const int j = node / L.rowp, i = hadi_slot_to_i(L, node - j * L.rowp);
+    return i < 0 ? -1 : j * PL + i;
+}
 
 template <int B, int W, bool AMER>
 __global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, HadiSmallArgs sm) {
@@ -86,6 +112,8 @@ __global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, Had
     __syncthreads();
 
     const int N = ip.N < sm.Nmax ? ip.N : sm.Nmax;
+    HadiSnapCursor snap = hadi_snap_begin(sm);
+    const int snap_off = sm.n_snap > 0 ? sm.snap_node[inst] : -1;
     HADI_STAMP_DECL(c.stamp_acc_)
     const double *__restrict__ vs = sm.vec_s ? sm.vec_s + (size_t)inst * (m1 + 1) : nullptr;
     for (int n = 1; n <= N; n++) {
@@ -197,6 +225,11 @@ __global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, Had
             }
         }
         __syncthreads();
+        // maturity ladder: nothing writes U before the next barrier (the row pass reads it, a dividend copies it to Y first)
+        if (n == snap.next) {
+            if (tid == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
+            hadi_snap_advance(sm, snap);
+        }
     }
 #if defined(HADI_STAMPS) && !defined(HADI_EMU)
     if (lane == 0)
@@ -313,6 +346,8 @@ __global__ void __launch_bounds__(64) hadi_small_seq_kernel(HadiSweepArgs a, Had
     __syncthreads();
 
     const int N = ip.N < sm.Nmax ? ip.N : sm.Nmax;
+    HadiSnapCursor snap = hadi_snap_begin(sm);
+    const int snap_off = sm.n_snap > 0 ? hadi_snap_natural(a.L, sm.snap_node[inst], PL) : -1;
     const double *__restrict__ vs = sm.vec_s ? sm.vec_s + (size_t)inst * (m1 + 1) : nullptr;
     for (int n = 1; n <= N; n++) {
         // ---- discrete dividend at the start of the step (device_solver.hpp:448-504) ---------------
@@ -553,6 +588,11 @@ __global__ void __launch_bounds__(64) hadi_small_seq_kernel(HadiSweepArgs a, Had
             }
         }
         __syncthreads();
+        // maturity ladder: lane 0 reads the node before it stores anything of the next step (one wavefront: nobody else has yet)
+        if (n == snap.next) {
+            if (lane == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
+            hadi_snap_advance(sm, snap);
+        }
     }
     for (int e = lane; e < nrows * (m1 + 1); e += 64) {
         const int jj = e / (m1 + 1), i = e - jj * (m1 + 1);
@@ -646,6 +686,9 @@ __global__ void __launch_bounds__(64) hadi_small_seq2_kernel(HadiSweepArgs a, Ha
     const double *b2p = last ? b2l : bl + Ls.off_zero;      // b2 lives on the last v-row only
     __syncthreads();
 
+    HadiSnapCursor snap = hadi_snap_begin(sm);
+    // (lanes 0 and 32 serve the two instances; the odd last block has no second one)
+    const int snap_off = (sm.n_snap > 0 && jl == 0 && (half == 0 || has1)) ? hadi_snap_natural(a.L, sm.snap_node[inst], PL) : -1;
     for (int n = 1; n <= Nw; n++) {
         // ---- discrete dividends at the start of the step, instance by instance (device_solver.hpp:448-504) ----
         for (int h = 0; h < (has1 ? 2 : 1); h++) {
@@ -880,6 +923,12 @@ __global__ void __launch_bounds__(64) hadi_small_seq2_kernel(HadiSweepArgs a, Ha
             }
         }
         __syncthreads();
+        // maturity ladder: one lane per instance reads its node before it stores anything of the next step
+        if (n == snap.next) {
+            if (jl == 0 && (half == 0 || has1) && n <= Nl)
+                sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
+            hadi_snap_advance(sm, snap);
+        }
     }
     for (int h = 0; h < (has1 ? 2 : 1); h++) {
         const int ih = h ? inst1 : inst0;

@@ -342,6 +342,8 @@ __global__ void __launch_bounds__(64) hadi_small_sch_kernel(HadiSweepArgs a, Had
     const bool rowrun = act;
 #endif
     const int N = ip.N < sm.Nmax ? ip.N : sm.Nmax;
+    HadiSnapCursor snap = hadi_snap_begin(sm);
+    const int snap_off = sm.n_snap > 0 ? hadi_snap_natural(a.L, sm.snap_node[inst], PL) : -1;
     for (int n = 1; n <= N; n++) {
         const double e_nm1 = exp(ip.bc_rate * ip.dt * (n - 1));
         const double e_n = exp(ip.bc_rate * ip.dt * n);
@@ -353,6 +355,11 @@ __global__ void __launch_bounds__(64) hadi_small_sch_kernel(HadiSweepArgs a, Had
         __syncthreads();
         cols();                                           // Y -> the new U
         __syncthreads();
+        // maturity ladder: lane 0 reads the node before it stores anything of the next step (one wavefront: nobody else has yet)
+        if (n == snap.next) {
+            if (lane == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
+            hadi_snap_advance(sm, snap);
+        }
     }
     for (int e = lane; e < nrows * (m1 + 1); e += 64) {
         const int jj = e / (m1 + 1), i = e - jj * (m1 + 1);

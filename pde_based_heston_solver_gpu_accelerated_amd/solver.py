@@ -339,6 +339,73 @@ class HestonADI:
             self._raise(rc)
         return (out, lad) if ladder else out
 
+    # ---- maturity ladder (hadi_maturity_ladder and its launchers; no reference counterpart) ---------------
+    @staticmethod
+    def _snap(snap_steps):
+        a = np.ascontiguousarray(np.asarray(snap_steps, dtype=np.int32).reshape(-1))
+        if a.size < 1:
+            raise ValueError("snap_steps is empty")
+        return a
+
+    def maturity_ladder(self, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U, S_0, V_0, snap_steps,
+                        variant=EU, U_0=None, dividends=None, per_instance=None, scheme=0, option_type=CALL, strikes=None):
+        """ONE sweep of N steps from the initial condition U (not modified) on the caller's grids; returns [n][len(snap_steps)]:
+        the price node of (S_0, V_0) after each of the steps snap_steps (strictly increasing, within 1..N) -- entry q is, bit for
+        bit, what the same call with N = snap_steps[q] returns.  The maturities share delta_t (per_instance['delta_t_i'] gives
+        every instance its own) and, for the dividend variants, the one schedule on the sweep's clock.  per_instance must not
+        carry N_i.  Call boundary data with r_f != 0 raise HadiError (status 2): their tables depend on N (hadi.h)."""
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U=U, U_0=U_0,
+                          dividends=dividends, per_instance=per_instance, scheme=scheme, option_type=option_type,
+                          strikes=strikes)
+        steps = self._snap(snap_steps)
+        out, optr = self._out(grids.Vec_s.shape[0], steps.size, U)
+        rc = self._lib.hadi_maturity_ladder(self._h, C.byref(p), float(S_0), float(V_0), int(steps.size),
+                                            steps.ctypes.data_as(_ip), optr)
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return out.reshape(-1, steps.size)
+
+    def compute_base_prices_ladder(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                   num_strikes, deviceGrids, workspace, snap_steps, variant=EU, U_0=None, dividends=None,
+                                   per_instance=None, scheme=0):
+        """compute_base_prices* (the v-grid rebuilt for V_0 or per_instance['V_0_i']) with the ladder's output: [n][len(snap_steps)],
+        entry q what the single call with N = snap_steps[q] returns.  workspace.U is the initial condition and is not modified."""
+        option_type, strikes = self._option(per_instance)
+        if total_size != (m1 + 1) * (m2 + 1):
+            raise ValueError("total_size != (m1+1)*(m2+1)")
+        if deviceGrids.Vec_s.shape[0] != num_strikes:
+            raise ValueError("num_strikes does not match the grid batch")
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=workspace.U,
+                          U_0=U_0, dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
+                          option_type=option_type, strikes=strikes)
+        steps = self._snap(snap_steps)
+        out, optr = self._out(num_strikes, steps.size, workspace.U)
+        rc = self._lib.hadi_compute_base_prices_ladder(self._h, C.byref(p), float(S_0), float(V_0), int(steps.size),
+                                                       steps.ctypes.data_as(_ip), optr)
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return out.reshape(-1, steps.size)
+
+    def compute_jacobian_ladder(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                num_strikes, deviceGrids, U_0, snap_steps, eps=1e-6, variant=EU, dividends=None,
+                                per_instance=None, scheme=0):
+        """compute_jacobian* with the ladder's outputs: (J [n][len(snap_steps)][5], base_prices [n][len(snap_steps)]); J[:, q, :]
+        and base_prices[:, q] are what compute_jacobian* with N = snap_steps[q] returns."""
+        if total_size != (m1 + 1) * (m2 + 1):
+            raise ValueError("total_size != (m1+1)*(m2+1)")
+        option_type, strikes = self._option(per_instance)
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=None, U_0=U_0,
+                          dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
+                          option_type=option_type, strikes=strikes)
+        steps = self._snap(snap_steps)
+        J, jptr = self._out(num_strikes * steps.size, 5, U_0)
+        base, bptr = self._out(num_strikes, steps.size, U_0)
+        rc = self._lib.hadi_compute_jacobian_ladder(self._h, C.byref(p), float(S_0), float(V_0), float(eps), int(steps.size),
+                                                    steps.ctypes.data_as(_ip), jptr, bptr)
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return J.reshape(num_strikes, steps.size, 5), base.reshape(-1, steps.size)
+
     # ---- compute_base_prices* (src/jacobian_computation.cpp:368, 629, 922, 1232) ---------------
     def _base_prices(self, variant, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N,
                      theta, delta_t, num_strikes, deviceGrids, workspace, U_0=None, dividends=None,
