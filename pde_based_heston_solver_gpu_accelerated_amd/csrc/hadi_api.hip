@@ -14,7 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "hadi_dispatch.h"
+#include "hadi_route.h"
 
 namespace {
 
@@ -49,26 +49,10 @@ struct Ctx {
     // cumulative per handle (hadi_get_tuning "graph_captures" / "graph_replays" / "graph_drops" / "graph_evictions"): time loops
     // captured, replayed from the cache, cache entries destroyed because a buffer was freed (ensure), evicted as least recently used
     unsigned long long graph_captures = 0, graph_replays = 0, graph_drops = 0, graph_evictions = 0;
-    int use_graph = 1;
-    int graph_max_melems = 8;  // hipGraph replay for batches of up to this many Mi state elements (hadi_set_tuning "graph_max_melems")
-    int use_small = 1;  // LDS-resident one-launch path for small grids
-    int small_seq = -1;  // ... European / dividend sweeps on the one-wavefront-per-instance kernel: -1 by batch size, 0 never, 1 always
-    int use_amp = 1;    // American sweeps without the lambda_bar array when the payoff depends on s only
-    int device_vgrid = 1;  // compute_base_prices / compute_jacobian: v-grids rebuilt per instance on the device
-    int sub_batch = 1;     // large batches run sub-batch by sub-batch (run_sweep)
-    int small_sch = -1;    // predictor-corrector schemes on the one-wavefront-per-instance LDS kernel (hadi_small_sch_kernel): -1 by batch size, 0 never, 1 wherever admitted
-    int small_pairs = -1;  // small-grid sequential kernel with two instances per wavefront: -1 by batch size, 0 never, 1 always
-    // Two measured alternatives of the column pass, both opt-in (round 4; neither moves the 16-chunk pass by more than +-2 %:
-    // profiles/r04_colpass_ab.txt): the blocks of an instance take their full column tiles interleaved (hadi_pb_tiles), and
-    // hadi_pass_b2 -- part of the next tile prefetched into LDS -- instead of hadi_pass_b1 for European sweeps of 9 .. 16 chunks
-    int tile_il = 0;
-    int col_prefetch = 0;
-    int cs_strips = 1;       // Craig-Sneyd row passes on the barrier-free strips where the plan chose strips (0: shared ring, as before round 4)
-    int streams = 0;       // hadi_set_tuning "streams": 0 automatic (hadi_plan_row_idle), 1 one stream, 2 two streams side by side
+    HadiHandleTuning t;  // the tuning words (hadi_set_tuning; csrc/hadi_route.h)
     hipStream_t stream2 = nullptr;                 // the second stream of a two-stream sweep
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;
     int last_nsub = 1;
-    HadiTuning tune;    // kernel-selection overrides (hadi_set_tuning)
     hipEvent_t wait_ev = nullptr;  // hadi_wait_stream
     DevBuf lm31;
     std::string last_path;  // which kernels the last sweep ran (hadi_describe_last_sweep)
@@ -89,14 +73,9 @@ struct Ctx {
     char *pin = nullptr;
     size_t pin_cap = 0, pin_used = 0, pin_want = 0;
     int pin_dirty = 0;  // copies out of the arena may be in flight (cleared by the stream synchronisation that ends a call)
-    int debug_fault = 0;  // test hook (hadi_set_tuning "debug_fault"): HADI_DEBUG_* bits handed to the sweep kernels
-    // instance-resident launch (hadi_team_kernel): -1 automatic, 0 never, 1 whenever the shape allows it; team_failed is set
-    // when a team could not form or a team barrier timed out once on this handle (the automatic choice then stays away)
-    int team_launch = -1, team_failed = 0;
+    int team_failed = 0;  // a team (hadi_team_kernel) could not form or a team barrier timed out once on this handle: the automatic
+                          // choice then stays away (hadi_set_tuning "team_launch" clears it)
     DevBuf team;
-    // resident sweep (hadi_sweep_resident: both passes of every step in one launch, one block per instance): -1 automatic, 0 never,
-    // 1 wherever the sub-batch is eligible (run_sweep)
-    int resident_sweep = -1;
 };
 
 // Every GPU entry point runs on the handle's device whatever the caller's current device is (a torch rank that
@@ -258,100 +237,31 @@ hipError_t raise_lds_limit(K kernel) {
     return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
-// ---- run_sweep, part 1: how the batch is cut ---------------------------------------------------------------------------
-struct SubBatch { int off, cnt; HadiPlan pl; int lane; };  // lane: 0 = the handle's stream, 1 = its second stream
-struct BatchPlan {
-    std::vector<SubBatch> subs;
-    bool two_streams = false;
-    int fork_before = 0;  // the second stream forks off right before this sub-batch is enqueued
+// ---- run_sweep: plan and route (csrc/hadi_route.h), grow buffers, stage inputs, then one whole-loop launch or the time loop ----
+// Everything the steps below share.  The route is a pure function of `in`; `amp` is the one thing the device decides.
+struct Sweep {
+    const SweepDesc &d;
+    HadiRouteIn in;
+    HadiRoute r;
+    size_t tot = 0, st = 0;      // the packed state of the whole batch: elements, and bytes as fp64
+    std::vector<char> div_step;  // step -> somebody pays a dividend at its start
+    std::vector<int> snap_q;     // step -> snapshot index of a ladder call, or -1
+    int flag_stride = 0;         // dividend table: one shared row (0) or a row of Nmax flags per instance
+    bool amp = false;            // American sweeps in the P representation (hadi_row_step, AMER == 2)
+    HadiSweepArgs a, av;         // whole-batch arguments; Craig-Sneyd: the predictor's column pass writes V (= Y2), the
+                                 // corrector's row pass reads V (av.U)
 };
-// Sub-batches (whole rounds of one instance per CU + the remainder) and the one-or-two-streams decision.  `pl` is the plan of
-// the whole batch on entry and the plan the caller sees (layout, table sizes) on exit.
-int plan_batches(Ctx *c, const SweepDesc &d, HadiPlan &pl, int state_bytes, bool seq_shape, BatchPlan &bp) {
-    std::vector<SubBatch> &subs = bp.subs;
-    bool &two_streams = bp.two_streams;
-    int &fork_before = bp.fork_before;
-    // Large batches on grids where ONE round of the one-block-per-CU kernels (cu_count instances) already moves more than
-    // the 256 MB memory-side cache holds: the two passes of a step then re-use each other's data only while the batch is
-    // one round deep (measured at 512x256: 512 instances at once ran the column pass 6 % slower per instance than 256;
-    // 384 at once: 0.188 + 0.205 ms per step against 0.173 + 0.177 as 256 + 128).  Instances are independent, so the time
-    // loop runs sub-batch by sub-batch -- whole rounds of cu_count instances plus the remainder (a remainder below a
-    // quarter round rides with the last full round) -- each with the launch geometry of its own size.
-    // (the strip kernels scale the A1 action by (1 - theta) / theta and keep the s-convection weights multiplied by
-    // theta dt (r_d - r_f): hadi_strip_step)
-    const bool no_strips = !(d.theta > 0.0) || d.r_d == d.r_f;
-    auto plan_for = [&](int cnt, HadiPlan *q) {
-        if (hadi_make_plan(d.m1, d.m2, cnt, 8 * c->cu_count, q, c->tune, state_bytes)) return 1;
-        if (no_strips) q->use_strip = 0;
-        return 0;
-    };
-    if (no_strips) pl.use_strip = 0;
-    if (d.scheme == HADI_SCHEME_DOUGLAS && !d.debug && c->sub_batch && d.n > c->cu_count &&
-        2ll * c->cu_count * pl.L.inst_stride * (long long)state_bytes >= (256ll << 20)) {  // (bytes the sweep streams: 4 per element with the fp32 state)
-        const int cu = c->cu_count, full = d.n / cu, rem = d.n - full * cu;
-        for (int k = 0; k < full; k++) subs.push_back(SubBatch{k * cu, cu, pl, 0});
-        if (rem >= cu / 4) subs.push_back(SubBatch{full * cu, rem, pl, 0});
-        else subs.back().cnt += rem;
-        for (auto &sbt : subs)
-            if (plan_for(sbt.cnt, &sbt.pl)) return fail(c, HADI_ERR_UNSUPPORTED, "plan failed");
-        pl = subs[0].pl;  // (what the caller sees: layout and table sizes are the same for every sub-batch)
-    } else {
-        subs.push_back(SubBatch{0, d.n, pl, 0});
-    }
-    // Two streams.  Forced (hadi_set_tuning "streams" = 2): the sub-batches alternate between the two streams from the start; a
-    // batch that is one sub-batch is cut in two halves for it.  Automatic ("streams" = 0, the default): the LAST sub-batch --
-    // the whole batch, or the remainder behind the full rounds -- is cut in two halves that run side by side when its row
-    // pass would leave a partial round of CUs idle (hadi_plan_row_idle); the full rounds before it run on one stream.
-    // Instances are independent and the two passes of a step stay ordered within their own stream.
-    const bool streams_ok = d.scheme == HADI_SCHEME_DOUGLAS && !d.debug && !c->profiling && d.n >= 2 && !seq_shape;
-    auto split_last = [&]() -> int {
-        const SubBatch last = subs.back();
-        const int h0 = (last.cnt + 1) / 2;
-        subs.pop_back();
-        subs.push_back(SubBatch{last.off, h0, last.pl, 0});
-        subs.push_back(SubBatch{last.off + h0, last.cnt - h0, last.pl, 1});
-        for (size_t k = subs.size() - 2; k < subs.size(); k++)
-            if (plan_for(subs[k].cnt, &subs[k].pl)) return 1;
-        return 0;
-    };
-    if (streams_ok && c->streams == 2) {
-        if (subs.size() == 1) {
-            if (split_last()) return fail(c, HADI_ERR_UNSUPPORTED, "plan failed");
-        } else {
-            for (size_t k = 0; k < subs.size(); k++) subs[k].lane = (int)(k & 1);
-        }
-        two_streams = true;
-        fork_before = 0;
-    } else if (streams_ok && c->streams == 0 && subs.back().cnt >= 2 &&
-               hadi_plan_row_idle(subs.back().pl, subs.back().cnt, c->cu_count) >= HADI_TWO_STREAM_IDLE) {
-        const SubBatch whole = subs.back();
-        if (split_last()) return fail(c, HADI_ERR_UNSUPPORTED, "plan failed");
-        if (subs[subs.size() - 2].pl.use_strip && subs.back().pl.use_strip) {
-            two_streams = true;
-            fork_before = (int)subs.size() - 2;
-        } else {  // (a half that falls back to the shared ring: the rounds argument does not carry over -- one stream)
-            subs.pop_back();
-            subs.back() = whole;
-        }
-    }
-    // Several sub-batches (whole rounds plus a remainder) and no half-cut above: they alternate between the two streams, as in the
-    // forced mode -- the remainder's launches run in the shadow of a full round's instead of behind it.  Measured on strips
-    // (profiles/r04_stream_big.txt): 512x256 x320 +5.1 %, x384 +3.2 %, American x320 / x384 +5.8 / +5.9 %, and within +-1 % from
-    // two full rounds on (x512 +0.7 %, x768 -0.3 %, x1024 +0.8 %): never a loss, deterministic per (shape, batch size).
-    if (streams_ok && c->streams == 0 && !two_streams && subs.size() >= 2) {
-        bool strips = true;
-        for (auto &sb : subs) strips = strips && sb.pl.use_strip;
-        if (strips) {
-            for (size_t k = 0; k < subs.size(); k++) subs[k].lane = (int)(k & 1);
-            two_streams = true;
-            fork_before = 0;
-        }
-    }
-    if (two_streams) pl = subs[0].pl;
-    return HADI_OK;
+
+HadiRouteIn route_in(const Ctx *c, const SweepDesc &d) {
+    HadiRouteIn in;
+    in.cu_count = c->cu_count;
+    in.n = d.n; in.m1 = d.m1; in.m2 = d.m2; in.variant = d.variant; in.scheme = d.scheme; in.prec = d.prec;
+    in.theta = d.theta; in.rates_equal = d.r_d == d.r_f;
+    in.debug = d.debug; in.profiling = c->profiling != 0; in.n_snap = d.n_snap; in.dividends = d.num_div > 0;
+    in.uniform_steps = d.uniform_steps; in.team_failed = c->team_failed != 0; in.t = c->t;
+    return in;
 }
 
-// ---- run_sweep, part 2: which kernel runs a pass -----------------------------------------------------------------------
 // The choice, the launch geometry and the words are hadi_dispatch.h's (the rules: DESIGN.md section 4.1); this launches it.
 int launch_pass(Ctx *c, const HadiSel &sel, hipStream_t q, const HadiSweepArgs &ar, int nstep) {
     if (!sel.k) return fail(c, HADI_ERR_INTERNAL, "no kernel for this pass (grid %dx%d)", ar.L.m1, ar.L.m2);
@@ -359,129 +269,76 @@ int launch_pass(Ctx *c, const HadiSel &sel, hipStream_t q, const HadiSweepArgs &
     return HADI_OK;
 }
 
-// ---- run_sweep, part 3: the kernels of the streaming path in words (hadi_describe_last_sweep) ------------------------
-std::string describe_streaming_path(const HadiPassCtx &pc, const BatchPlan &bp) {
-    const std::vector<SubBatch> &subs = bp.subs;
-    const int nsub = (int)subs.size();
-    const bool two_streams = bp.two_streams;
-    const int fork_before = bp.fork_before;
-    char buf[384];
-    hadi_describe_passes(pc, buf, sizeof buf);
-    std::string last_path = buf;
-    if (nsub > 1) {
-        bool same = true;
-        for (auto &sbt : subs) same = same && sbt.cnt == subs[0].cnt;
-        if (same) last_path += "; " + std::to_string(nsub) + " sub-batches of " + std::to_string(subs[0].cnt) + " instances";
-        else {
-            last_path += "; " + std::to_string(nsub) + " sub-batches of";
-            for (auto &sbt : subs) last_path += " " + std::to_string(sbt.cnt);
-            last_path += " instances (each with the geometry of its own size)";
-        }
-        if (two_streams && fork_before > 0) last_path += ", the last two side by side on two streams";
-        else if (two_streams) last_path += ", side by side on two streams";
-    }
-    return last_path;
-}
-
-int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
-    const int state_bytes = d.prec == HADI_STATE_FP32 ? 4 : 8;
-    if (hadi_make_plan(d.m1, d.m2, d.n, 8 * c->cu_count, &pl, c->tune, state_bytes))
-        return fail(c, HADI_ERR_UNSUPPORTED, "grid %dx%d not supported (need m1 >= 2, m2 >= 3 and (m1 + 16)(m2 + 1) < 2^28)", d.m1, d.m2);
-    const bool seq_shape = pl.row_seq || pl.col_seq;  // shapes beyond the streaming kernels: the sequential passes
-    if (seq_shape && (d.scheme != HADI_SCHEME_DOUGLAS || d.prec != HADI_STATE_FP64))
-        return fail(c, HADI_ERR_UNSUPPORTED, "grids with m1 > 1024 or m2 > %d run Douglas sweeps with the fp64 state only", HADI_MAX_P * HADI_LC - 1);
-    BatchPlan bp;
-    {
-        const int rcp = plan_batches(c, d, pl, state_bytes, seq_shape, bp);
-        if (rcp) return rcp;
-    }
-    const std::vector<SubBatch> &subs = bp.subs;
-    const bool two_streams = bp.two_streams;
-    const int fork_before = bp.fork_before;
-    const int nsub = (int)subs.size();
-    const HadiLayout &L = pl.L;
-    const bool american = d.variant == HADI_AM || d.variant == HADI_AM_DIV;
-    const bool dividend = d.variant == HADI_DIV || d.variant == HADI_AM_DIV;
-    const size_t st = (size_t)L.inst_stride * d.n * sizeof(double);
+int grow_buffers(Ctx *c, Sweep &w) {
+    const SweepDesc &d = w.d;
+    const HadiRoute &r = w.r;
+    const HadiPlan &pl = r.pl;
+    const size_t st = w.st, n = d.n;
     int rc;
-    if ((rc = ensure(c, c->U, st))) return rc;
-    if ((rc = ensure(c, c->Y, st))) return rc;
-    if (american) {
-        if ((rc = ensure(c, c->LAM, st))) return rc;
-        if ((rc = ensure(c, c->U0, st))) return rc;
-    }
-    if (dividend && (rc = ensure(c, c->UT, st))) return rc;
-    const bool cs = d.scheme != HADI_SCHEME_DOUGLAS;  // a predictor-corrector scheme (CS, MCS, HV): R1 / C2 carry-over, V = Y2
-    const bool f32 = d.prec == HADI_STATE_FP32;  // European Douglas (with or without dividends) only (validated)
-    if (f32 && ((rc = ensure(c, c->Uf, st / 2)) || (rc = ensure(c, c->Yf, st / 2)))) return rc;
-    // (a caller who pins the streaming kernels' geometry -- hadi_set_tuning "strip", "row_tile", "col_groups", "strip_blocks" --
-    // gets those kernels: no whole-loop kernel is chosen automatically)
-    const bool pinned = c->tune.strip >= 0 || c->tune.row_tile > 0 || c->tune.col_groups > 0 || c->tune.strip_blocks > 0;
-    // Predictor-corrector sweeps of grids that fit in LDS (m1 <= 128, m2 <= 32): the whole time loop in one launch, one
-    // wavefront per instance (hadi_small_sch_kernel).  "small_sch" = 1: wherever admitted; 0: never; -1 (default): batches of
-    // more instances than CUs (the rule of "small_seq") on grids of which a CU's LDS holds at least three instances, unless the
-    // caller pinned the streaming geometry or "cs_strips" = 0.  Measured (profiles/r08_small_sch_ab.txt, MCS / HV, ms per step,
-    // streaming -> this kernel): 50x25 (three per CU) x257 0.040 -> 0.020, x500 0.057 -> 0.021, x1024 0.082 -> 0.041, x3000
-    // 0.210 -> 0.100; 100x30 (one per CU: one wavefront on each CU) x500 0.064 -> 0.081, so such grids stay streaming.
-    const size_t smem_sch = hadi_small_sch_smem(L);
-    const bool small_sch = cs && c->use_small && !c->profiling && !d.debug && !c->debug_fault && !f32 && d.variant == HADI_EU &&
-                           !seq_shape && hadi_small_sch_admits(L) &&
-                           (c->small_sch > 0 || (c->small_sch < 0 && d.n > c->cu_count && 3 * smem_sch <= (size_t)160 * 1024 &&
-                                                 !pinned && c->cs_strips != 0));
-    if (cs && !small_sch && ((rc = ensure(c, c->V, st)) || (rc = ensure(c, c->R1, st)) || (rc = ensure(c, c->C2, st)))) return rc;
-    if (pl.row_seq && (rc = ensure(c, c->R1, st))) return rc;  // (hadi_pass_a_seq parks the Thomas multipliers there)
-    const bool pair_tab = L.G == 2 && !cs && !pl.row_seq;  // paired strips (Douglas steps) take the pairs' coupling column from a table built once per solve
-    if (pair_tab && (rc = ensure(c, c->rs_tab, (size_t)d.n * L.nrows * 128 * 8))) return rc;
-    const size_t n = d.n;
-    if ((rc = ensure(c, c->scoef, pl.n_scoef * n * 8))) return rc;
-    if ((rc = ensure(c, c->b2row, pl.n_b2row * n * 8))) return rc;
-    if ((rc = ensure(c, c->rowc, pl.n_rowc * n * 8))) return rc;
-    if ((rc = ensure(c, c->a2i, pl.n_a2i * n * 8))) return rc;
-    if ((rc = ensure(c, c->pb, pl.n_pb * n * 8))) return rc;
-    if ((rc = ensure(c, c->rinv, pl.n_rinv * n * 8))) return rc;
-    if ((rc = ensure(c, c->rwork, pl.n_rwork * n * 8))) return rc;
-    if ((rc = ensure(c, c->ipar, sizeof(HadiInstPar) * n))) return rc;
-    if ((rc = ensure(c, c->par8, 8 * 8 * n))) return rc;
-    // A ladder call: its buffers are grown here, before anything is captured (a grown buffer drops the graph cache); its American
-    // sweeps run on the explicit (U, lambda_bar) pair (P does not hold U between steps), and it never takes the resident sweep or
-    // the team launch -- those sub-batches run the streaming kernels, as under profiling.
-    const bool ladder = d.n_snap > 0 && !d.debug;
-    std::vector<int> snap_q(d.Nmax + 2, -1);  // step -> snapshot index
-    if (ladder) {
+    if ((rc = ensure(c, c->U, st)) || (rc = ensure(c, c->Y, st))) return rc;
+    if (r.need_lam_u0 && ((rc = ensure(c, c->LAM, st)) || (rc = ensure(c, c->U0, st)))) return rc;
+    if (r.need_ut && (rc = ensure(c, c->UT, st))) return rc;
+    if (r.need_f32 && ((rc = ensure(c, c->Uf, st / 2)) || (rc = ensure(c, c->Yf, st / 2)))) return rc;
+    if (r.need_v_r1_c2 && ((rc = ensure(c, c->V, st)) || (rc = ensure(c, c->R1, st)) || (rc = ensure(c, c->C2, st)))) return rc;
+    if (r.need_r1 && (rc = ensure(c, c->R1, st))) return rc;
+    if (r.pair_tab && (rc = ensure(c, c->rs_tab, n * pl.L.nrows * 128 * 8))) return rc;
+    if ((rc = ensure(c, c->scoef, pl.n_scoef * n * 8)) || (rc = ensure(c, c->b2row, pl.n_b2row * n * 8)) ||
+        (rc = ensure(c, c->rowc, pl.n_rowc * n * 8)) || (rc = ensure(c, c->a2i, pl.n_a2i * n * 8)) ||
+        (rc = ensure(c, c->pb, pl.n_pb * n * 8)) || (rc = ensure(c, c->rinv, pl.n_rinv * n * 8)) ||
+        (rc = ensure(c, c->rwork, pl.n_rwork * n * 8)) || (rc = ensure(c, c->ipar, sizeof(HadiInstPar) * n)) ||
+        (rc = ensure(c, c->par8, 8 * 8 * n)))
+        return rc;
+    // A ladder call: its buffers are grown here, before anything is captured (a grown buffer drops the graph cache).
+    w.snap_q.assign(d.Nmax + 2, -1);
+    if (r.ladder) {
         if ((rc = ensure(c, c->snap_steps, sizeof(int) * d.n_snap)) || (rc = ensure(c, c->snap_node, sizeof(int) * n)) ||
             (rc = ensure(c, c->snap_out, 8 * n * d.n_snap)) || (rc = ensure(c, c->status, sizeof(int) * n)))
             return rc;
-        for (int q = 0; q < d.n_snap; q++) snap_q[d.snap_steps[q]] = q;
+        for (int q = 0; q < d.n_snap; q++) w.snap_q[d.snap_steps[q]] = q;
     }
+    return HADI_OK;
+}
 
+// Discrete dividends: host-built table "which dividend does instance k pay at the start of step n" (one shared
+// row when the batch has a single (N, delta_t)), plus the set of steps where anybody pays.
+int stage_dividends(Ctx *c, Sweep &w) {
+    const SweepDesc &d = w.d;
+    w.div_step.assign(d.Nmax + 1, 0);
+    w.flag_stride = d.uniform_steps ? 0 : d.Nmax;
+    if (!w.r.have_div) return HADI_OK;
+    const int rows = d.uniform_steps ? 1 : d.n;
+    std::vector<int> div_flags((size_t)rows * d.Nmax);
+    for (int k = 0; k < rows; k++) {
+        const double dt = d.par8[(size_t)k * 8 + 4];
+        const int N = (int)d.par8[(size_t)k * 8 + 5];
+        int *f = div_flags.data() + (size_t)k * d.Nmax;
+        hadi_dividend_steps(N, dt, d.num_div, d.div_dates, f, d.Nmax);
+        for (int q = 0; q < d.Nmax; q++)
+            if (f[q] >= 0) w.div_step[q + 1] = 1;
+    }
+    int rc;
+    if ((rc = ensure(c, c->div_flag, div_flags.size() * sizeof(int))) || (rc = ensure(c, c->div_amt, d.num_div * 8)) ||
+        (rc = ensure(c, c->div_pct, d.num_div * 8)))
+        return rc;
+    if ((rc = stage_to_device(c, c->div_flag.p, div_flags.data(), div_flags.size() * sizeof(int))) ||
+        (rc = stage_to_device(c, c->div_amt.p, d.div_amounts, (size_t)d.num_div * 8)) ||
+        (rc = stage_to_device(c, c->div_pct.p, d.div_pcts, (size_t)d.num_div * 8)))
+        return rc;
+    return HADI_OK;
+}
+
+// Parameters and dividend tables to the device, the operator tables (setup), the ladder's price nodes (locate), the packed
+// state and, for American sweeps, the payoff and its shape -- which decides w.amp.
+int stage_inputs(Ctx *c, Sweep &w) {
+    const SweepDesc &d = w.d;
+    const HadiRoute &r = w.r;
+    const HadiLayout &L = r.pl.L;
+    const size_t n = d.n, tot = w.tot, st = w.st;
     hipStream_t s = c->stream;
+    int rc;
     HIP_TRY(c, hipEventRecord(c->ev[0], s));
     if ((rc = stage_to_device(c, c->par8.p, d.par8.data(), 8 * 8 * n))) return rc;
-    // Discrete dividends: host-built table "which dividend does instance k pay at the start of step n" (one shared
-    // row when the batch has a single (N, delta_t)), plus the set of steps where anybody pays.
-    std::vector<int> div_flags;
-    std::vector<char> div_step(d.Nmax + 1, 0);
-    const int flag_stride = d.uniform_steps ? 0 : d.Nmax;
-    const bool have_div = dividend && d.num_div > 0 && !d.debug;  // (diagnostics take p->U as the state the pass starts from)
-    if (have_div) {
-        const int rows = d.uniform_steps ? 1 : d.n;
-        div_flags.resize((size_t)rows * d.Nmax);
-        for (int k = 0; k < rows; k++) {
-            const double dt = d.par8[(size_t)k * 8 + 4];
-            const int N = (int)d.par8[(size_t)k * 8 + 5];
-            int *f = div_flags.data() + (size_t)k * d.Nmax;
-            hadi_dividend_steps(N, dt, d.num_div, d.div_dates, f, d.Nmax);
-            for (int q = 0; q < d.Nmax; q++)
-                if (f[q] >= 0) div_step[q + 1] = 1;
-        }
-        if ((rc = ensure(c, c->div_flag, div_flags.size() * sizeof(int))) || (rc = ensure(c, c->div_amt, d.num_div * 8)) ||
-            (rc = ensure(c, c->div_pct, d.num_div * 8)))
-            return rc;
-        if ((rc = stage_to_device(c, c->div_flag.p, div_flags.data(), div_flags.size() * sizeof(int))) ||
-            (rc = stage_to_device(c, c->div_amt.p, d.div_amounts, (size_t)d.num_div * 8)) ||
-            (rc = stage_to_device(c, c->div_pct.p, d.div_pcts, (size_t)d.num_div * 8)))
-            return rc;
-    }
+    if ((rc = stage_dividends(c, w))) return rc;
     // identity padding rows of Y must read as zeros in the column pass (the row pass never writes them)
     HIP_TRY(c, hipMemsetAsync(c->Y.p, 0, st, s));
 
@@ -494,15 +351,14 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     sa.a2i = ptr<double>(c->a2i); sa.pb = ptr<double>(c->pb); sa.rinv = ptr<double>(c->rinv);
     sa.rwork = ptr<double>(c->rwork); sa.ipar = ptr<HadiInstPar>(c->ipar);
     hipLaunchKernelGGL(hadi_setup_kernel, dim3(d.n), dim3(256), 0, s, sa);
-    if (ladder) {
+    if (r.ladder) {
         if ((rc = stage_to_device(c, c->snap_steps.p, d.snap_steps, sizeof(int) * d.n_snap))) return rc;
         hipLaunchKernelGGL(hadi_locate_kernel, dim3((d.n + 63) / 64), dim3(64), 0, s, L, d.n, d.d_vec_s, d.d_vec_v, d.S_0, d.d_v0_i, d.V_0,
                            ptr<int>(c->snap_node), ptr<int>(c->status));
     }
 
-    const size_t tot = (size_t)L.inst_stride * d.n;
     hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src, d.d_natU, ptr<double>(c->U));
-    if (american) {
+    if (r.american) {
         hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src,
                            d.d_natU0 ? d.d_natU0 : d.d_natU, ptr<double>(c->U0));
         HIP_TRY(c, hipMemsetAsync(c->LAM.p, 0, st, s));  // lambda_bar <- 0, device_solver.hpp:310-313
@@ -510,399 +366,401 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
         HIP_TRY(c, hipMemsetAsync(c->pay_mis.p, 0, sizeof(int) * n, s));
         hipLaunchKernelGGL(hadi_payoff_shape_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, ptr<double>(c->U0), ptr<int>(c->pay_mis));
     }
-    // American in the P representation (hadi_row_step, AMER == 2): every payoff of the batch must depend on s only.
-    // One small device-to-host copy per solve decides it.
-    bool amp = false;
-    const bool takes_small_path = c->use_small && !c->profiling && !cs && !f32 && !d.debug && (american ? pl.smem_small_am : pl.smem_small_eu) > 0;
-    if (american && c->use_amp && !cs && !takes_small_path && !d.debug && !seq_shape && !ladder) {
+    // American in the P representation: every payoff of the batch must depend on s only.  One small device-to-host copy per
+    // solve decides it.
+    w.amp = false;
+    if (r.read_payoff_shape) {
         std::vector<int> mis(d.n);
         HIP_TRY(c, hipMemcpyAsync(mis.data(), c->pay_mis.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        amp = true;
-        for (int k = 0; k < d.n; k++) amp = amp && mis[k] == 0;
+        w.amp = true;
+        for (int k = 0; k < d.n; k++) w.amp = w.amp && mis[k] == 0;
     }
     HIP_TRY(c, hipGetLastError());
-
-    if (f32) {  // round the packed state to fp32; Y's identity padding rows must read as zeros
+    if (r.f32) {  // round the packed state to fp32; Y's identity padding rows must read as zeros
         hipLaunchKernelGGL(hadi_narrow_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, ptr<double>(c->U), ptr<float>(c->Uf), tot);
         HIP_TRY(c, hipMemsetAsync(c->Yf.p, 0, st / 2, s));
     }
-    HadiSweepArgs a;
+    return HADI_OK;
+}
+
+// The whole-batch argument blocks of the sweep kernels.
+void sweep_args(Ctx *c, Sweep &w) {
+    const HadiRoute &r = w.r;
+    const HadiPlan &pl = r.pl;
+    HadiSweepArgs &a = w.a;
     a.U = ptr<double>(c->U); a.Y = ptr<double>(c->Y);
-    if (f32) {  // the kernels instantiated for float reinterpret these two
+    if (r.f32) {  // the kernels instantiated for float reinterpret these two
         a.U = reinterpret_cast<double *>(c->Uf.p);
         a.Y = reinterpret_cast<double *>(c->Yf.p);
     }
-    a.LAM = american ? ptr<double>(c->LAM) : nullptr;
-    a.U0 = american ? ptr<double>(c->U0) : nullptr;
-    a.pay_mis = american ? ptr<int>(c->pay_mis) : nullptr;
+    a.LAM = r.american ? ptr<double>(c->LAM) : nullptr;
+    a.U0 = r.american ? ptr<double>(c->U0) : nullptr;
+    a.pay_mis = r.american ? ptr<int>(c->pay_mis) : nullptr;
     a.scoef = ptr<double>(c->scoef); a.b2row = ptr<double>(c->b2row); a.rowc = ptr<double>(c->rowc);
     a.pb = ptr<double>(c->pb); a.rinv = ptr<double>(c->rinv); a.ipar = ptr<HadiInstPar>(c->ipar);
-    a.L = L; a.n_inst = d.n; a.R = pl.R; a.ntiles = pl.ntiles; a.ctiles = pl.ctiles; a.btpw = pl.btpw; a.bgroups = pl.bgroups;
-    a.american = american ? 1 : 0; a.pos_m1 = pl.pos_m1;
-    a.tile_il = c->tile_il;
+    a.L = pl.L; a.n_inst = w.d.n; a.R = pl.R; a.ntiles = pl.ntiles; a.ctiles = pl.ctiles; a.btpw = pl.btpw; a.bgroups = pl.bgroups;
+    a.american = r.american ? 1 : 0; a.pos_m1 = pl.pos_m1;
+    a.tile_il = c->t.tile_il;
     a.RS = pl.RS; a.sblocks = pl.sblocks;
-    a.err = c->err_dev; a.debug = c->debug_fault;
-    a.R1 = ((cs && !small_sch) || pl.row_seq) ? ptr<double>(c->R1) : nullptr;  // (hadi_small_sch_kernel keeps V, R1, C2 in LDS)
-    a.C2 = (cs && !small_sch) ? ptr<double>(c->C2) : nullptr;
-    a.rs_tab = pair_tab ? ptr<double>(c->rs_tab) : nullptr;
-    // Craig-Sneyd: the predictor's column pass writes V (= Y2), the corrector's row pass reads V
-    HadiSweepArgs av = a;
-    if (cs && !small_sch) av.U = ptr<double>(c->V);
+    a.err = c->err_dev; a.debug = c->t.debug_fault;
+    a.R1 = (r.need_v_r1_c2 || r.need_r1) ? ptr<double>(c->R1) : nullptr;
+    a.C2 = r.need_v_r1_c2 ? ptr<double>(c->C2) : nullptr;
+    a.rs_tab = r.pair_tab ? ptr<double>(c->rs_tab) : nullptr;
+    w.av = a;
+    if (r.need_v_r1_c2) w.av.U = ptr<double>(c->V);
+}
 
-    const bool prof = c->profiling != 0 && !d.debug;
-    if (prof) {
-        const size_t need = (size_t)4 * d.Nmax * nsub;
+// ---- one launch for the whole time loop ----------------------------------------------------------------------------------
+// The small-grid kernels' second argument block: dividend tables and, for batches of mixed maturities, the dispatch order.
+int small_args(Ctx *c, const Sweep &w, HadiSmallArgs &sm) {
+    const SweepDesc &d = w.d;
+    int rc;
+    sm.div_flag = nullptr; sm.div_amounts = nullptr; sm.div_pcts = nullptr; sm.vec_s = d.d_vec_s; sm.Nmax = d.Nmax;
+    sm.order = nullptr;
+    if (!d.uniform_steps) {  // longest-processing-time-first dispatch order
+        std::vector<int> order(d.n);
+        for (int k = 0; k < d.n; k++) order[k] = k;
+        std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+            return d.par8[(size_t)x * 8 + 5] > d.par8[(size_t)y * 8 + 5];
+        });
+        if ((rc = ensure(c, c->order, sizeof(int) * d.n))) return rc;
+        if ((rc = stage_to_device(c, c->order.p, order.data(), sizeof(int) * d.n))) return rc;
+        sm.order = ptr<int>(c->order);
+    }
+    sm.flag_stride = w.flag_stride;
+    if (w.r.have_div) {
+        sm.div_flag = ptr<int>(c->div_flag); sm.div_amounts = ptr<double>(c->div_amt); sm.div_pcts = ptr<double>(c->div_pct);
+    }
+    if (w.r.ladder) {
+        sm.snap_steps = ptr<int>(c->snap_steps); sm.n_snap = d.n_snap;
+        sm.snap_node = ptr<int>(c->snap_node); sm.snap_out = ptr<double>(c->snap_out);
+    }
+    return HADI_OK;
+}
+
+// Small grids: the whole instance fits in LDS (hadi_small_sch_kernel, hadi_small_kernel, hadi_small_seq_kernel, hadi_small_seq2_kernel).
+int run_small(Ctx *c, Sweep &w) {
+    const SweepDesc &d = w.d;
+    const HadiLayout &L = w.r.pl.L;
+    HadiSel sel{nullptr, (unsigned)d.n, 64, 0};
+    HadiLoopFn fn;
+    if (w.r.kind == HADI_ROUTE_SMALL_SCH) {
+        fn = hadi_small_sch_fn(L.B, hadi_route_sch(d.scheme));
+        if (!fn) return fail(c, HADI_ERR_INTERNAL, "no small-grid kernel of scheme %d for grid %dx%d", d.scheme, d.m1, d.m2);
+        sel.smem = hadi_small_sch_smem(L);
+    } else {
+        sel = hadi_route_small_sel(w.r, d.n);
+        if (!sel.k) return fail(c, HADI_ERR_INTERNAL, "no small-grid kernel for grid %dx%d", d.m1, d.m2);
+        fn = sel.k->loop;
+    }
+    c->last_path = hadi_describe_route(w.r, w.in, false);
+    HadiSmallArgs sm;
+    const int rc = small_args(c, w, sm);
+    if (rc) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
+    hipLaunchKernelGGL(fn, dim3(sel.grid), dim3(sel.block), sel.smem, c->stream, w.a, sm);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[2], c->stream));
+    return HADI_OK;
+}
+
+// Instance-resident launch (hadi_team_kernel), between the same two events.  Any failure of the team protocol is recorded by
+// the kernel and checked here; the batch is then packed again and *fell_back sends the caller on to the streaming path.
+int run_team(Ctx *c, Sweep &w, bool *fell_back) {
+    const SweepDesc &d = w.d;
+    const HadiLayout &L = w.r.pl.L;
+    hipStream_t s = c->stream;
+    const bool have_div = w.r.have_div;
+    int rc;
+    HIP_TRY(c, hipEventRecord(c->ev[1], s));
+    if ((rc = ensure(c, c->team, 512 * sizeof(int)))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->team.p, 0, 512 * sizeof(int), s));
+    HadiTeamArgs ta;
+    ta.form = ptr<int>(c->team); ta.bar = ptr<int>(c->team) + 64; ta.nb = c->cu_count / 8; ta.N = d.Nmax;
+    ta.div_flag = have_div ? ptr<int>(c->div_flag) : nullptr; ta.flag_stride = w.flag_stride;
+    ta.div_amounts = have_div ? ptr<double>(c->div_amt) : nullptr; ta.div_pcts = have_div ? ptr<double>(c->div_pct) : nullptr;
+    ta.vec_s = d.d_vec_s;
+    ta.stamps = reinterpret_cast<unsigned long long *>(ptr<int>(c->team) + 384);
+    const size_t smem = hadi_team_smem(L, have_div);
+    if (L.B == 8) hipLaunchKernelGGL((hadi_team_kernel<8>), dim3(c->cu_count), dim3(512), smem, s, w.a, ta);
+    else hipLaunchKernelGGL((hadi_team_kernel<4>), dim3(c->cu_count), dim3(512), smem, s, w.a, ta);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const int deverr = __atomic_exchange_n(c->err_host, 0, __ATOMIC_ACQ_REL);
+    if (!deverr) {
+        c->last_path = hadi_describe_route(w.r, w.in, w.amp, HADI_TEAM_RAN);
+        HIP_TRY(c, hipEventRecord(c->ev[2], s));
+        return HADI_OK;
+    }
+    if (deverr & ~HADI_DEVERR_TEAM) __atomic_fetch_or(c->err_host, deverr & ~HADI_DEVERR_TEAM, __ATOMIC_RELAXED);  // (not ours: keep it for finish_timing)
+    c->team_failed = 1;
+    // start again from the caller's initial condition on the streaming path
+    hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(w.tot)), dim3(256), 0, s, L, d.n, d.n_src, d.d_natU, ptr<double>(c->U));
+    HIP_TRY(c, hipMemsetAsync(c->Y.p, 0, w.st, s));
+    c->last_path = hadi_describe_route(w.r, w.in, w.amp, HADI_TEAM_FELL_BACK);
+    *fell_back = true;
+    return HADI_OK;
+}
+
+// ---- the time loop over the pass kernels ------------------------------------------------------------------------------------
+// The whole-batch arguments narrowed to the sub-batch of `cnt` instances from instance `o` on, with its own launch geometry.
+HadiSweepArgs sub_args(const Sweep &w, HadiSweepArgs x, int o, int cnt, const HadiPlan &sp) {
+    const HadiPlan &pl = w.r.pl;
+    const HadiLayout &L = pl.L;
+    x.n_inst = cnt; x.R = sp.R; x.ntiles = sp.ntiles; x.ctiles = sp.ctiles; x.btpw = sp.btpw; x.bgroups = sp.bgroups;
+    x.RS = sp.RS; x.sblocks = sp.sblocks;
+    const size_t so = (size_t)o * L.inst_stride;
+    if (w.r.f32) {
+        x.U = reinterpret_cast<double *>(reinterpret_cast<float *>(x.U) + so);
+        x.Y = reinterpret_cast<double *>(reinterpret_cast<float *>(x.Y) + so);
+    } else {
+        x.U += so;
+        x.Y += so;
+    }
+    if (x.LAM) x.LAM += so;
+    if (x.U0) x.U0 += so;
+    if (x.pay_mis) x.pay_mis += o;
+    if (x.R1) x.R1 += so;
+    if (x.C2) x.C2 += so;
+    if (x.rs_tab) x.rs_tab += (size_t)o * L.nrows * 128;
+    x.scoef += (size_t)o * pl.n_scoef; x.b2row += (size_t)o * pl.n_b2row; x.rowc += (size_t)o * pl.n_rowc;
+    x.pb += (size_t)o * pl.n_pb; x.rinv += (size_t)o * pl.n_rinv; x.ipar += o;
+    return x;
+}
+
+// Sub-batch `sb` through its whole time loop on stream q.
+int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
+    const SweepDesc &d = w.d;
+    const HadiRoute &r = w.r;
+    const HadiLayout &L = r.pl.L;
+    const HadiSubBatch &sub = r.bp.subs[sb];
+    const HadiPlan &sp = sub.pl;  // launch geometry of THIS sub-batch
+    const int o = sub.off, nsb = sub.cnt;
+    const bool cs = r.cs, f32 = r.f32, have_div = r.have_div, amp = w.amp;
+    const int n_first = d.debug ? d.debug_step : 1, n_last = d.debug ? d.debug_step : d.Nmax;
+    const size_t so = (size_t)o * L.inst_stride;
+    const HadiSweepArgs a = sub_args(w, w.a, o, nsb, sp), av = sub_args(w, w.av, o, nsb, sp);
+    const size_t tot = (size_t)L.inst_stride * nsb, st = tot * sizeof(double);  // the sub-batch's packed state
+    double *const Ub = ptr<double>(c->U) + so, *const LAMb = r.american ? ptr<double>(c->LAM) + so : nullptr;
+    double *const U0b = r.american ? ptr<double>(c->U0) + so : nullptr, *const UTb = r.dividend ? ptr<double>(c->UT) + so : nullptr;
+    const int ev0 = 4 * sb * d.Nmax;  // profiling events of this sub-batch
+    int rc;
+    if (r.pair_tab && sp.use_strip) {  // paired strips: the pairs' coupling column, once per solve (hadi_strip_step, RSTAB)
+        HadiSweepArgs at = a;
+        at.U = Ub;  // (any packed fp64 array: the table depends on the matrix only)
+        if ((rc = launch_pass(c, hadi_select_pair_table(sp), q, at, 1))) return rc;
+    }
+    if (r.resident[sb])  // the sub-batch's whole time loop in one launch (LDS: the strip rings; the column phase aliases them)
+        return launch_pass(c, hadi_select_resident(sp), q, a, n_last);
+    for (int nstep = n_first; nstep <= n_last; nstep++) {
+        // P representation: the first step (the caller's initial U need not dominate the payoff) and dividend steps
+        // (the jump acts on U alone) run on the explicit (U, lambda_bar) pair, converted on the way in and out
+        const bool xstep = amp && (nstep == 1 || (have_div && w.div_step[nstep]));
+        if (xstep && nstep > 1)
+            hipLaunchKernelGGL(hadi_am_materialise_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, nsb, a.ipar, U0b, Ub, LAMb, sp.pos_m1);
+        if (have_div && w.div_step[nstep]) {  // device_solver.hpp:426-517: U_temp <- U, U <- interpolated jump
+            if (f32)  // fp32 state: the jump works on the fp64 packed array -- widen, jump, round again (<= num_dividends steps)
+                hipLaunchKernelGGL(hadi_widen_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, reinterpret_cast<const float *>(a.U), Ub, tot);
+            HIP_TRY(c, hipMemcpyAsync(UTb, Ub, st, hipMemcpyDeviceToDevice, q));
+            const size_t npts = (size_t)nsb * L.nrows * (L.m1 + 1);
+            hipLaunchKernelGGL(hadi_dividend_kernel, dim3(grid1d(npts)), dim3(256), 0, q, L, nsb, a.ipar,
+                               d.d_vec_s + (size_t)o * (L.m1 + 1), UTb, Ub, ptr<int>(c->div_flag) + (size_t)o * w.flag_stride,
+                               w.flag_stride, nstep, ptr<double>(c->div_amt), ptr<double>(c->div_pct));
+            if (f32)
+                hipLaunchKernelGGL(hadi_narrow_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, Ub, reinterpret_cast<float *>(a.U), tot);
+        }
+        hipEvent_t *const kev = r.prof ? &c->kev[ev0 + 4 * (nstep - 1)] : nullptr;
+        if (kev) HIP_TRY(c, hipEventRecord(kev[0], q));
+        const HadiPassCtx pc{sp, nsb, r.american, amp, xstep, f32, d.scheme, c->t.cs_strips, c->t.col_prefetch};
+        const HadiSel col = hadi_select_col_pass(pc);
+        if (d.debug == 2) {  // diagnostics: one column solve of the packed input (moved to Y), nothing else
+            HIP_TRY(c, hipMemcpyAsync(a.Y, a.U, f32 ? st / 2 : st, hipMemcpyDeviceToDevice, q));
+            if ((rc = launch_pass(c, col, q, a, nstep))) return rc;
+            break;
+        }
+        if ((rc = launch_pass(c, hadi_select_row_pass(pc, cs ? 1 : 0), q, a, nstep))) return rc;
+        if (d.debug == 1) break;  // diagnostics: Y now holds the right-hand side of the A2 solve
+        if (kev) {
+            HIP_TRY(c, hipEventRecord(kev[1], q));
+            HIP_TRY(c, hipEventRecord(kev[2], q));
+        }
+        if ((rc = launch_pass(c, col, q, cs ? av : a, nstep))) return rc;
+        if (kev) HIP_TRY(c, hipEventRecord(kev[3], q));
+        if (cs) {  // corrector (profiling events cover the predictor's two passes only)
+            if ((rc = launch_pass(c, hadi_select_row_pass(pc, 2), q, av, nstep)) || (rc = launch_pass(c, col, q, a, nstep))) return rc;
+        }
+        if (r.ladder && w.snap_q[nstep] >= 0)  // (U is explicit here: a ladder call never runs in the P representation)
+            hipLaunchKernelGGL(hadi_snap_kernel, dim3((nsb + 63) / 64), dim3(64), 0, q, L, nsb, Ub, ptr<int>(c->snap_node) + o,
+                               ptr<double>(c->snap_out) + (size_t)o * d.n_snap, d.n_snap, w.snap_q[nstep]);
+        if (xstep)
+            hipLaunchKernelGGL(hadi_am_dematerialise_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, nsb, a.ipar, U0b, Ub, LAMb);
+    }
+    if (amp)  // explicit U and lambda_bar for the outputs
+        hipLaunchKernelGGL(hadi_am_materialise_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, nsb, a.ipar, U0b, Ub, LAMb, sp.pos_m1);
+    return HADI_OK;
+}
+
+// The whole time loop as a function of the stream, so it can be enqueued directly or captured: one sub-batch after the other
+// (per stream), each through its whole time loop.
+int enqueue_body(Ctx *c, const Sweep &w, hipStream_t q0, bool *forked) {
+    const HadiBatchPlan &bp = w.r.bp;
+    for (int sb = 0; sb < (int)bp.subs.size(); sb++) {
+        if (bp.two_streams && sb == bp.fork_before) {  // fork: the second stream starts behind everything enqueued so far
+            HIP_TRY(c, hipEventRecord(c->fork_ev, q0));
+            HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->fork_ev, 0));
+            *forked = true;
+        }
+        const int rc = enqueue_sub_batch(c, w, sb, (bp.two_streams && bp.subs[sb].lane) ? c->stream2 : q0);
+        if (rc) return rc;
+    }
+    return HADI_OK;
+}
+// Fork / join around the body.  The join is enqueued even when the body failed half way: a second stream left un-joined
+// would make hipStreamEndCapture fail ("unjoined work") and stay in capture mode for the handle's next call.
+int enqueue_loop(Ctx *c, const Sweep &w, hipStream_t q0) {
+    bool forked = false;
+    const int rcb = enqueue_body(c, w, q0, &forked);
+    if (forked) {  // join
+        const hipError_t e1 = hipEventRecord(c->join_ev, c->stream2);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(q0, c->join_ev, 0) : e1;
+        if (!rcb && e2 != hipSuccess) return fail(c, HADI_ERR_HIP, "joining the second stream failed: %s", hipGetErrorString(e2));
+    }
+    return rcb;
+}
+
+// Every kernel argument is baked into the nodes of a captured loop, so the key is everything they depend on.  Addresses: every
+// pointer of both argument blocks, and every array enqueue_sub_batch names itself (the fp64 packed U, which the table kernel and
+// the fp32 dividend steps use even when the state is fp32; lambda_bar, payoff, U_temp, the dividend tables and the caller's
+// s-grid).  The library's buffers only move when ensure() grows one, and that empties the cache (drop_graphs).
+std::string graph_key(const Ctx *c, const Sweep &w) {
+    const SweepDesc &d = w.d;
+    const HadiSweepArgs &a = w.a;
+    const HadiPlan &pl = w.r.pl;
+    const HadiBatchPlan &bp = w.r.bp;
+    std::string key;
+    auto put = [&](const void *p_, size_t nbytes) { key.append(static_cast<const char *>(p_), nbytes); };
+    {  // field by field: struct padding is not initialised
+        const void *pa[HADI_SWEEP_ARGS_NPTRS], *pv[HADI_SWEEP_ARGS_NPTRS];
+        hadi_sweep_args_ptrs(a, pa);
+        hadi_sweep_args_ptrs(w.av, pv);
+        const void *own[] = {c->U.p, c->LAM.p, c->U0.p, c->UT.p, c->div_flag.p, c->div_amt.p, c->div_pct.p, d.d_vec_s};
+        const int ints[] = {a.debug, a.L.m1, a.L.m2, a.L.B, a.L.G, a.L.P, a.n_inst, a.R, a.ntiles, a.ctiles, a.btpw, a.bgroups,
+                            a.american, a.pos_m1, d.scheme, d.prec, (int)w.amp, (int)bp.two_streams, (int)bp.subs.size(), pl.row_seq, pl.col_seq, pl.use_pairs, pl.use_strip, pl.RS, pl.sblocks, pl.grid_as, pl.grid_a, pl.grid_b, pl.block_b, pl.W, (int)pl.smem_a, (int)pl.smem_b};
+        put(pa, sizeof(pa));
+        put(pv, sizeof(pv));
+        put(own, sizeof(own));
+        put(ints, sizeof(ints));
+    }
+    for (size_t sb = 0; sb < bp.subs.size(); sb++) {  // the launch geometry of EVERY sub-batch is baked into the nodes (unequal halves
+                                                      // on two streams, a tuning change that flips only the second sub-batch's plan)
+        const HadiSubBatch &sbt = bp.subs[sb];
+        const HadiPlan &q = sbt.pl;
+        const int geo[] = {c->t.col_prefetch, c->t.cs_strips, c->t.tile_il, sbt.lane, bp.fork_before, sbt.off, sbt.cnt, q.R, q.ntiles, q.grid_a, (int)q.smem_a, q.use_strip, q.use_pairs, q.RS, q.sblocks, q.grid_as,
+                           (int)q.smem_as, q.ctiles, q.btpw, q.bgroups, q.grid_b, q.block_b, (int)q.smem_b, q.row_seq, q.col_seq, q.W, q.NG, q.PD,
+                           w.r.resident[sb] ? 1 : 0};
+        put(geo, sizeof(geo));
+    }
+    put(&d.Nmax, sizeof(int)); put(&d.dt0, sizeof(double));
+    put(&d.variant, sizeof(int));
+    if (w.r.ladder) {  // the snapshot launches sit behind the steps of the list, with these addresses
+        const void *lad[] = {c->snap_node.p, c->snap_out.p};
+        put(lad, sizeof(lad));
+        put(&d.n_snap, sizeof(int));
+        put(d.snap_steps, sizeof(int) * d.n_snap);
+    }
+    if (w.r.have_div) {  // amounts / percentages / per-instance tables are re-uploaded every call; the node list
+                         // only depends on which steps carry a dividend launch
+        put(&w.flag_stride, sizeof(int));
+        put(w.div_step.data(), w.div_step.size());
+    }
+    return key;
+}
+
+// Replays the time loop from the graph cached under `key`, capturing it first (and evicting the least recently used of 8
+// entries) when there is none.
+int replay_or_capture(Ctx *c, const Sweep &w, const std::string &key) {
+    hipStream_t s = c->stream;
+    Ctx::GraphEntry *hit = nullptr;
+    for (auto &g : c->graphs)
+        if (g.key == key) { hit = &g; break; }
+    if (!hit) {
+        if (c->graphs.size() >= 8) {  // evict the least recently used entry
+            size_t lru = 0;
+            for (size_t k = 1; k < c->graphs.size(); k++)
+                if (c->graphs[k].stamp < c->graphs[lru].stamp) lru = k;
+            (void)hipGraphExecDestroy(c->graphs[lru].exec);
+            (void)hipGraphDestroy(c->graphs[lru].graph);
+            c->graphs.erase(c->graphs.begin() + lru);
+            c->graph_evictions++;
+        }
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        HIP_TRY(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        const int rcl = enqueue_loop(c, w, s);
+        hipError_t ec = hipStreamEndCapture(s, &graph);
+        if (rcl || ec != hipSuccess) {  // nothing half-built survives: the captured graph is dropped
+            if (graph) (void)hipGraphDestroy(graph);
+            if (rcl) return rcl;
+        }
+        HIP_TRY(c, ec);
+        HIP_TRY(c, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        c->graphs.push_back(Ctx::GraphEntry{key, graph, exec, 0});
+        hit = &c->graphs.back();
+        c->graph_captures++;
+    } else {
+        c->graph_replays++;
+    }
+    hit->stamp = ++c->graph_clock;
+    HIP_TRY(c, hipGraphLaunch(hit->exec, s));
+    return HADI_OK;
+}
+
+int run_streaming(Ctx *c, Sweep &w, bool team_fell_back) {
+    hipStream_t s = c->stream;
+    int rc;
+    if (!team_fell_back) {  // (the team's attempt has set both)
+        c->last_path = hadi_describe_route(w.r, w.in, w.amp);
+        HIP_TRY(c, hipEventRecord(c->ev[1], s));
+    }
+    if ((rc = w.r.graphable ? replay_or_capture(c, w, graph_key(c, w)) : enqueue_loop(c, w, s))) return rc;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[2], s));
+    if (w.r.f32)  // back to the fp64 packed array the unpack / price-pick kernels read
+        hipLaunchKernelGGL(hadi_widen_kernel, dim3(grid1d(w.tot)), dim3(256), 0, s, w.r.pl.L, ptr<float>(c->Uf), ptr<double>(c->U), w.tot);
+    return HADI_OK;
+}
+
+int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
+    Sweep w{d, route_in(c, d)};
+    w.r = hadi_route(w.in);
+    if (w.r.status == HADI_ROUTE_BAD_GRID)
+        return fail(c, HADI_ERR_UNSUPPORTED, "grid %dx%d not supported (need m1 >= 2, m2 >= 3 and (m1 + 16)(m2 + 1) < 2^28)", d.m1, d.m2);
+    if (w.r.status == HADI_ROUTE_SEQ_UNSUPPORTED)
+        return fail(c, HADI_ERR_UNSUPPORTED, "grids with m1 > 1024 or m2 > %d run Douglas sweeps with the fp64 state only", HADI_MAX_P * HADI_LC - 1);
+    if (w.r.status) return fail(c, HADI_ERR_UNSUPPORTED, "plan failed");
+    pl = w.r.pl;
+    w.tot = (size_t)pl.L.inst_stride * d.n;
+    w.st = w.tot * sizeof(double);
+    int rc;
+    if ((rc = grow_buffers(c, w)) || (rc = stage_inputs(c, w))) return rc;
+    sweep_args(c, w);
+    if (w.r.prof) {
+        const size_t need = (size_t)4 * d.Nmax * w.r.bp.subs.size();
         while (c->kev.size() < need) {
             hipEvent_t e;
             HIP_TRY(c, hipEventCreate(&e));
             c->kev.push_back(e);
         }
     }
-    // The whole time loop as a function of the stream, so it can be enqueued directly or captured.
-    // Instance offset `o` applied to every per-instance array of the sweep arguments (sub-batches, see nsub above).
-    auto shift = [&](HadiSweepArgs x, int o, int cnt, const HadiPlan &sp) {
-        x.n_inst = cnt; x.R = sp.R; x.ntiles = sp.ntiles; x.ctiles = sp.ctiles; x.btpw = sp.btpw; x.bgroups = sp.bgroups;
-        x.RS = sp.RS; x.sblocks = sp.sblocks;
-        const size_t so = (size_t)o * L.inst_stride;
-        if (f32) {
-            x.U = reinterpret_cast<double *>(reinterpret_cast<float *>(x.U) + so);
-            x.Y = reinterpret_cast<double *>(reinterpret_cast<float *>(x.Y) + so);
-        } else {
-            x.U += so;
-            x.Y += so;
-        }
-        if (x.LAM) x.LAM += so;
-        if (x.U0) x.U0 += so;
-        if (x.pay_mis) x.pay_mis += o;
-        if (x.R1) x.R1 += so;
-        if (x.C2) x.C2 += so;
-        if (x.rs_tab) x.rs_tab += (size_t)o * L.nrows * 128;
-        x.scoef += (size_t)o * pl.n_scoef; x.b2row += (size_t)o * pl.n_b2row; x.rowc += (size_t)o * pl.n_rowc;
-        x.pb += (size_t)o * pl.n_pb; x.rinv += (size_t)o * pl.n_rinv; x.ipar += o;
-        return x;
-    };
-    // Resident sweep (hadi_sweep_resident): European Douglas steps with the fp64 state, 8 nodes per lane on one wavefront per
-    // v-row, at most 8 column chunks, and a sub-batch whose strip row pass is ONE block per instance in ONE round of CUs with
-    // less than HADI_TWO_STREAM_IDLE of them idle -- a block that waited for a second round would wait for a whole time loop.
-    // Other sub-batches of the same call (a small remainder) stay on the streaming kernels.  "resident_sweep" = -1 (default):
-    // wherever eligible unless the caller pinned the streaming geometry; 1: wherever eligible; 0: never.
-    // (`pinned`, above: neither the resident sweep nor, below, the team launch is chosen automatically)
-    const bool resident_shape = (c->resident_sweep > 0 || (c->resident_sweep < 0 && !pinned)) && d.scheme == HADI_SCHEME_DOUGLAS &&
-                                d.variant == HADI_EU && !f32 && L.B == 8 && L.G == 1 && L.P <= 8 && !seq_shape && d.theta > 0.0 &&
-                                d.r_d != d.r_f && !d.debug && !c->debug_fault && !prof && !ladder;  // (test hooks: the streaming kernels they are for)
-    auto resident = [&](const SubBatch &sbt) {
-        return resident_shape && sbt.pl.use_strip && !sbt.pl.use_pairs && sbt.pl.sblocks == 1 && sbt.cnt <= c->cu_count &&
-               hadi_plan_row_idle(sbt.pl, sbt.cnt, c->cu_count) < HADI_TWO_STREAM_IDLE;
-    };
-    const HadiSweepArgs a_all = a, av_all = av;
-    bool forked = false;
-    auto enqueue_body = [&](hipStream_t q0) -> int {
-      const int n_first = d.debug ? d.debug_step : 1, n_last = d.debug ? d.debug_step : d.Nmax;
-      for (int sb = 0; sb < nsub; sb++) {  // one sub-batch after the other (per stream), each through its whole time loop
-        if (two_streams && sb == fork_before) {  // fork: the second stream starts behind everything enqueued so far
-            HIP_TRY(c, hipEventRecord(c->fork_ev, q0));
-            HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->fork_ev, 0));
-            forked = true;
-        }
-        hipStream_t q = (two_streams && subs[sb].lane) ? c->stream2 : q0;
-        const int o = subs[sb].off, nsb = subs[sb].cnt;
-        const HadiPlan &pl = subs[sb].pl;  // (shadows the whole-batch plan: launch geometry of THIS sub-batch)
-        const size_t so = (size_t)o * L.inst_stride;
-        const HadiSweepArgs a = shift(a_all, o, nsb, pl), av = shift(av_all, o, nsb, pl);
-        const size_t tot = (size_t)L.inst_stride * nsb, st = tot * sizeof(double);  // (shadow the whole-batch sizes)
-        double *const Ub = ptr<double>(c->U) + so, *const LAMb = american ? ptr<double>(c->LAM) + so : nullptr;
-        double *const U0b = american ? ptr<double>(c->U0) + so : nullptr, *const UTb = dividend ? ptr<double>(c->UT) + so : nullptr;
-        const int ev0 = 4 * sb * d.Nmax;  // profiling events of this sub-batch
-        if (pair_tab && pl.use_strip) {  // paired strips: the pairs' coupling column, once per solve (hadi_strip_step, RSTAB)
-            HadiSweepArgs at = a;
-            at.U = Ub;  // (any packed fp64 array: the table depends on the matrix only)
-            if ((rc = launch_pass(c, hadi_select_pair_table(pl), q, at, 1))) return rc;
-        }
-        if (resident(subs[sb])) {  // the sub-batch's whole time loop in one launch (LDS: the strip rings; the column phase aliases them)
-            if ((rc = launch_pass(c, hadi_select_resident(pl), q, a, n_last))) return rc;
-            continue;
-        }
-        for (int nstep = n_first; nstep <= n_last; nstep++) {
-            // P representation: the first step (the caller's initial U need not dominate the payoff) and dividend steps
-            // (the jump acts on U alone) run on the explicit (U, lambda_bar) pair, converted on the way in and out
-            const bool xstep = amp && (nstep == 1 || (have_div && div_step[nstep]));
-            if (xstep && nstep > 1)
-                hipLaunchKernelGGL(hadi_am_materialise_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, nsb, a.ipar, U0b, Ub, LAMb, pl.pos_m1);
-            if (have_div && div_step[nstep]) {  // device_solver.hpp:426-517: U_temp <- U, U <- interpolated jump
-                if (f32)  // fp32 state: the jump works on the fp64 packed array -- widen, jump, round again (<= num_dividends steps)
-                    hipLaunchKernelGGL(hadi_widen_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, reinterpret_cast<const float *>(a.U), Ub, tot);
-                HIP_TRY(c, hipMemcpyAsync(UTb, Ub, st, hipMemcpyDeviceToDevice, q));
-                const size_t npts = (size_t)nsb * L.nrows * (L.m1 + 1);
-                hipLaunchKernelGGL(hadi_dividend_kernel, dim3(grid1d(npts)), dim3(256), 0, q, L, nsb, a.ipar,
-                                   d.d_vec_s + (size_t)o * (L.m1 + 1), UTb, Ub, ptr<int>(c->div_flag) + (size_t)o * flag_stride,
-                                   flag_stride, nstep, ptr<double>(c->div_amt), ptr<double>(c->div_pct));
-                if (f32)
-                    hipLaunchKernelGGL(hadi_narrow_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, Ub, reinterpret_cast<float *>(a.U), tot);
-            }
-            if (prof) HIP_TRY(c, hipEventRecord(c->kev[ev0 + 4 * (nstep - 1) + 0], q));
-            const HadiPassCtx pc{pl, nsb, american, amp, xstep, f32, d.scheme, c->cs_strips, c->col_prefetch};
-            auto row_pass = [&](const HadiSweepArgs &ar, int mode) { return launch_pass(c, hadi_select_row_pass(pc, mode), q, ar, nstep); };
-            auto col_pass = [&](const HadiSweepArgs &ar) { return launch_pass(c, hadi_select_col_pass(pc), q, ar, nstep); };
-            if (d.debug == 2) {  // diagnostics: one column solve of the packed input (moved to Y), nothing else
-                HIP_TRY(c, hipMemcpyAsync(a.Y, a.U, f32 ? st / 2 : st, hipMemcpyDeviceToDevice, q));
-                if ((rc = col_pass(a))) return rc;
-                break;
-            }
-            if ((rc = row_pass(a, cs ? 1 : 0))) return rc;
-            if (d.debug == 1) break;  // diagnostics: Y now holds the right-hand side of the A2 solve
-            if (prof) {
-                HIP_TRY(c, hipEventRecord(c->kev[ev0 + 4 * (nstep - 1) + 1], q));
-                HIP_TRY(c, hipEventRecord(c->kev[ev0 + 4 * (nstep - 1) + 2], q));
-            }
-            if ((rc = col_pass(cs ? av : a))) return rc;
-            if (prof) HIP_TRY(c, hipEventRecord(c->kev[ev0 + 4 * (nstep - 1) + 3], q));
-            if (cs) {  // corrector (profiling events cover the predictor's two passes only)
-                if ((rc = row_pass(av, 2)) || (rc = col_pass(a))) return rc;
-            }
-            if (ladder && snap_q[nstep] >= 0)  // (U is explicit here: a ladder call never runs in the P representation)
-                hipLaunchKernelGGL(hadi_snap_kernel, dim3((nsb + 63) / 64), dim3(64), 0, q, L, nsb, Ub, ptr<int>(c->snap_node) + o,
-                                   ptr<double>(c->snap_out) + (size_t)o * d.n_snap, d.n_snap, snap_q[nstep]);
-            if (xstep)
-                hipLaunchKernelGGL(hadi_am_dematerialise_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, nsb, a.ipar, U0b, Ub, LAMb);
-        }
-        if (amp)  // explicit U and lambda_bar for the outputs
-            hipLaunchKernelGGL(hadi_am_materialise_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, nsb, a.ipar, U0b, Ub, LAMb, pl.pos_m1);
-      }
-      return HADI_OK;
-    };
-    // Fork / join around the body.  The join is enqueued even when the body failed half way: a second stream left un-joined
-    // would make hipStreamEndCapture fail ("unjoined work") and stay in capture mode for the handle's next call.
-    auto enqueue_loop = [&](hipStream_t q0) -> int {
-      forked = false;
-      const int rcb = enqueue_body(q0);
-      if (forked) {  // join
-          const hipError_t e1 = hipEventRecord(c->join_ev, c->stream2);
-          const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(q0, c->join_ev, 0) : e1;
-          if (!rcb && e2 != hipSuccess) return fail(c, HADI_ERR_HIP, "joining the second stream failed: %s", hipGetErrorString(e2));
-      }
-      return rcb;
-    };
-
-    // ---- small grids: the whole instance fits in LDS -> one launch runs the entire time loop ----------
-    // European / dividend sweeps: one wavefront per instance with sequential line solves (hadi_small_seq_kernel) issues about
-    // half the instructions per instance and step but runs them on ONE wavefront -- ahead once there are more instances than
-    // CUs (50x25, 40 steps, ms block kernel / this one: 256 instances 0.49 / 0.55, 320: 0.67 / 0.60, 512: 0.71 / 0.63, 768: 0.95 /
-    // 0.80; 3000 x 50 steps: 3.75 / 2.13), behind below that (a single instance: 10 against 12 us per step).
-    // "small_seq" = 1 forces it, 0 forbids it, -1 (default) picks by batch size.
-    const bool seq = takes_small_path && !american && (c->small_seq > 0 || (c->small_seq < 0 && d.n > c->cu_count));
-    const size_t smem_seq = hadi_small_seq_smem(L);
-    // ... and two instances per wavefront for batches of more than 2 and at most 4.5 instances per CU: a wavefront then retires
-    // two instances' steps in 1.15x the time of one, but the launch has half the wavefronts -- below 2 per CU the instances are
-    // better spread over the CUs, at the 6 per CU that the LDS holds either way the halved instruction count and the halved
-    // latency hiding cancel (50x25 x 200 steps, ms: 768 instances 3.20 -> 2.76, 1024: 3.49 -> 2.78, 1536: 3.53 -> 3.83, 3072:
-    // 6.68 -> 6.98).  "small_pairs" = 1 forces it, 0 forbids it, -1 (default) picks by batch size.  Needs nrows <= 32.
-    const bool seq2 = seq && L.nrows <= 32 && 2 * smem_seq <= (size_t)160 * 1024 &&
-                      (c->small_pairs > 0 || (c->small_pairs < 0 && d.n > 2 * c->cu_count && 2 * d.n <= 9 * c->cu_count));
-    // The whole-loop kernels' second argument block: dividend tables and, for batches of mixed maturities, the dispatch order.
-    auto small_args = [&](HadiSmallArgs &sm) -> int {
-        sm.div_flag = nullptr; sm.div_amounts = nullptr; sm.div_pcts = nullptr; sm.vec_s = d.d_vec_s; sm.Nmax = d.Nmax;
-        sm.order = nullptr;
-        if (!d.uniform_steps) {  // longest-processing-time-first dispatch order
-            std::vector<int> order(d.n);
-            for (int k = 0; k < d.n; k++) order[k] = k;
-            std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
-                return d.par8[(size_t)x * 8 + 5] > d.par8[(size_t)y * 8 + 5];
-            });
-            if ((rc = ensure(c, c->order, sizeof(int) * n))) return rc;
-            if ((rc = stage_to_device(c, c->order.p, order.data(), sizeof(int) * n))) return rc;
-            sm.order = ptr<int>(c->order);
-        }
-        sm.flag_stride = flag_stride;
-        if (have_div) {
-            sm.div_flag = ptr<int>(c->div_flag); sm.div_amounts = ptr<double>(c->div_amt); sm.div_pcts = ptr<double>(c->div_pct);
-        }
-        if (ladder) {
-            sm.snap_steps = ptr<int>(c->snap_steps); sm.n_snap = d.n_snap;
-            sm.snap_node = ptr<int>(c->snap_node); sm.snap_out = ptr<double>(c->snap_out);
-        }
-        return HADI_OK;
-    };
-    // what hadi_describe_last_sweep adds for a ladder call
-    const std::string ladder_loop = ladder ? "; maturity ladder: " + std::to_string(d.n_snap) + " snapshots copied inside the time loop" : "";
-    const std::string ladder_stream = ladder ? "; maturity ladder: " + std::to_string(d.n_snap) + " snapshots, hadi_snap_kernel after each snapshot step" : "";
-    if (small_sch) {
-        const int sch = d.scheme == HADI_SCHEME_MCS ? HADI_SCH_MCS : d.scheme == HADI_SCHEME_HV ? HADI_SCH_HV : HADI_SCH_CS;
-        const HadiLoopFn fn = hadi_small_sch_fn(L.B, sch);
-        if (!fn) return fail(c, HADI_ERR_INTERNAL, "no small-grid kernel of scheme %d for grid %dx%d", d.scheme, d.m1, d.m2);
-        const size_t smem = smem_sch;
-        char buf[256];
-        std::snprintf(buf, sizeof buf, "hadi_small_sch_kernel<%d,%s>: whole time loop in one launch, one wavefront per instance, predictor and corrector lines solved sequentially in LDS (%zu B)",
-                      L.B, sch == HADI_SCH_MCS ? "MCS" : sch == HADI_SCH_HV ? "HV" : "CS", smem);
-        c->last_path = buf + ladder_loop;
-        HadiSmallArgs sm;
-        if ((rc = small_args(sm))) return rc;
-        HIP_TRY(c, hipEventRecord(c->ev[1], s));
-        hipLaunchKernelGGL(fn, dim3(d.n), dim3(64), smem, s, a, sm);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventRecord(c->ev[2], s));
-        return HADI_OK;
+    if (w.r.kind != HADI_ROUTE_TEAM && w.r.kind != HADI_ROUTE_STREAMING) return run_small(c, w);
+    c->last_nsub = (int)w.r.bp.subs.size();
+    bool fell_back = false;
+    if (w.r.kind == HADI_ROUTE_TEAM) {
+        c->last_path = hadi_describe_route(w.r, w.in, w.amp);
+        if ((rc = run_team(c, w, &fell_back)) || !fell_back) return rc;
     }
-    if (takes_small_path) {
-        // wavefronts per instance: 4 when the batch fills the GPU (throughput), 8 for small batches (latency of the
-        // dependent per-step phases; more waves share the rows of the row pass)
-        // (measured, 50x25 grid: 1 instance x 100 steps 1.27 -> 1.04 ms with 8; 3000 instances x 50 steps 4.19 -> 4.58 ms)
-        const int sw = c->tune.small_waves ? c->tune.small_waves : (d.n <= 2 * c->cu_count ? 8 : 4);
-        const HadiSel sel = hadi_select_small(pl, d.n, seq2 ? 2 : seq ? 1 : 0, sw, american);
-        if (!sel.k) return fail(c, HADI_ERR_INTERNAL, "no small-grid kernel for grid %dx%d", d.m1, d.m2);
-        {
-            char buf[192];
-            if (seq2)
-                std::snprintf(buf, sizeof buf, "hadi_small_seq2_kernel<%d>: whole time loop in one launch, two instances per wavefront, lines solved sequentially in LDS (2 x %zu B)", L.B, smem_seq);
-            else if (seq)
-                std::snprintf(buf, sizeof buf, "hadi_small_seq_kernel<%d>: whole time loop in one launch, one wavefront per instance, lines solved sequentially in LDS (%zu B)", L.B, smem_seq);
-            else
-                std::snprintf(buf, sizeof buf, "hadi_small_kernel<%d,%d,%s>: whole time loop in one launch, instance resident in LDS (%zu B)", L.B,
-                              sel.k->G, american ? "AM" : "EU", sel.smem);
-            c->last_path = buf + ladder_loop;
-        }
-        HadiSmallArgs sm;
-        if ((rc = small_args(sm))) return rc;
-        HIP_TRY(c, hipEventRecord(c->ev[1], s));
-        hipLaunchKernelGGL((sel.k->loop), dim3(sel.grid), dim3(sel.block), sel.smem, s, a, sm);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventRecord(c->ev[2], s));
-        return HADI_OK;
-    }
-
-    c->last_path = describe_streaming_path(HadiPassCtx{pl, d.n, american, amp, false, f32, d.scheme, c->cs_strips, c->col_prefetch}, bp);
-    {
-        int nres = 0;
-        for (const auto &sbt : subs) nres += resident(sbt) ? 1 : 0;
-        if (nres == nsub)
-            c->last_path += "; both passes of every step in one launch: hadi_sweep_resident<8> (one block per instance, all column tiles)";
-        else if (nres)
-            c->last_path += "; both passes of every step in one launch for " + std::to_string(nres) +
-                            " sub-batches of one round: hadi_sweep_resident<8> (one block per instance, all column tiles), the others streaming";
-        c->last_path += ladder_stream;
-    }
-    c->last_nsub = nsub;
-    HIP_TRY(c, hipEventRecord(c->ev[1], s));
-    // ---- instance-resident launch: up to 8 large European instances, one per XCD, whole time loop in one kernel ----------
-    // (hadi_team_kernel; the reference runs every instance's time loop inside one kernel, device_solver.hpp:83-88,226-265).
-    // Chosen automatically for batches of up to 8 instances on the full 256-CU device; any failure of the team protocol is
-    // recorded by the kernel, checked here, and the batch is solved again on the streaming path below.
-    const bool team_shape = d.n <= 8 && L.G == 1 && (L.B == 8 || L.B == 4) && L.P <= 8 && !seq_shape && (d.variant == HADI_EU || d.variant == HADI_DIV) && !cs && !f32 &&
-                            !d.debug && !prof && d.theta > 0.0 && d.r_d != d.r_f && c->cu_count == 256;
-    if (team_shape && !ladder && (c->team_launch > 0 || (c->team_launch < 0 && !c->team_failed && !pinned))) {
-        if ((rc = ensure(c, c->team, 512 * sizeof(int)))) return rc;
-        HIP_TRY(c, hipMemsetAsync(c->team.p, 0, 512 * sizeof(int), s));
-        HadiTeamArgs ta;
-        ta.form = ptr<int>(c->team); ta.bar = ptr<int>(c->team) + 64; ta.nb = c->cu_count / 8; ta.N = d.Nmax;
-        ta.div_flag = have_div ? ptr<int>(c->div_flag) : nullptr; ta.flag_stride = flag_stride;
-        ta.div_amounts = have_div ? ptr<double>(c->div_amt) : nullptr; ta.div_pcts = have_div ? ptr<double>(c->div_pct) : nullptr;
-        ta.vec_s = d.d_vec_s;
-        ta.stamps = reinterpret_cast<unsigned long long *>(ptr<int>(c->team) + 384);
-        const size_t smem = hadi_team_smem(L, have_div);
-        if (L.B == 8) hipLaunchKernelGGL((hadi_team_kernel<8>), dim3(c->cu_count), dim3(512), smem, s, a, ta);
-        else hipLaunchKernelGGL((hadi_team_kernel<4>), dim3(c->cu_count), dim3(512), smem, s, a, ta);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(s));
-        const int deverr = __atomic_exchange_n(c->err_host, 0, __ATOMIC_ACQ_REL);
-        if (!deverr) {
-            char buf[200];
-            std::snprintf(buf, sizeof buf, "hadi_team_kernel<%d>: whole time loop in one launch, every instance resident in one XCD's L2 (teams of %d blocks)",
-                          L.B, ta.nb);
-            c->last_path = buf;
-            HIP_TRY(c, hipEventRecord(c->ev[2], s));
-            return HADI_OK;
-        }
-        if (deverr & ~HADI_DEVERR_TEAM) __atomic_fetch_or(c->err_host, deverr & ~HADI_DEVERR_TEAM, __ATOMIC_RELAXED);  // (not ours: keep it for finish_timing)
-        c->team_failed = 1;
-        // start again from the caller's initial condition on the streaming path
-        hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src, d.d_natU, ptr<double>(c->U));
-        HIP_TRY(c, hipMemsetAsync(c->Y.p, 0, st, s));
-        c->last_path += " (after a failed instance-resident launch)";
-    }
-    // Small batches are launch-bound (2*N dependent launches of a few microseconds each): replay the loop
-    // from a cached hipGraph.  Every kernel argument is baked into the nodes, so the key is everything they
-    // depend on.  Addresses: every pointer of both argument blocks, and every array enqueue_body names itself (the fp64 packed
-    // U, which the table kernel and the fp32 dividend steps use even when the state is fp32; lambda_bar, payoff, U_temp, the
-    // dividend tables and the caller's s-grid).  The library's buffers only move when ensure() grows one, and that empties the
-    // cache (drop_graphs).
-    const bool graphable = c->use_graph && !prof && !d.debug && (long long)d.n * L.inst_stride <= ((long long)c->graph_max_melems << 20);
-    if (graphable) {
-        std::string key;
-        auto put = [&](const void *p_, size_t nbytes) { key.append(static_cast<const char *>(p_), nbytes); };
-        {  // field by field: struct padding is not initialised
-            const void *pa[HADI_SWEEP_ARGS_NPTRS], *pv[HADI_SWEEP_ARGS_NPTRS];
-            hadi_sweep_args_ptrs(a, pa);
-            hadi_sweep_args_ptrs(av, pv);
-            const void *own[] = {c->U.p, c->LAM.p, c->U0.p, c->UT.p, c->div_flag.p, c->div_amt.p, c->div_pct.p, d.d_vec_s};
-            const int ints[] = {a.debug, a.L.m1, a.L.m2, a.L.B, a.L.G, a.L.P, a.n_inst, a.R, a.ntiles, a.ctiles, a.btpw, a.bgroups,
-                                a.american, a.pos_m1, d.scheme, d.prec, (int)amp, (int)two_streams, nsub, pl.row_seq, pl.col_seq, pl.use_pairs, pl.use_strip, pl.RS, pl.sblocks, pl.grid_as, pl.grid_a, pl.grid_b, pl.block_b, pl.W, (int)pl.smem_a, (int)pl.smem_b};
-            put(pa, sizeof(pa));
-            put(pv, sizeof(pv));
-            put(own, sizeof(own));
-            put(ints, sizeof(ints));
-        }
-        for (const auto &sbt : subs) {  // the launch geometry of EVERY sub-batch is baked into the nodes (unequal halves on two
-                                        // streams, a tuning change that flips only the second sub-batch's plan)
-            const HadiPlan &q = sbt.pl;
-            const int geo[] = {c->col_prefetch, c->cs_strips, c->tile_il, sbt.lane, fork_before, sbt.off, sbt.cnt, q.R, q.ntiles, q.grid_a, (int)q.smem_a, q.use_strip, q.use_pairs, q.RS, q.sblocks, q.grid_as,
-                               (int)q.smem_as, q.ctiles, q.btpw, q.bgroups, q.grid_b, q.block_b, (int)q.smem_b, q.row_seq, q.col_seq, q.W, q.NG, q.PD,
-                               resident(sbt) ? 1 : 0};
-            put(geo, sizeof(geo));
-        }
-        put(&d.Nmax, sizeof(int)); put(&d.dt0, sizeof(double));
-        put(&d.variant, sizeof(int));
-        if (ladder) {  // the snapshot launches sit behind the steps of the list, with these addresses
-            const void *lad[] = {c->snap_node.p, c->snap_out.p};
-            put(lad, sizeof(lad));
-            put(&d.n_snap, sizeof(int));
-            put(d.snap_steps, sizeof(int) * d.n_snap);
-        }
-        if (have_div) {  // amounts / percentages / per-instance tables are re-uploaded every call; the node list
-                         // only depends on which steps carry a dividend launch
-            put(&flag_stride, sizeof(int));
-            put(div_step.data(), div_step.size());
-        }
-        Ctx::GraphEntry *hit = nullptr;
-        for (auto &g : c->graphs)
-            if (g.key == key) { hit = &g; break; }
-        if (!hit) {
-            if (c->graphs.size() >= 8) {  // evict the least recently used entry
-                size_t lru = 0;
-                for (size_t k = 1; k < c->graphs.size(); k++)
-                    if (c->graphs[k].stamp < c->graphs[lru].stamp) lru = k;
-                (void)hipGraphExecDestroy(c->graphs[lru].exec);
-                (void)hipGraphDestroy(c->graphs[lru].graph);
-                c->graphs.erase(c->graphs.begin() + lru);
-                c->graph_evictions++;
-            }
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            HIP_TRY(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            const int rcl = enqueue_loop(s);
-            hipError_t ec = hipStreamEndCapture(s, &graph);
-            if (rcl || ec != hipSuccess) {  // nothing half-built survives: the captured graph is dropped
-                if (graph) (void)hipGraphDestroy(graph);
-                if (rcl) return rcl;
-            }
-            HIP_TRY(c, ec);
-            HIP_TRY(c, hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            c->graphs.push_back(Ctx::GraphEntry{key, graph, exec, 0});
-            hit = &c->graphs.back();
-            c->graph_captures++;
-        } else {
-            c->graph_replays++;
-        }
-        hit->stamp = ++c->graph_clock;
-        HIP_TRY(c, hipGraphLaunch(hit->exec, s));
-    } else {
-        const int rcl = enqueue_loop(s);
-        if (rcl) return rcl;
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev[2], s));
-    if (f32)  // back to the fp64 packed array the unpack / price-pick kernels read
-        hipLaunchKernelGGL(hadi_widen_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, ptr<float>(c->Uf), ptr<double>(c->U), tot);
-    return HADI_OK;
+    return run_streaming(c, w, fell_back);
 }
 
 int finish_timing(Ctx *c, const SweepDesc &d) {
@@ -983,7 +841,7 @@ int check_problem(Ctx *c, const hadi_problem *p, bool need_U, bool need_vgrid) {
     {  // grid shape, before anything is staged
         HadiPlan tmp;
         if (p->m1 < 2 || p->m2 < 3 ||
-            hadi_make_plan(p->m1, p->m2, p->n_instances, 8 * c->cu_count, &tmp, c->tune, p->state_precision == HADI_STATE_FP32 ? 4 : 8))
+            hadi_make_plan(p->m1, p->m2, p->n_instances, 8 * c->cu_count, &tmp, c->t.tune, p->state_precision == HADI_STATE_FP32 ? 4 : 8))
             return fail(c, HADI_ERR_UNSUPPORTED, "grid %dx%d not supported (need m1 >= 2, m2 >= 3 and (m1 + 16)(m2 + 1) < 2^28)", p->m1, p->m2);
     }
     const bool dividend = p->variant == HADI_DIV || p->variant == HADI_AM_DIV;
@@ -1095,8 +953,8 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
     if (debug == 1 && (debug_step < 1 || debug_step > d.Nmax)) return fail(c, HADI_ERR_INVALID, "step %d outside 1..%d", debug_step, d.Nmax);
     if ((rc = to_device(c, p->memspace, p->vec_s, (size_t)n * (m1 + 1), c->g_s, &d.d_vec_s))) return rc;
     if ((rc = to_device(c, p->memspace, p->delta_s, (size_t)n * m1, c->g_ds, &d.d_delta_s))) return rc;
-    const bool per_inst_v0 = rebuild_v && c->device_vgrid;
-    if (rebuild_v && !c->device_vgrid && p->V_0_i)
+    const bool per_inst_v0 = rebuild_v && c->t.device_vgrid;
+    if (rebuild_v && !c->t.device_vgrid && p->V_0_i)
         return fail(c, HADI_ERR_INVALID, "V_0_i needs the device v-grid rebuild (hadi_set_tuning \"device_vgrid\", 1)");
     if (per_inst_v0) {
         std::vector<double> v0i(n);
@@ -1239,36 +1097,11 @@ int greeks_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double 
     return HADI_OK;
 }
 
-// compute_jacobian*: the reference runs 6 solves one after the other inside each team
-// (jacobian_computation.cpp:232-363); here they are 6n independent instances of ONE batched sweep:
-// group 0 = base, 1..4 = kappa, eta, sigma, rho + eps, 5 = v-grid rebuilt for V_0 + eps.
-// Ladder (n_snap > 0; hadi_compute_jacobian_ladder): J [n][n_snap][5] and base_prices [n][n_snap] from the snapshots of the 6n solves.
-int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double eps, double *J, double *base_prices,
-                    int n_snap = 0, const int *snap_steps = nullptr) {
-    int rc = check_problem(c, p, false, false);
-    if (rc) return rc;
-    const bool ladder = n_snap > 0 || snap_steps;
-    if (ladder && (rc = check_ladder(c, p, n_snap, snap_steps, (J && base_prices) ? J : nullptr))) return rc;
-    DeviceGuard guard(c->device);
-    pin_rewind(c);
-    if (!p->U_0) return fail(c, HADI_ERR_INVALID, "U_0 (initial condition) is required for the Jacobian");
-    if (!J || !base_prices) return fail(c, HADI_ERR_INVALID, "J / base_prices missing");
-    const int n0 = p->n_instances, m1 = p->m1, m2 = p->m2, G = 6;
-    if (!c->device_vgrid && p->V_0_i)
-        return fail(c, HADI_ERR_INVALID, "V_0_i needs the device v-grid rebuild (hadi_set_tuning \"device_vgrid\", 1)");
-    const int n = n0 * G;
-    const size_t m = (size_t)(m1 + 1) * (m2 + 1);
-    SweepDesc d;
-    fill_common(p, d);
-    d.n = n; d.n_src = n0;
-    fill_par(p, d, G);
-    for (int k = 0; k < n0; k++) {
-        d.par8[((size_t)1 * n0 + k) * 8 + 2] += eps;  // kappa
-        d.par8[((size_t)2 * n0 + k) * 8 + 3] += eps;  // eta
-        d.par8[((size_t)3 * n0 + k) * 8 + 1] += eps;  // sigma
-        d.par8[((size_t)4 * n0 + k) * 8 + 0] += eps;  // rho
-    }
-    // s-grids: replicate the caller's rows into the 6 groups
+// The grids of the 6 groups of a Jacobian's batch: the caller's s-rows replicated, the v-grids rebuilt for V_0 (groups 0..4) and
+// V_0 + eps (group 5); c->v0_i keeps the per-instance V_0 for the price pick.
+int jacobian_grids(Ctx *c, const hadi_problem *p, int G, double V_0, double eps, int n_snap, SweepDesc &d) {
+    const int n0 = p->n_instances, m1 = p->m1, m2 = p->m2, n = n0 * G;
+    int rc;
     const double *src_s, *src_ds;
     // (natOut stages delta_s here and takes J and the base prices after the sweep; prices / status: the pick.  All grown before
     // the sweep: growing one after it would drop the loop it just captured)
@@ -1299,7 +1132,7 @@ int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, doubl
     hipLaunchKernelGGL(hadi_bcast_rows_kernel, dim3(grid1d((size_t)n * m1)), dim3(256), 0, s, m1, n, src_ds,
                        ptr<int>(c->sel_a), ptr<double>(c->g_ds));
     std::vector<double> hv(2 * (m2 + 1)), hdv(2 * m2);
-    if (c->device_vgrid) {
+    if (c->t.device_vgrid) {
         // every instance rebuilds its own v-grid on the device: V_0 for the groups 0..4, V_0 + eps for group 5
         // (jacobian_computation.cpp:253,339-341)
         if ((rc = rebuild_v_device(c, n, m2, v0i))) return rc;
@@ -1318,6 +1151,40 @@ int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, doubl
     // natOut are only reused by later operations of the same stream)
     d.d_vec_s = ptr<double>(c->g_s); d.d_delta_s = ptr<double>(c->g_ds);
     d.d_vec_v = ptr<double>(c->g_v); d.d_delta_v = ptr<double>(c->g_dv);
+    return HADI_OK;
+}
+
+// compute_jacobian*: the reference runs 6 solves one after the other inside each team
+// (jacobian_computation.cpp:232-363); here they are 6n independent instances of ONE batched sweep:
+// group 0 = base, 1..4 = kappa, eta, sigma, rho + eps, 5 = v-grid rebuilt for V_0 + eps.
+// Ladder (n_snap > 0; hadi_compute_jacobian_ladder): J [n][n_snap][5] and base_prices [n][n_snap] from the snapshots of the 6n solves.
+int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double eps, double *J, double *base_prices,
+                    int n_snap = 0, const int *snap_steps = nullptr) {
+    int rc = check_problem(c, p, false, false);
+    if (rc) return rc;
+    const bool ladder = n_snap > 0 || snap_steps;
+    if (ladder && (rc = check_ladder(c, p, n_snap, snap_steps, (J && base_prices) ? J : nullptr))) return rc;
+    DeviceGuard guard(c->device);
+    pin_rewind(c);
+    if (!p->U_0) return fail(c, HADI_ERR_INVALID, "U_0 (initial condition) is required for the Jacobian");
+    if (!J || !base_prices) return fail(c, HADI_ERR_INVALID, "J / base_prices missing");
+    const int n0 = p->n_instances, m1 = p->m1, m2 = p->m2, G = 6;
+    if (!c->t.device_vgrid && p->V_0_i)
+        return fail(c, HADI_ERR_INVALID, "V_0_i needs the device v-grid rebuild (hadi_set_tuning \"device_vgrid\", 1)");
+    const int n = n0 * G;
+    const size_t m = (size_t)(m1 + 1) * (m2 + 1);
+    SweepDesc d;
+    fill_common(p, d);
+    d.n = n; d.n_src = n0;
+    fill_par(p, d, G);
+    for (int k = 0; k < n0; k++) {
+        d.par8[((size_t)1 * n0 + k) * 8 + 2] += eps;  // kappa
+        d.par8[((size_t)2 * n0 + k) * 8 + 3] += eps;  // eta
+        d.par8[((size_t)3 * n0 + k) * 8 + 1] += eps;  // sigma
+        d.par8[((size_t)4 * n0 + k) * 8 + 0] += eps;  // rho
+    }
+    if ((rc = jacobian_grids(c, p, G, V_0, eps, n_snap, d))) return rc;
+    hipStream_t s = c->stream;
     // every solve starts from U_0 (jacobian_computation.cpp:307-309); payoff for American = U_0 too
     if ((rc = to_device(c, p->memspace, p->U_0, n0 * m, c->natU0, &d.d_natU))) return rc;
     d.d_natU0 = d.d_natU;
@@ -1489,85 +1356,33 @@ int hadi_set_profiling(hadi_ctx *ctx, int enabled) {
     return HADI_OK;
 }
 
+// The keys, their fields and normalisations: hadi_tuning_key (csrc/hadi_route.h).  Here: the four read-only counters, and
+// "team_launch", which clears team_failed when set and reads back as -2 once a team has failed.
+static const unsigned long long *graph_counter(const Ctx *c, const char *key) {
+    return !std::strcmp(key, "graph_captures") ? &c->graph_captures : !std::strcmp(key, "graph_replays") ? &c->graph_replays :
+           !std::strcmp(key, "graph_drops") ? &c->graph_drops : !std::strcmp(key, "graph_evictions") ? &c->graph_evictions : nullptr;
+}
+
 int hadi_set_tuning(hadi_ctx *ctx, const char *key, int value) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (!c || !key) return HADI_ERR_INVALID;
-    if (!std::strcmp(key, "graph")) c->use_graph = value ? 1 : 0;
-    else if (!std::strcmp(key, "small_grid")) c->use_small = value ? 1 : 0;
-    else if (!std::strcmp(key, "small_seq")) c->small_seq = value < 0 ? -1 : (value ? 1 : 0);
-    else if (!std::strcmp(key, "small_sch")) c->small_sch = value < 0 ? -1 : (value ? 1 : 0);
-    else if (!std::strcmp(key, "american_p")) c->use_amp = value ? 1 : 0;
-    else if (!std::strcmp(key, "device_vgrid")) c->device_vgrid = value ? 1 : 0;
-    else if (!std::strcmp(key, "sub_batch")) c->sub_batch = value ? 1 : 0;
-    else if (!std::strcmp(key, "small_pairs")) c->small_pairs = value < 0 ? -1 : (value ? 1 : 0);
-    else if (!std::strcmp(key, "streams")) c->streams = value == 2 ? 2 : (value == 1 ? 1 : 0);
-    else if (!std::strcmp(key, "col_prefetch")) c->col_prefetch = value ? 1 : 0;
-    else if (!std::strcmp(key, "cs_strips")) c->cs_strips = (value >= 0 && value <= 3) ? value : 1;
-    else if (!std::strcmp(key, "graph_max_melems")) c->graph_max_melems = value > 0 ? value : 0;
-    else if (!std::strcmp(key, "tile_interleave")) c->tile_il = value ? 1 : 0;
-    else if (!std::strcmp(key, "strip")) c->tune.strip = value < 0 ? -1 : (value ? 1 : 0);
-    else if (!std::strcmp(key, "debug_fault")) c->debug_fault = value;
-    else if (!std::strcmp(key, "team_launch")) { c->team_launch = value < 0 ? -1 : (value ? 1 : 0); c->team_failed = 0; }
-    else if (!std::strcmp(key, "resident_sweep")) c->resident_sweep = value < 0 ? -1 : (value ? 1 : 0);
-    else if (!std::strcmp(key, "row_tile")) c->tune.row_tile = value > 0 ? value : 0;
-    else if (!std::strcmp(key, "strip_blocks")) c->tune.strip_blocks = value > 0 ? value : 0;
-    else if (!std::strcmp(key, "pair_strips")) c->tune.pair_strips = value < 0 ? -1 : (value ? 1 : 0);
-    else if (!std::strcmp(key, "col_groups")) c->tune.col_groups = value > 0 ? value : 0;
-    else if (!std::strncmp(key, "model_", 6)) {  // constants of the plan's cost model (hadi_plan.h)
-        struct { const char *k; int HadiTuning::*f; } const tab[] = {
-            {"model_strip_row_ns", &HadiTuning::strip_row_ns}, {"model_ring_row_ps", &HadiTuning::ring_row_ps}, {"model_ring_fixed_ns", &HadiTuning::ring_fixed_ns},
-            {"model_pstrip_row_ns", &HadiTuning::pstrip_row_ns}, {"model_pring_row_ps", &HadiTuning::pring_row_ps}, {"model_pring_fixed_ns", &HadiTuning::pring_fixed_ns}};
-        bool hit = false;
-        for (auto &e : tab)
-            if (!std::strcmp(key, e.k)) { if (value < 1) return fail(c, HADI_ERR_INVALID, "%s must be positive", key); c->tune.*(e.f) = value; hit = true; }
-        if (!hit) return fail(c, HADI_ERR_INVALID, "unknown tuning key '%s'", key);
-    }
-    else if (!std::strcmp(key, "small_waves")) {
-        if (value != 0 && value != 4 && value != 8) return fail(c, HADI_ERR_INVALID, "small_waves must be 0, 4 or 8");
-        c->tune.small_waves = value;
-    } else if (!std::strcmp(key, "graph_captures") || !std::strcmp(key, "graph_replays") || !std::strcmp(key, "graph_drops") ||
-               !std::strcmp(key, "graph_evictions")) {
-        return fail(c, HADI_ERR_INVALID, "'%s' is a read-only counter", key);
-    } else return fail(c, HADI_ERR_INVALID, "unknown tuning key '%s'", key);
+    if (graph_counter(c, key)) return fail(c, HADI_ERR_INVALID, "'%s' is a read-only counter", key);
+    const HadiTuneKey *e = hadi_tuning_key(key);
+    if (!e) return fail(c, HADI_ERR_INVALID, "unknown tuning key '%s'", key);
+    const char *refused = hadi_tuning_set(c->t, *e, value);
+    if (refused) return fail(c, HADI_ERR_INVALID, refused, key);
+    if (e->f == &HadiHandleTuning::team_launch) c->team_failed = 0;
     return HADI_OK;
 }
 
 int hadi_get_tuning(const hadi_ctx *ctx, const char *key, int *value) {
     const Ctx *c = reinterpret_cast<const Ctx *>(ctx);
     if (!c || !key || !value) return HADI_ERR_INVALID;
-    if (!std::strcmp(key, "graph")) *value = c->use_graph;
-    else if (!std::strcmp(key, "small_grid")) *value = c->use_small;
-    else if (!std::strcmp(key, "small_seq")) *value = c->small_seq;
-    else if (!std::strcmp(key, "small_sch")) *value = c->small_sch;
-    else if (!std::strcmp(key, "american_p")) *value = c->use_amp;
-    else if (!std::strcmp(key, "device_vgrid")) *value = c->device_vgrid;
-    else if (!std::strcmp(key, "sub_batch")) *value = c->sub_batch;
-    else if (!std::strcmp(key, "small_pairs")) *value = c->small_pairs;
-    else if (!std::strcmp(key, "streams")) *value = c->streams;
-    else if (!std::strcmp(key, "col_prefetch")) *value = c->col_prefetch;
-    else if (!std::strcmp(key, "cs_strips")) *value = c->cs_strips;
-    else if (!std::strcmp(key, "graph_max_melems")) *value = c->graph_max_melems;
-    else if (!std::strcmp(key, "tile_interleave")) *value = c->tile_il;
-    else if (!std::strcmp(key, "strip")) *value = c->tune.strip;
-    else if (!std::strcmp(key, "debug_fault")) *value = c->debug_fault;
-    else if (!std::strcmp(key, "team_launch")) *value = c->team_failed ? -2 : c->team_launch;
-    else if (!std::strcmp(key, "resident_sweep")) *value = c->resident_sweep;
-    else if (!std::strcmp(key, "row_tile")) *value = c->tune.row_tile;
-    else if (!std::strcmp(key, "strip_blocks")) *value = c->tune.strip_blocks;
-    else if (!std::strcmp(key, "pair_strips")) *value = c->tune.pair_strips;
-    else if (!std::strcmp(key, "col_groups")) *value = c->tune.col_groups;
-    else if (!std::strcmp(key, "model_strip_row_ns")) *value = c->tune.strip_row_ns;
-    else if (!std::strcmp(key, "model_ring_row_ps")) *value = c->tune.ring_row_ps;
-    else if (!std::strcmp(key, "model_ring_fixed_ns")) *value = c->tune.ring_fixed_ns;
-    else if (!std::strcmp(key, "model_pstrip_row_ns")) *value = c->tune.pstrip_row_ns;
-    else if (!std::strcmp(key, "model_pring_row_ps")) *value = c->tune.pring_row_ps;
-    else if (!std::strcmp(key, "model_pring_fixed_ns")) *value = c->tune.pring_fixed_ns;
-    else if (!std::strcmp(key, "small_waves")) *value = c->tune.small_waves;
-    else if (!std::strcmp(key, "graph_captures")) *value = (int)std::min<unsigned long long>(c->graph_captures, INT_MAX);
-    else if (!std::strcmp(key, "graph_replays")) *value = (int)std::min<unsigned long long>(c->graph_replays, INT_MAX);
-    else if (!std::strcmp(key, "graph_drops")) *value = (int)std::min<unsigned long long>(c->graph_drops, INT_MAX);
-    else if (!std::strcmp(key, "graph_evictions")) *value = (int)std::min<unsigned long long>(c->graph_evictions, INT_MAX);
-    else return HADI_ERR_INVALID;
+    const HadiTuneKey *e = hadi_tuning_key(key);
+    if (const unsigned long long *n = graph_counter(c, key)) *value = (int)std::min<unsigned long long>(*n, INT_MAX);
+    else if (!e) return HADI_ERR_INVALID;
+    else if (e->f == &HadiHandleTuning::team_launch && c->team_failed) *value = -2;
+    else *value = hadi_tuning_word(c->t, *e);
     return HADI_OK;
 }
 

@@ -2,12 +2,13 @@
 // under the host-thread wave emulator so tests can compare its logic with the oracle without a GPU.
 // Never shipped, never linked into libhadi; see wave_emu.h.
 #define HADI_EMU 1
-#include "hadi_dispatch.h"
+#include "hadi_route.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -84,6 +85,39 @@ extern "C" int emu_select(const int *in, long long *o, char *name, char *desc, i
     o[8] = sel.grid; o[9] = sel.block; o[10] = (long long)sel.smem;
     hadi_kernel_name(*sel.k, pl, name, cap);
     hadi_describe_passes(pc, desc, cap);
+    return 0;
+}
+
+// The route of a whole call (csrc/hadi_route.h: what run_sweep consumes), for tests/test_route_selection.py.  in[16]: CUs,
+// instances, m1, m2, variant, scheme, state precision (enums of hadi.h), r_d == r_f, debug, profiling, n_snap, dividends,
+// uniform_steps, team_failed, amp (the caller's payoff-shape read-back), what became of a team launch (HADI_TEAM_*); tuning:
+// "key=value,..." through the table hadi_set_tuning walks.  o[15]: status, kind, small_waves, sub-batches, two_streams,
+// fork_before, resident sub-batches, read_payoff_shape, pair_tab, need_lam_u0, need_ut, need_f32, need_v_r1_c2, need_r1,
+// graphable; subs: off, cnt, lane, resident of the first max_subs sub-batches; desc: hadi_describe_last_sweep's text.
+// Returns 0, 1 (no route: o[0] says why) or 2 (a tuning key or value the table refuses).
+extern "C" int emu_route(const int *in, double theta, const char *tuning, long long *o, int *subs, int max_subs, char *desc, int cap) {
+    HadiRouteIn ri;
+    ri.cu_count = in[0]; ri.n = in[1]; ri.m1 = in[2]; ri.m2 = in[3]; ri.variant = in[4]; ri.scheme = in[5]; ri.prec = in[6];
+    ri.theta = theta; ri.rates_equal = in[7] != 0; ri.debug = in[8]; ri.profiling = in[9] != 0; ri.n_snap = in[10];
+    ri.dividends = in[11] != 0; ri.uniform_steps = in[12] != 0; ri.team_failed = in[13] != 0;
+    for (std::string rest(tuning ? tuning : ""); !rest.empty();) {
+        const size_t comma = rest.find(','), eq = rest.find('=');
+        if (eq == std::string::npos || eq > comma) return 2;
+        const HadiTuneKey *e = hadi_tuning_key(rest.substr(0, eq).c_str());
+        if (!e || hadi_tuning_set(ri.t, *e, std::atoi(rest.c_str() + eq + 1))) return 2;
+        rest = comma == std::string::npos ? "" : rest.substr(comma + 1);
+    }
+    const HadiRoute r = hadi_route(ri);
+    o[0] = r.status;
+    if (r.status) return 1;
+    const long long v[15] = {r.status, r.kind, r.small_waves, (long long)r.bp.subs.size(), r.bp.two_streams, r.bp.fork_before, r.n_resident(),
+                             r.read_payoff_shape, r.pair_tab, r.need_lam_u0, r.need_ut, r.need_f32, r.need_v_r1_c2, r.need_r1, r.graphable};
+    std::copy(v, v + 15, o);
+    for (int k = 0; k < (int)r.bp.subs.size() && k < max_subs; k++) {
+        const int s4[4] = {r.bp.subs[k].off, r.bp.subs[k].cnt, r.bp.subs[k].lane, r.resident[k]};
+        std::copy(s4, s4 + 4, subs + 4 * k);
+    }
+    std::snprintf(desc, cap, "%s", hadi_describe_route(r, ri, in[14] != 0, in[15]).c_str());
     return 0;
 }
 
@@ -180,7 +214,7 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
                          const double *put_strikes /* NULL = call boundary data */, const int *N_i, const double *dt_i) {
     HadiPlan pl;
     if (hadi_make_plan(m1, m2, n_inst, target_waves, &pl, g_tune, scheme == 2 ? 4 : 8)) return 1;
-    if (!(theta > 0.0) || r_d == r_f) pl.use_strip = 0;  // as hadi_api.hip (no_strips): the strip kernels divide by theta dt
+    if (hadi_no_strips(theta, r_d == r_f)) pl.use_strip = 0;  // (the strip kernels divide by theta dt)
     const HadiLayout &L = pl.L;
     const int american = variant & 1, dividend = (variant >> 1) & 1;
     const size_t st = (size_t)L.inst_stride * n_inst;
@@ -234,7 +268,7 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
     if (american) emu::launch(8, 64, [&]() { hadi_payoff_shape_kernel(L, n_inst, dU0.data(), pay_mis.data()); });
     std::vector<double> dW(pl.row_seq ? st : 0);
     a.R1 = cs ? dR1.data() : pl.row_seq ? dW.data() : nullptr; a.C2 = cs ? dC2.data() : nullptr;
-    const bool pair_tab = pl.L.G == 2 && !cs && !pl.row_seq && pl.use_strip;  // as hadi_api.hip: the pairs' coupling column, built once
+    const bool pair_tab = hadi_pair_table(pl, cs) && pl.use_strip;  // the pairs' coupling column, built once
     std::vector<double> dRS(pair_tab ? (size_t)n_inst * pl.L.nrows * 128 : 0, std::nan(""));
     a.rs_tab = pair_tab ? dRS.data() : nullptr;
     HadiSweepArgs av = a;
@@ -244,8 +278,7 @@ extern "C" int emu_solve(int n_inst, int m1, int m2, int N, double dt, double th
     if (dividend) hadi_dividend_steps(N, dt, ndiv, ddates, flags.data(), N);
     if (use_small == 4) {  // instance-resident launch (hadi_team_kernel) with teams of ONE block: the emulator runs the blocks of a
                            // grid one after the other, so the team barrier is trivially met; indexing and arithmetic are real
-        if (american || cs || f32 || n_inst > 8 || L.G != 1 || (L.B != 8 && L.B != 4) || L.P > 8) return 3;
-        if (!(theta > 0.0) || r_d == r_f) return 3;  // as hadi_api.hip (team_shape): the team kernel's row step is the strips'
+        if (american || cs || f32 || !hadi_team_grid(pl, n_inst, theta, r_d == r_f)) return 3;  // (the team kernel's row step is the strips')
         std::vector<int> team(512, 0);
         HadiTeamArgs ta;
         // "team_blocks" > 1: teams of several blocks, all blocks of the grid running at once (the team barrier, the formation

@@ -20,9 +20,7 @@ extern "C" int emu_solve_resident(int n_inst, int m1, int m2, int N, double dt, 
     if (hadi_make_plan(m1, m2, n_inst, 8 * 256, &pl, tu, 8)) return 1;
     const HadiLayout &L = pl.L;
     if (P_out) *P_out = L.P;
-    if (!(theta > 0.0) || r_d == r_f || !pl.use_strip || pl.use_pairs || pl.sblocks != 1 || L.B != 8 || L.G != 1 || L.P > 8 ||
-        pl.row_seq || pl.col_seq)
-        return 3;
+    if (!hadi_resident_grid(pl, theta, r_d == r_f) || !hadi_resident_plan(pl)) return 3;
     if ((N_i || dt_i) && (!N_i || !dt_i)) return 3;
     if (put && !strike) return 3;
     int Nmax = N;
