@@ -31,7 +31,9 @@ struct HadiStripCtxT {
     const double *b2r;   // instance b2 row (global)
     int lane, rowp;
     double dt, thdt, e_nm1, e_n;
-    double c1, kap;           // 1 + theta dt r_d / 2, (1 - theta) / theta
+    double kap;               // (1 - theta) / theta
+    double cd, kim, ku;       // the diagonal of I - theta dt A1 and theta dt A1 U (hadi_strip_theta): 1 + theta dt r_d / 2, 0, 1
+                              // -- or, at a tiny theta, theta dt r_d / 2, 1, 0
     double hr0, inv0;         // i = 0 row of A1: reaction term (0 for the call) and 1 / (1 + theta dt hr0)
     double inv_dt;            // P representation: 1 / dt and the (lane, slot) of the s_max node
     int m1_lane, m1_r;
@@ -41,6 +43,25 @@ struct HadiStripCtxT {
     int debug;
     HADI_STAMP_ACC
 };
+
+// The strip step takes theta dt A1 U from the implicit diagonal: ig = cd - (il + iu), im = ig + kim, and the u0 share of
+// theta dt A1 U is fma(-ig, u0, ku u0).  With (cd, kim, ku) = (1 + theta dt r_d / 2, 0, 1) that is im = ig and (1 - im) u0: 1 - im
+// then holds il + iu - theta dt r_d / 2 to eps ABSOLUTE, and kap = (1 - theta) / theta carries that into the step as eps / theta
+// of |U|, whatever dt -- 5e-17 at theta = 0.8, 2e-7 at theta = 1e-9 (tests/test_gpu_regressions.py, the strips at a tiny theta).
+// Below HADI_STRIP_TINY_THETA the triple is (theta dt r_d / 2, 1, 0): -ig = il + iu - theta dt r_d / 2 is formed on its own and
+// im = 1 + ig from it.  Above it the old triple keeps every bit of the step as it was (x + 0 and 1 x are exact).
+#ifndef HADI_STRIP_TINY_THETA
+#define HADI_STRIP_TINY_THETA 1e-3
+#endif
+template <class T>
+HADI_DEV HADI_FORCEINLINE void hadi_strip_theta(HadiStripCtxT<T> &c, const HadiInstPar &ip) {
+    const bool tiny = ip.thdt < HADI_STRIP_TINY_THETA * ip.dt;
+    const double hrd = ip.thdt * ip.half_rd;
+    c.cd = hadi_uniform_d(tiny ? hrd : 1.0 + hrd);
+    c.kim = hadi_uniform_d(tiny ? 1.0 : 0.0);
+    c.ku = hadi_uniform_d(tiny ? 0.0 : 1.0);
+    c.kap = hadi_uniform_d((ip.dt - ip.thdt) / ip.thdt);  // the host keeps theta = 0 off the strip kernels
+}
 
 // Pair rendezvous flags in LDS (G = 2 strips and the shared ring): release store / acquire load at workgroup scope.
 HADI_DEV HADI_FORCEINLINE void hadi_flag_store(int *f, int v) {
@@ -140,7 +161,7 @@ HADI_DEV HADI_FORCEINLINE void hadi_strip_step(const HadiStripCtxT<T> &c, int j,
     constexpr int c0slot = 64 * B * G;
     constexpr int NB = B - 1;
     HADI_STAMP_DECL(c.stamp_acc_)
-    const double dt = c.dt, thdt = c.thdt, c1 = c.c1, kap = c.kap, e_nm1 = c.e_nm1, e_n = c.e_n;
+    const double dt = c.dt, thdt = c.thdt, cd = c.cd, kim = c.kim, ku = c.ku, kap = c.kap, e_nm1 = c.e_nm1, e_n = c.e_n;
     HadiSchK k{};  // MCS / HV (hadi_sch_ka ...): the scheme's scalars, formed per step
     if constexpr (SCH != HADI_SCH_CS) k = hadi_sch_consts<SCH>(dt, thdt);
     // rt = the entries RC_L2 .. RC_WPS of the row's table entry (HADI_SRC0): wm, wz, wp are the SCALED A0 v-weights,
@@ -336,9 +357,10 @@ HADI_DEV HADI_FORCEINLINE void hadi_strip_step(const HadiStripCtxT<T> &c, int j,
         double il = fma(-vth, Dm[r], Bm[r]);
         iu[r] = fma(-vth, Dp[r], Bp[r]);
         const double sm = il + iu[r];
-        const double im = c1 - sm;  // 1 + theta dt (lo + up + r_d / 2)
-        // theta dt A1 U = -il uL - iu uR + (1 - im) u0   (c1 - c2 = 1)
-        const double T1 = fma(-iu[r], uR, fma(-il, uL, fma(-im, u0r, u0r)));
+        const double ig = cd - sm;    // im, or im - 1 at a tiny theta (hadi_strip_theta)
+        const double im = ig + kim;   // 1 + theta dt (lo + up + r_d / 2)
+        // theta dt A1 U = -il uL - iu uR + (1 - im) u0
+        const double T1 = fma(-iu[r], uR, fma(-il, uL, fma(-ig, u0r, ku * u0r)));
         const double A0U = Bm[r] * tl - (Bm[r] + Bp[r]) * tt[r] + Bp[r] * tr;
         double y;
         if constexpr (MODE == 2) {
@@ -680,7 +702,7 @@ HADI_DEV HADI_FORCEINLINE void hadi_pair_step(const HadiStripCtxT<double> &c, in
     constexpr int B = 8, NB = 7, c0slot = 256;
     const int lane = c.lane;
     const bool first = (h == 0);
-    const double dt = c.dt, thdt = c.thdt, c1 = c.c1, kap = c.kap, e_nm1 = c.e_nm1, e_n = c.e_n;
+    const double dt = c.dt, thdt = c.thdt, cd = c.cd, kim = c.kim, ku = c.ku, kap = c.kap, e_nm1 = c.e_nm1, e_n = c.e_n;
     const double vth = rv[RC_VTH - HADI_SRC0];
     const double wm = rv[RC_WMS - HADI_SRC0], wz = rv[RC_WZS - HADI_SRC0], wp = rv[RC_WPS - HADI_SRC0];
     const double a2l2 = rv[RC_L2 - HADI_SRC0], a2l1 = rv[RC_L1 - HADI_SRC0], a2m = rv[RC_M - HADI_SRC0], a2u1 = rv[RC_U1 - HADI_SRC0],
@@ -771,8 +793,9 @@ HADI_DEV HADI_FORCEINLINE void hadi_pair_step(const HadiStripCtxT<double> &c, in
         double il = fma(-vth, Dm[r], Bm[r]);  // (Bm, Bp hold -theta dt (r_d - r_f) s beta_s: hadi_strip_step)
         iu[r] = fma(-vth, Dp[r], Bp[r]);
         const double sm = il + iu[r];
-        const double im = c1 - sm;
-        const double T1 = fma(-iu[r], uR, fma(-il, uL, fma(-im, u0[r], u0[r])));
+        const double ig = cd - sm;  // (hadi_strip_theta)
+        const double im = ig + kim;
+        const double T1 = fma(-iu[r], uR, fma(-il, uL, fma(-ig, u0[r], ku * u0[r])));
         const double A0U = Bm[r] * tl - (Bm[r] + Bp[r]) * tt[r] + Bp[r] * tr;
         double S = A0U + A2U[r];
         if constexpr (LAST) S += b2v[r] * e_nm1;
@@ -970,8 +993,7 @@ __global__ void __launch_bounds__(64 * HADI_PAIR_WAVES, 2) hadi_pass_a_pairs(Had
         return;
     }
     c.dt = hadi_uniform_d(ip.dt); c.thdt = hadi_uniform_d(ip.thdt);
-    c.c1 = hadi_uniform_d(1.0 + ip.thdt * ip.half_rd);
-    c.kap = hadi_uniform_d((ip.dt - ip.thdt) / ip.thdt);
+    hadi_strip_theta(c, ip);
     c.hr0 = hadi_uniform_d(ip.hr0); c.inv0 = hadi_uniform_d(1.0 / (1.0 + ip.thdt * ip.hr0));
     c.e_nm1 = hadi_uniform_d(exp(ip.bc_rate * ip.dt * (n - 1)));  // device_solver.hpp:238
     c.e_n = hadi_uniform_d(exp(ip.bc_rate * ip.dt * n));          // device_solver.hpp:246

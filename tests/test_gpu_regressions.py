@@ -325,3 +325,46 @@ def test_grids_beyond_1024_s_intervals_or_527_v_intervals(solver, m1, m2, N, n, 
     assert np.abs(U - Uo).max() < 1e-10 * np.abs(Uo).max()
     if american:
         assert np.abs(lam - lo).max() < 1e-8 * max(1.0, np.abs(lo).max())
+
+
+# ---- the strips at a tiny theta (tests/test_gpu_time_regimes.py, regime T7) ----------------------------------------------------
+@pytest.mark.parametrize("name,m1,m2,n,tuning,kernel", [
+    ("strips", 300, 80, 4, {"strip": 1, "team_launch": 0, "resident_sweep": 0, "small_grid": 0}, "hadi_pass_a_strip<8,EU>"),
+    ("pairs", 200, 60, 4, {"strip": 1, "pair_strips": 1, "team_launch": 0, "resident_sweep": 0, "small_grid": 0}, "hadi_pass_a_pairs<EU>"),
+    ("paired_strips", 600, 40, 4, {"strip": 1, "team_launch": 0, "resident_sweep": 0, "small_grid": 0}, "hadi_pass_a_strip<8,EU,double,2>"),
+    ("team", 300, 140, 3, {"team_launch": 1}, "hadi_team_kernel<8>"),
+    ("resident", 300, 80, 256, {"resident_sweep": 1}, "hadi_sweep_resident<8>")])
+def test_strip_step_at_theta_1e_minus_9(solver, name, m1, m2, n, tuning, kernel):
+    """theta = 1e-9, dt = 1e-6, N = 3: hadi_strip_step formed theta dt A1 U from the implicit diagonal, (1 - im) u0 with
+    im = fl(1 + theta dt r_d / 2 - (il + iu)), which keeps 1 - im to eps ABSOLUTE, and carried it into the step with
+    kap = (1 - theta) / theta: an error of eps / theta of |U| whatever dt.  Under the wave emulator, before the fix, against
+    the oracle (itself <= 1e-13 from its binary128 twin there): strips 3.6e-7, pairs 3.5e-7, paired strips 3.6e-7, team kernel
+    3.6e-7 (1.0e-6 with dividends), resident sweep 3.6e-7 of max|U|, the shared-ring and LDS kernels 2e-16 .. 7e-16; at
+    theta = 0.8 the same term is 5e-17 and nothing showed.  Below theta = 1e-3 the step now forms il + iu - theta dt r_d / 2 on
+    its own and im from it (hadi_strip_theta; above it every bit stays what it was): <= 2e-15 on the same cases.  Every
+    strip-step kernel, full field at the project's 1e-10."""
+    from oracle import oracle as O
+    if name in ("team", "resident") and solver.device_info()["compute_units"] != 256:
+        pytest.skip("needs the 256-CU device")
+    theta, dt, N = 1e-9, 1e-6, 3
+    strikes = Cm.well_conditioned_strikes(m1, n)
+    grids = H.GridViewsBatch.for_strikes(m1, m2, Cm.S_0, Cm.V_0, strikes)
+    Cm.assert_well_conditioned(grids.Delta_s, grids.Delta_v)
+    U0 = grids.call_payoff(strikes)
+    U = U0.copy()
+    defaults = {"strip": -1, "pair_strips": -1, "team_launch": -1, "resident_sweep": -1, "small_grid": 1}
+    for k, v in tuning.items():
+        solver.set_tuning(k, v)
+    try:
+        solver.DO_timestepping(m1, m2, N, dt, theta, Cm.R_D, 0.01, Cm.RHO, Cm.SIGMA, Cm.KAPPA, Cm.ETA, grids, U)
+        path = solver.describe_last_sweep()
+    finally:
+        for k in tuning:
+            solver.set_tuning(k, defaults[k])
+    assert kernel in path, path
+    p = O.make_params(m1, m2, N, dt, theta, Cm.R_D, 0.01, Cm.RHO, Cm.SIGMA, Cm.KAPPA, Cm.ETA, O.EU)
+    Uo, _, _ = O.solve_batch(p, grids.Vec_s, grids.Vec_v, grids.Delta_s, grids.Delta_v, U0, U0, threads=16)
+    assert np.isfinite(Uo).all() and np.abs(Uo - U0).max() > 1e-5 * np.abs(Uo).max()  # (the three steps moved the field)
+    e = (np.abs(U - Uo).max(axis=1) / np.abs(Uo).max(axis=1)).max()
+    print("%s at theta 1e-9: field error %.3e of max|U_ref|" % (name, e))
+    assert e <= 1e-10, e
