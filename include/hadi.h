@@ -26,6 +26,8 @@
  *                                      v-row of V_0, from the state the sweep leaves on the device
  *   hadi_maturity_ladder, hadi_compute_{base_prices,jacobian}_ladder <- no counterpart: the price node after chosen steps of ONE sweep
  *                                      (a whole maturity ladder per strike on a shared delta_t)
+ *   hadi_bermudan_timestepping, hadi_compute_{base_prices,jacobian}_bermudan <- no counterpart: the European sweep with exercise
+ *                                      on chosen steps (U <- max(U, payoff) at their end)
  *   hadi_make_grid / hadi_rebuild_variance <- Grid::Grid (src/grid.cpp:16-61),
  *                                      GridViews::rebuild_variance_views (src/grid_pod.hpp:25-73)
  *
@@ -216,7 +218,7 @@ int hadi_get_timing(const hadi_ctx *ctx, hadi_timing *out);
  *                 (profiles/r08_small_sch_ab.txt)
  *   "graph"       hipGraph replay of the time loop for small batches (default 1).  The handle caches up to 8 captured loops,
  *                 keyed by everything their nodes bake in: the launch geometry of every sub-batch, the scheme, variant and
- *                 precision, the steps that carry a dividend, the snapshot steps of a ladder call, and every device address the loop uses (the library's buffers --
+ *                 precision, the steps that carry a dividend, the snapshot steps of a ladder call, the exercise steps of a Bermudan call, and every device address the loop uses (the library's buffers --
  *                 rs_tab and the fp64 packed U of an fp32-state sweep among them -- and the caller's s-grid).  Whenever a call
  *                 frees a buffer to grow it, the whole cache is dropped first, so a replay never touches freed memory.
  *                 Read-only counters, cumulative over the handle's life (hadi_get_tuning only; hadi_set_tuning returns
@@ -378,6 +380,30 @@ int hadi_compute_base_prices_ladder(hadi_ctx *ctx, const hadi_problem *p, double
                                     double *prices /* [n][n_snap] */);
 int hadi_compute_jacobian_ladder(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, int n_snap,
                                  const int *snap_steps, double *J /* [n][n_snap][5] */, double *base_prices /* [n][n_snap] */);
+
+/* Bermudan options -- NOT a reference feature.  A Bermudan sweep is the European sweep of hadi_DO_timestepping (variant HADI_EU
+ * or HADI_DIV) with one addition: after the last pass of every listed step n, every node of every instance that lists n takes
+ * U <- max(U, payoff) -- all (m1+1)(m2+1) nodes, boundary rows and columns included.  The payoff is p->U_0, or the initial p->U
+ * where U_0 is NULL.  Step n is time to maturity n delta_t_k on the instance's own clock; n = N_k is exercise at the valuation
+ * date.  A dividend acts at the START of its step, exercise at the END; a step may carry both.  With a predictor-corrector scheme
+ * the exercise follows the corrector's column pass.  lambda_bar is neither used nor written.
+ *   ex_steps  host array [ex_rows][n_ex]; ex_rows is 1 (one schedule for the batch) or n_instances.  Each row is strictly
+ *             increasing within 1 .. N_k and may end in zeros (an instance with fewer dates); with ex_rows == 1 every entry must be
+ *             <= every instance's N_k.  n_ex == 0 is the plain European call: same route, same bits.
+ * hadi_bermudan_timestepping reads and writes p exactly as hadi_DO_timestepping does (per-instance parameters, (N_i, delta_t_i), put
+ * data with strike_i, dividends, scheme, memory space).  The two launchers rebuild the v-grid and honour V_0_i exactly as
+ * hadi_compute_base_prices / hadi_compute_jacobian do, the variant from p->variant; the six groups of a Jacobian share their
+ * instance's schedule.  The LDS-resident whole-loop kernels apply the exercise inside their time loop (the payoff read from its
+ * packed global array on exercise steps only); the streaming kernels are followed by hadi_exercise_kernel on the steps that some
+ * instance lists.  A Bermudan call never takes hadi_sweep_resident or hadi_team_kernel: those batches run the streaming kernels.
+ * Errors: HADI_AM / HADI_AM_DIV or HADI_STATE_FP32: HADI_ERR_UNSUPPORTED; a bad schedule (an entry outside 1 .. N_k, not
+ * increasing, a non-zero behind a zero), ex_rows other than 1 or n, n_ex < 0: HADI_ERR_INVALID; everything the underlying entry
+ * point refuses keeps its status. */
+int hadi_bermudan_timestepping(hadi_ctx *ctx, const hadi_problem *p, int n_ex, const int *ex_steps, int ex_rows);
+int hadi_compute_base_prices_bermudan(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, int n_ex, const int *ex_steps,
+                                      int ex_rows, double *base_prices);
+int hadi_compute_jacobian_bermudan(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, int n_ex,
+                                   const int *ex_steps, int ex_rows, double *J, double *base_prices);
 
 /* v-grid rebuilt from (V_0, V = 5.0, d = 5.0/500) exactly as every call site of the reference
  * does (jacobian_computation.cpp:253); p->vec_v / p->delta_v are ignored. */

@@ -221,6 +221,50 @@ inline void compute_jacobian_ladder(Handle &h, double S_0, double V_0, double /*
                                                   base_prices.data()));
 }
 
+// Bermudan options (hadi_bermudan_timestepping and its two launchers; NOT in the reference): the European or dividend sweep with
+// U <- max(U, payoff) at the end of the listed steps.  ex_steps: [ex_rows][ex_steps.size() / ex_rows], ex_rows = 1 (one schedule
+// for the batch) or num_strikes (rows strictly increasing within 1..N, zero-padded).  The payoff is U_0, or the initial
+// workspace.U where U_0 is null; workspace.U receives the field.
+inline void bermudan_timestepping(Handle &h, int m1, int m2, int N, double delta_t, double theta, double r_d, double r_f, double rho,
+                                  double sigma, double kappa, double eta, int num_strikes, const GridViews &deviceGrids,
+                                  DO_Workspace &workspace, const std::vector<int> &ex_steps, int ex_rows = 1, int variant = HADI_EU,
+                                  const std::vector<double> *U_0 = nullptr, const Dividends *div = nullptr,
+                                  const PutStrikes *put = nullptr) {
+    if (ex_rows < 1 || ex_steps.size() % (size_t)ex_rows) throw std::runtime_error("ex_steps is not [ex_rows][n_ex]");
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  workspace.U.data(), U_0 ? U_0->data() : nullptr, div, put);
+    detail::check(h, hadi_bermudan_timestepping(h.ctx, &p, (int)(ex_steps.size() / ex_rows), ex_steps.data(), ex_rows));
+}
+// ... with the v-grid rebuilt for V_0 and the price pick, as compute_base_prices does
+inline void compute_base_prices_bermudan(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho,
+                                         double sigma, double kappa, double eta, int m1, int m2, int /*total_size*/, int N,
+                                         double theta, double delta_t, int num_strikes, const GridViews &deviceGrids,
+                                         DO_Workspace &workspace, const std::vector<int> &ex_steps, std::vector<double> &base_prices,
+                                         int ex_rows = 1, int variant = HADI_EU, const std::vector<double> *U_0 = nullptr,
+                                         const Dividends *div = nullptr, const PutStrikes *put = nullptr) {
+    if (ex_rows < 1 || ex_steps.size() % (size_t)ex_rows) throw std::runtime_error("ex_steps is not [ex_rows][n_ex]");
+    base_prices.resize(num_strikes);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  workspace.U.data(), U_0 ? U_0->data() : nullptr, div, put);
+    detail::check(h, hadi_compute_base_prices_bermudan(h.ctx, &p, S_0, V_0, (int)(ex_steps.size() / ex_rows), ex_steps.data(), ex_rows,
+                                                       base_prices.data()));
+}
+// J: [num_strikes][5], base_prices: [num_strikes]; the six solves of an instance share its schedule
+inline void compute_jacobian_bermudan(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho,
+                                      double sigma, double kappa, double eta, int m1, int m2, int /*total_size*/, int N, double theta,
+                                      double delta_t, int num_strikes, const GridViews &deviceGrids, const std::vector<double> &U_0,
+                                      const std::vector<int> &ex_steps, std::vector<double> &J, std::vector<double> &base_prices,
+                                      double eps = 1e-6, int ex_rows = 1, int variant = HADI_EU, const Dividends *div = nullptr,
+                                      const PutStrikes *put = nullptr) {
+    if (ex_rows < 1 || ex_steps.size() % (size_t)ex_rows) throw std::runtime_error("ex_steps is not [ex_rows][n_ex]");
+    J.resize((size_t)num_strikes * 5);
+    base_prices.resize(num_strikes);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  nullptr, U_0.data(), div, put);
+    detail::check(h, hadi_compute_jacobian_bermudan(h.ctx, &p, S_0, V_0, eps, (int)(ex_steps.size() / ex_rows), ex_steps.data(), ex_rows,
+                                                    J.data(), base_prices.data()));
+}
+
 // jacobian_computation.cpp:204-364 and the three variants.  J: [num_strikes][5], columns kappa, eta, sigma, rho, v0.
 inline void compute_jacobian(Handle &h, double S_0, double V_0, double, double r_d, double r_f, double rho, double sigma,
                              double kappa, double eta, int m1, int m2, int, int N, double theta, double delta_t,

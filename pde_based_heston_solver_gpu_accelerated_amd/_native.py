@@ -69,6 +69,7 @@ EXPORTS = [
     "hadi_make_grid", "hadi_rebuild_variance", "hadi_find_s_index", "hadi_find_v_index",
     "hadi_DO_timestepping", "hadi_parallel_DO_solve", "hadi_compute_greeks",
     "hadi_maturity_ladder", "hadi_compute_base_prices_ladder", "hadi_compute_jacobian_ladder",
+    "hadi_bermudan_timestepping", "hadi_compute_base_prices_bermudan", "hadi_compute_jacobian_bermudan",
     "hadi_compute_base_prices", "hadi_compute_base_prices_american",
     "hadi_compute_base_prices_dividends", "hadi_compute_base_prices_american_dividends",
     "hadi_compute_jacobian", "hadi_compute_jacobian_american",
@@ -139,6 +140,12 @@ def _load(LIB_PATH):
             getattr(L, name).argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_int, _ip, C.c_void_p]
         L.hadi_compute_jacobian_ladder.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_double, C.c_int, _ip,
                                                    C.c_void_p, C.c_void_p]
+    if hasattr(L, "hadi_bermudan_timestepping"):  # (likewise: a build from before the Bermudan entry points)
+        L.hadi_bermudan_timestepping.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_int, _ip, C.c_int]
+        L.hadi_compute_base_prices_bermudan.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_int, _ip, C.c_int,
+                                                        C.c_void_p]
+        L.hadi_compute_jacobian_bermudan.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_double, C.c_int, _ip,
+                                                     C.c_int, C.c_void_p, C.c_void_p]
     for sfx in ("", "_american", "_dividends", "_american_dividends"):
         getattr(L, "hadi_compute_base_prices" + sfx).argtypes = [
             C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_void_p]

@@ -9,6 +9,7 @@ normal equations are all-reduced (31 doubles per iteration, 1 double for the tri
     calibrate_american_dividends                test_calibration_american_dividends                :1588-2160
     calibrate_european_multi_maturity           test_calibration_european_multi_maturity           :2428-2933
     calibrate_american_dividends_multi_maturity test_calibration_american_divident_multi_maturity  :3245-3820
+    calibrate_bermudan                          no counterpart: European / dividend sweeps with exercise on chosen steps
     calibrate_european_maturity_ladder          no counterpart: all maturities of a strike from ONE sweep on a shared delta_t
 
 `solver` is anything with the mirrored launchers of solver.HestonADI (`compute_jacobian*`, `compute_base_prices*`).
@@ -314,6 +315,43 @@ def calibrate_european_maturity_ladder(solver, S_0, r_d, r_f, kappa, eta, sigma,
     return calibrate(solver, EU, S_0, None, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, None, theta, grids, U_0, market,
                      max_iter=max_iter, tol=t if tol is None else tol, delta_tol=dtol if delta_tol is None else delta_tol,
                      scheme=scheme, launchers=launch, **kw)
+
+
+def _bermudan_launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, schedule, grids, U_0, dividends, scheme=0):
+    """The closures of calibrate() over the Bermudan launchers: one instance per strike, as the single-maturity drivers."""
+    n_loc = grids.Vec_s.shape[0]
+    total_size = (m1 + 1) * (m2 + 1)
+    delta_t = T / N
+    kw = {"variant": variant, "dividends": dividends}
+    if scheme:
+        kw["scheme"] = scheme
+
+    def jac(k, e, s, r, v, eps):
+        return solver.compute_jacobian_bermudan(S_0, v, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t, n_loc, grids,
+                                                U_0, schedule, eps=eps, **kw)
+
+    def base(k, e, s, r, v):
+        ws = _WS()
+        ws.U = _clone(U_0)
+        return solver.compute_base_prices_bermudan(S_0, v, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t, n_loc,
+                                                   grids, ws, schedule, **kw)
+
+    return jac, base
+
+
+def calibrate_bermudan(solver, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0, market_prices,
+                       exercise_steps, dividends=None, max_iter=15, tol=0.1, scheme=0, **kw):
+    """calibrate_european / calibrate_dividends on Bermudan quotes: every Jacobian and trial-price solve is the European sweep
+    (with `dividends`: the dividend sweep) with exercise at the end of the steps `exercise_steps` -- a list shared by the
+    strikes, or one list per strike (solver.exercise_steps maps calendar dates to steps).  U_0 is the payoff.  scheme / theta:
+    see calibrate (without dividends only)."""
+    variant = DIV if dividends is not None and len(dividends) else EU
+    if scheme and variant != EU:
+        raise ValueError("scheme %r: the predictor-corrector schemes price European sweeps only" % (scheme,))
+    launch = _bermudan_launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, exercise_steps, grids, U_0,
+                                 dividends if variant == DIV else None, scheme=scheme)
+    return calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0, market_prices,
+                     dividends=dividends, max_iter=max_iter, tol=tol, scheme=scheme, launchers=launch, **kw)
 
 
 def calibrate_american_dividends_multi_maturity(solver, S_0, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, theta,

@@ -59,6 +59,7 @@ struct Ctx {
     DevBuf div_flag, div_amt, div_pct;
     DevBuf pay_mis;  // American: per-instance payoff-shape flags (hadi_payoff_shape_kernel)
     DevBuf order;    // small-grid path: dispatch order of the instances (multi-maturity batches)
+    DevBuf ex_flag;  // Bermudan: the exercise table, one row of Nmax flags (shared) or one per instance
     DevBuf snap_steps, snap_node, snap_out;  // maturity ladder: the snapshot steps, the instances' price nodes, the snapshots [n][n_snap]
     // Sticky device error word: one int in host-pinned, device-visible memory.  Kernels OR a HADI_DEVERR_* code into it
     // (system-scope atomic, only ever on a failure path); finish_timing reads it after the stream synchronisation every
@@ -228,6 +229,17 @@ struct SweepDesc {
     const int *snap_steps = nullptr;
     double S_0 = 0, V_0 = 0;
     const double *d_v0_i = nullptr;  // device [n] or null: per-instance V_0 of the node's v-row
+    // Bermudan (hadi_bermudan_timestepping and its launchers): n_ex > 0 = ex_steps [ex_rows][n_ex] (host array, validated: rows
+    // strictly increasing within 1 .. N_k, zero-padded) lists the steps at whose end an instance takes U <- max(U, payoff); ex_rows
+    // 1 = one schedule for the batch, else one row per source instance (instance k reads row k % n_src: a Jacobian's groups share)
+    int n_ex = 0, ex_rows = 0;
+    const int *ex_steps = nullptr;
+};
+
+// A Bermudan schedule as the entry points receive it.
+struct ExSched {
+    int n_ex, rows;
+    const int *steps;
 };
 
 // Kernels whose dynamic LDS can exceed the 64 KiB default need the limit raised once (hadi_create: every kernel of
@@ -246,6 +258,8 @@ struct Sweep {
     size_t tot = 0, st = 0;      // the packed state of the whole batch: elements, and bytes as fp64
     std::vector<char> div_step;  // step -> somebody pays a dividend at its start
     std::vector<int> snap_q;     // step -> snapshot index of a ladder call, or -1
+    std::vector<char> ex_step;   // step -> somebody may be exercised at its end (Bermudan)
+    int ex_stride = 0;           // exercise table: one shared row (0) or a row of Nmax flags per instance
     int flag_stride = 0;         // dividend table: one shared row (0) or a row of Nmax flags per instance
     bool amp = false;            // American sweeps in the P representation (hadi_row_step, AMER == 2)
     HadiSweepArgs a, av;         // whole-batch arguments; Craig-Sneyd: the predictor's column pass writes V (= Y2), the
@@ -260,6 +274,16 @@ HadiRouteIn route_in(const Ctx *c, const SweepDesc &d) {
     in.debug = d.debug; in.profiling = c->profiling != 0; in.n_snap = d.n_snap; in.dividends = d.num_div > 0;
     in.uniform_steps = d.uniform_steps; in.team_failed = c->team_failed != 0; in.t = c->t;
     return in;
+}
+
+// Bermudan: the steps of the time loop behind which hadi_exercise_kernel is launched, and their number for the route.
+void mark_exercise_steps(Sweep &w) {
+    const SweepDesc &d = w.d;
+    w.ex_step.assign(d.Nmax + 1, 0);
+    w.ex_stride = d.ex_rows > 1 ? d.Nmax : 0;
+    for (size_t e = 0; e < (size_t)d.ex_rows * d.n_ex; e++)
+        if (d.ex_steps[e] > 0) w.ex_step[d.ex_steps[e]] = 1;
+    w.in.n_ex_steps = (int)std::count(w.ex_step.begin(), w.ex_step.end(), (char)1);
 }
 
 // The choice, the launch geometry and the words are hadi_dispatch.h's (the rules: DESIGN.md section 4.1); this launches it.
@@ -277,6 +301,8 @@ int grow_buffers(Ctx *c, Sweep &w) {
     int rc;
     if ((rc = ensure(c, c->U, st)) || (rc = ensure(c, c->Y, st))) return rc;
     if (r.need_lam_u0 && ((rc = ensure(c, c->LAM, st)) || (rc = ensure(c, c->U0, st)))) return rc;
+    if (r.need_u0 && (rc = ensure(c, c->U0, st))) return rc;
+    if (r.bermudan && (rc = ensure(c, c->ex_flag, sizeof(int) * (size_t)(w.ex_stride ? d.n : 1) * d.Nmax))) return rc;
     if (r.need_ut && (rc = ensure(c, c->UT, st))) return rc;
     if (r.need_f32 && ((rc = ensure(c, c->Uf, st / 2)) || (rc = ensure(c, c->Yf, st / 2)))) return rc;
     if (r.need_v_r1_c2 && ((rc = ensure(c, c->V, st)) || (rc = ensure(c, c->R1, st)) || (rc = ensure(c, c->C2, st)))) return rc;
@@ -327,6 +353,19 @@ int stage_dividends(Ctx *c, Sweep &w) {
     return HADI_OK;
 }
 
+// Bermudan: host-built table "may instance k be exercised at the end of step n" (one shared row for one shared schedule).
+int stage_exercise(Ctx *c, const Sweep &w) {
+    const SweepDesc &d = w.d;
+    const int rows = w.ex_stride ? d.n : 1;
+    std::vector<int> flags((size_t)rows * d.Nmax, 0);
+    for (int k = 0; k < rows; k++) {
+        const int *row = d.ex_steps + (size_t)(w.ex_stride ? k % d.n_src : 0) * d.n_ex;
+        for (int q = 0; q < d.n_ex; q++)
+            if (row[q] > 0) flags[(size_t)k * d.Nmax + row[q] - 1] = 1;
+    }
+    return stage_to_device(c, c->ex_flag.p, flags.data(), flags.size() * sizeof(int));
+}
+
 // Parameters and dividend tables to the device, the operator tables (setup), the ladder's price nodes (locate), the packed
 // state and, for American sweeps, the payoff and its shape -- which decides w.amp.
 int stage_inputs(Ctx *c, Sweep &w) {
@@ -358,6 +397,11 @@ int stage_inputs(Ctx *c, Sweep &w) {
     }
 
     hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src, d.d_natU, ptr<double>(c->U));
+    if (r.bermudan) {  // the payoff, packed as the state is, and the exercise table
+        hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src,
+                           d.d_natU0 ? d.d_natU0 : d.d_natU, ptr<double>(c->U0));
+        if ((rc = stage_exercise(c, w))) return rc;
+    }
     if (r.american) {
         hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src,
                            d.d_natU0 ? d.d_natU0 : d.d_natU, ptr<double>(c->U0));
@@ -395,7 +439,7 @@ void sweep_args(Ctx *c, Sweep &w) {
         a.Y = reinterpret_cast<double *>(c->Yf.p);
     }
     a.LAM = r.american ? ptr<double>(c->LAM) : nullptr;
-    a.U0 = r.american ? ptr<double>(c->U0) : nullptr;
+    a.U0 = (r.american || r.need_u0) ? ptr<double>(c->U0) : nullptr;
     a.pay_mis = r.american ? ptr<int>(c->pay_mis) : nullptr;
     a.scoef = ptr<double>(c->scoef); a.b2row = ptr<double>(c->b2row); a.rowc = ptr<double>(c->rowc);
     a.pb = ptr<double>(c->pb); a.rinv = ptr<double>(c->rinv); a.ipar = ptr<HadiInstPar>(c->ipar);
@@ -431,6 +475,9 @@ int small_args(Ctx *c, const Sweep &w, HadiSmallArgs &sm) {
     sm.flag_stride = w.flag_stride;
     if (w.r.have_div) {
         sm.div_flag = ptr<int>(c->div_flag); sm.div_amounts = ptr<double>(c->div_amt); sm.div_pcts = ptr<double>(c->div_pct);
+    }
+    if (w.r.bermudan) {
+        sm.ex_flag = ptr<int>(c->ex_flag); sm.ex_stride = w.ex_stride;
     }
     if (w.r.ladder) {
         sm.snap_steps = ptr<int>(c->snap_steps); sm.n_snap = d.n_snap;
@@ -543,7 +590,7 @@ int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
     const HadiSweepArgs a = sub_args(w, w.a, o, nsb, sp), av = sub_args(w, w.av, o, nsb, sp);
     const size_t tot = (size_t)L.inst_stride * nsb, st = tot * sizeof(double);  // the sub-batch's packed state
     double *const Ub = ptr<double>(c->U) + so, *const LAMb = r.american ? ptr<double>(c->LAM) + so : nullptr;
-    double *const U0b = r.american ? ptr<double>(c->U0) + so : nullptr, *const UTb = r.dividend ? ptr<double>(c->UT) + so : nullptr;
+    double *const U0b = (r.american || r.need_u0) ? ptr<double>(c->U0) + so : nullptr, *const UTb = r.dividend ? ptr<double>(c->UT) + so : nullptr;
     const int ev0 = 4 * sb * d.Nmax;  // profiling events of this sub-batch
     int rc;
     if (r.pair_tab && sp.use_strip) {  // paired strips: the pairs' coupling column, once per solve (hadi_strip_step, RSTAB)
@@ -589,6 +636,11 @@ int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
         if (kev) HIP_TRY(c, hipEventRecord(kev[3], q));
         if (cs) {  // corrector (profiling events cover the predictor's two passes only)
             if ((rc = launch_pass(c, hadi_select_row_pass(pc, 2), q, av, nstep)) || (rc = launch_pass(c, col, q, a, nstep))) return rc;
+        }
+        if (r.bermudan && w.ex_step[nstep]) {  // Bermudan exercise behind the step's last column pass (European sweeps: U is explicit)
+            const int bpi = hadi_exercise_bpi(L);
+            hipLaunchKernelGGL(hadi_exercise_kernel, dim3((unsigned)nsb * bpi), dim3(HADI_EX_THREADS), 0, q, L, nsb, bpi, Ub, U0b,
+                               ptr<int>(c->ex_flag) + (size_t)o * w.ex_stride, w.ex_stride, nstep);
         }
         if (r.ladder && w.snap_q[nstep] >= 0)  // (U is explicit here: a ladder call never runs in the P representation)
             hipLaunchKernelGGL(hadi_snap_kernel, dim3((nsb + 63) / 64), dim3(64), 0, q, L, nsb, Ub, ptr<int>(c->snap_node) + o,
@@ -669,6 +721,13 @@ std::string graph_key(const Ctx *c, const Sweep &w) {
         put(&d.n_snap, sizeof(int));
         put(d.snap_steps, sizeof(int) * d.n_snap);
     }
+    if (w.r.bermudan) {  // the per-instance table is re-uploaded every call; the node list only depends on which steps carry an
+                         // exercise launch, on the table's address and on its stride (the payoff's address is in both argument blocks)
+        const void *ex[] = {c->ex_flag.p};
+        put(ex, sizeof(ex));
+        put(&w.ex_stride, sizeof(int));
+        put(w.ex_step.data(), w.ex_step.size());
+    }
     if (w.r.have_div) {  // amounts / percentages / per-instance tables are re-uploaded every call; the node list
                          // only depends on which steps carry a dividend launch
         put(&w.flag_stride, sizeof(int));
@@ -733,6 +792,7 @@ int run_streaming(Ctx *c, Sweep &w, bool team_fell_back) {
 
 int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     Sweep w{d, route_in(c, d)};
+    mark_exercise_steps(w);
     w.r = hadi_route(w.in);
     if (w.r.status == HADI_ROUTE_BAD_GRID)
         return fail(c, HADI_ERR_UNSUPPORTED, "grid %dx%d not supported (need m1 >= 2, m2 >= 3 and (m1 + 16)(m2 + 1) < 2^28)", d.m1, d.m2);
@@ -880,6 +940,32 @@ int check_ladder(Ctx *c, const hadi_problem *p, int n_snap, const int *snap_step
     return HADI_OK;
 }
 
+// What the Bermudan entry points ask beyond check_problem (which has passed).
+int check_bermudan(Ctx *c, const hadi_problem *p, const ExSched &ex) {
+    if (p->variant == HADI_AM || p->variant == HADI_AM_DIV)
+        return fail(c, HADI_ERR_UNSUPPORTED, "a Bermudan sweep is the European sweep (HADI_EU or HADI_DIV) with exercise steps");
+    if (p->state_precision == HADI_STATE_FP32) return fail(c, HADI_ERR_UNSUPPORTED, "Bermudan sweeps need the fp64 state");
+    if (ex.n_ex < 0) return fail(c, HADI_ERR_INVALID, "n_ex must be >= 0");
+    if (ex.rows != 1 && ex.rows != p->n_instances) return fail(c, HADI_ERR_INVALID, "ex_rows must be 1 or n_instances");
+    if (ex.n_ex > 0 && !ex.steps) return fail(c, HADI_ERR_INVALID, "ex_steps missing");
+    for (int k = 0; k < ex.rows; k++) {
+        int Nk = p->N_i ? p->N_i[k] : p->N;
+        if (ex.rows == 1 && p->N_i)  // one schedule for the batch: within every instance's time loop
+            for (int z = 0; z < p->n_instances; z++) Nk = std::min(Nk, p->N_i[z]);
+        const int *row = ex.steps + (size_t)k * ex.n_ex;
+        for (int q = 0; q < ex.n_ex; q++) {
+            if (row[q] == 0) {
+                for (int z = q + 1; z < ex.n_ex; z++)
+                    if (row[z] != 0) return fail(c, HADI_ERR_INVALID, "ex_steps row %d: entry %d is non-zero behind a zero", k, z);
+                break;
+            }
+            if (row[q] < 1 || row[q] > Nk || (q && row[q] <= row[q - 1]))
+                return fail(c, HADI_ERR_INVALID, "ex_steps row %d must be strictly increasing within 1..%d (entry %d is %d)", k, Nk, q, row[q]);
+        }
+    }
+    return HADI_OK;
+}
+
 // Fills the per-instance parameter rows for `groups` copies of the caller's batch.
 void fill_par(const hadi_problem *p, SweepDesc &d, int groups) {
     const int n0 = p->n_instances;
@@ -931,9 +1017,11 @@ int rebuild_v_device(Ctx *c, int n, int m2, const std::vector<double> &v0i) {
 // Ladder (n_snap > 0; hadi_maturity_ladder, hadi_compute_base_prices_ladder): prices_out is [n][n_snap], the snapshots the sweep
 // took on the way; p->U and p->lambda_bar are not written.
 int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, double S_0, double V_0, double *prices_out,
-                 int debug = 0, int debug_step = 1, double *debug_out = nullptr, int n_snap = 0, const int *snap_steps = nullptr) {
+                 int debug = 0, int debug_step = 1, double *debug_out = nullptr, int n_snap = 0, const int *snap_steps = nullptr,
+                 const ExSched *ex = nullptr) {
     int rc = check_problem(c, p, true, !rebuild_v);
     if (rc) return rc;
+    if (ex && (rc = check_bermudan(c, p, *ex))) return rc;
     const bool ladder = n_snap > 0 || snap_steps;
     if (ladder && (rc = check_ladder(c, p, n_snap, snap_steps, prices_out))) return rc;
     if (debug && !debug_out) return fail(c, HADI_ERR_INVALID, "output array missing");
@@ -988,6 +1076,7 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
         d.n_snap = n_snap; d.snap_steps = snap_steps; d.S_0 = S_0; d.V_0 = V_0;
         d.d_v0_i = per_inst_v0 ? ptr<double>(c->v0_i) : nullptr;
     }
+    if (ex && ex->n_ex > 0) { d.n_ex = ex->n_ex; d.ex_rows = ex->rows; d.ex_steps = ex->steps; }
 
     HadiPlan pl;
     if ((rc = run_sweep(c, d, pl))) return rc;
@@ -1159,9 +1248,10 @@ int jacobian_grids(Ctx *c, const hadi_problem *p, int G, double V_0, double eps,
 // group 0 = base, 1..4 = kappa, eta, sigma, rho + eps, 5 = v-grid rebuilt for V_0 + eps.
 // Ladder (n_snap > 0; hadi_compute_jacobian_ladder): J [n][n_snap][5] and base_prices [n][n_snap] from the snapshots of the 6n solves.
 int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double eps, double *J, double *base_prices,
-                    int n_snap = 0, const int *snap_steps = nullptr) {
+                    int n_snap = 0, const int *snap_steps = nullptr, const ExSched *ex = nullptr) {
     int rc = check_problem(c, p, false, false);
     if (rc) return rc;
+    if (ex && (rc = check_bermudan(c, p, *ex))) return rc;
     const bool ladder = n_snap > 0 || snap_steps;
     if (ladder && (rc = check_ladder(c, p, n_snap, snap_steps, (J && base_prices) ? J : nullptr))) return rc;
     DeviceGuard guard(c->device);
@@ -1191,6 +1281,7 @@ int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, doubl
     if (ladder) {
         d.n_snap = n_snap; d.snap_steps = snap_steps; d.S_0 = S_0; d.V_0 = V_0; d.d_v0_i = ptr<double>(c->v0_i);
     }
+    if (ex && ex->n_ex > 0) { d.n_ex = ex->n_ex; d.ex_rows = ex->rows; d.ex_steps = ex->steps; }
 
     HadiPlan pl;
     if ((rc = run_sweep(c, d, pl))) return rc;
@@ -1240,7 +1331,7 @@ void release_handle(Ctx *c) {
                       &c->rinv, &c->rwork, &c->ipar, &c->par8, &c->g_s, &c->g_v, &c->g_ds, &c->g_dv, &c->src_v,
                       &c->src_dv, &c->sel_a, &c->sel_b, &c->v0_i, &c->natU, &c->natU0, &c->natOut, &c->prices,
                       &c->status, &c->div_flag, &c->div_amt, &c->div_pct, &c->V, &c->R1, &c->C2, &c->pay_mis, &c->Uf, &c->Yf,
-                      &c->order, &c->lm31, &c->team, &c->rs_tab, &c->snap_steps, &c->snap_node, &c->snap_out};
+                      &c->order, &c->lm31, &c->team, &c->rs_tab, &c->snap_steps, &c->snap_node, &c->snap_out, &c->ex_flag};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &g : c->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
@@ -1536,6 +1627,26 @@ int hadi_compute_jacobian_ladder(hadi_ctx *ctx, const hadi_problem *p, double S_
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
     return jacobian_common(c, p, S_0, V_0, eps, J, base_prices, n_snap, snap_steps);
+}
+
+// ---- Bermudan: the European sweep with U <- max(U, payoff) at the end of the listed steps --------------------
+int hadi_bermudan_timestepping(hadi_ctx *ctx, const hadi_problem *p, int n_ex, const int *ex_steps, int ex_rows) {
+    const ExSched ex{n_ex, ex_rows, ex_steps};
+    return solve_common(reinterpret_cast<Ctx *>(ctx), p, false, false, 0.0, 0.0, nullptr, 0, 1, nullptr, 0, nullptr, &ex);
+}
+
+int hadi_compute_base_prices_bermudan(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, int n_ex, const int *ex_steps,
+                                      int ex_rows, double *base_prices) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && !base_prices) return fail(c, HADI_ERR_INVALID, "base_prices missing");
+    const ExSched ex{n_ex, ex_rows, ex_steps};
+    return solve_common(c, p, true, true, S_0, V_0, base_prices, 0, 1, nullptr, 0, nullptr, &ex);
+}
+
+int hadi_compute_jacobian_bermudan(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, int n_ex,
+                                   const int *ex_steps, int ex_rows, double *J, double *base_prices) {
+    const ExSched ex{n_ex, ex_rows, ex_steps};
+    return jacobian_common(reinterpret_cast<Ctx *>(ctx), p, S_0, V_0, eps, J, base_prices, 0, nullptr, &ex);
 }
 
 HADI_VARIANT_WRAPPERS(american, HADI_AM)

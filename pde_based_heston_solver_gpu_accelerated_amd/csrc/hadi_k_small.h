@@ -26,6 +26,10 @@ struct HadiSmallArgs {
     int n_snap = 0;
     const int *snap_node = nullptr;
     double *snap_out = nullptr;
+    // Bermudan exercise (hadi_bermudan_timestepping; nullptr = none): instance k takes U <- max(U, payoff) at the END of step n
+    // where ex_flag[k*ex_stride + n-1] != 0 (ex_stride 0 = one shared row).  The payoff is HadiSweepArgs::U0 (packed, global).
+    const int *ex_flag = nullptr;
+    int ex_stride = 0;
 };
 
 // The ladder's running cursor of a whole-loop kernel: wave-uniform (kernel arguments and the step counter only).  `next` is the
@@ -225,6 +229,12 @@ __global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, Had
             }
         }
         __syncthreads();
+        if constexpr (!AMER) {  // Bermudan exercise at the end of the step (European sweeps only; block-uniform)
+            if (hadi_ex_listed(sm.ex_flag, sm.ex_stride, inst, n)) {
+                hadi_exercise_lds<B>(Ul, rowp, false, a.U0 + (size_t)inst * a.L.inst_stride, nrows, m1, rowp, tid, NT);
+                __syncthreads();
+            }
+        }
         // maturity ladder: nothing writes U before the next barrier (the row pass reads it, a dividend copies it to Y first)
         if (n == snap.next) {
             if (tid == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
@@ -588,6 +598,10 @@ __global__ void __launch_bounds__(64) hadi_small_seq_kernel(HadiSweepArgs a, Had
             }
         }
         __syncthreads();
+        if (hadi_ex_listed(sm.ex_flag, sm.ex_stride, inst, n)) {  // Bermudan exercise at the end of the step (wave-uniform)
+            hadi_exercise_lds<B>(Ul, PL, true, a.U0 + (size_t)inst * a.L.inst_stride, nrows, m1, rowp, lane, 64);
+            __syncthreads();
+        }
         // maturity ladder: lane 0 reads the node before it stores anything of the next step (one wavefront: nobody else has yet)
         if (n == snap.next) {
             if (lane == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
@@ -923,6 +937,14 @@ __global__ void __launch_bounds__(64) hadi_small_seq2_kernel(HadiSweepArgs a, Ha
             }
         }
         __syncthreads();
+        // Bermudan exercise at the end of the step, instance by instance: each on its own schedule and within its own N
+        for (int h = 0; h < (has1 ? 2 : 1); h++) {
+            const int ih = h ? inst1 : inst0, Nh = h ? N1 : N0;
+            if (n <= Nh && hadi_ex_listed(sm.ex_flag, sm.ex_stride, ih, n)) {  // (wave-uniform)
+                hadi_exercise_lds<B>(h ? base1 : base0, PL, true, a.U0 + (size_t)ih * a.L.inst_stride, nrows, m1, rowp, lane, 64);
+                __syncthreads();
+            }
+        }
         // maturity ladder: one lane per instance reads its node before it stores anything of the next step
         if (n == snap.next) {
             if (jl == 0 && (half == 0 || has1) && n <= Nl)

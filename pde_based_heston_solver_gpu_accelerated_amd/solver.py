@@ -406,6 +406,78 @@ class HestonADI:
             self._raise(rc)
         return J.reshape(num_strikes, steps.size, 5), base.reshape(-1, steps.size)
 
+    # ---- Bermudan options (hadi_bermudan_timestepping and its launchers; no reference counterpart) --------------
+    @staticmethod
+    def _schedule(exercise_steps):
+        """(int32 array [rows][n_ex], rows, n_ex) of a schedule given as a list of steps (one schedule for the batch) or a
+        ragged list of lists (one per instance, padded with zeros here)."""
+        ex = list(exercise_steps)
+        if ex and all(np.ndim(r) == 1 for r in ex):
+            width = max(len(r) for r in ex)
+            a = np.zeros((len(ex), width), dtype=np.int32)
+            for k, r in enumerate(ex):
+                a[k, :len(r)] = np.asarray(r, dtype=np.int32)
+        else:
+            a = np.asarray(ex, dtype=np.int32).reshape(1, -1)
+        a = np.ascontiguousarray(a)
+        return a, int(a.shape[0]), int(a.shape[1])
+
+    def bermudan_timestepping(self, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U, exercise_steps,
+                              variant=EU, U_0=None, dividends=None, per_instance=None, scheme=0, option_type=CALL, strikes=None):
+        """DO_timestepping (variant EU or DIV) with exercise: after the last pass of every step of `exercise_steps` every node
+        of the instances that list it takes U <- max(U, payoff); the payoff is U_0, or the initial U where U_0 is None.
+        exercise_steps: a list of step indices (one schedule for the batch; step n is time to maturity n delta_t, n = N the
+        valuation date) or a list of lists, one per instance.  An empty schedule is the plain European call.  U is updated
+        in place."""
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U=U, U_0=U_0,
+                          dividends=dividends, per_instance=per_instance, scheme=scheme, option_type=option_type, strikes=strikes)
+        ex, rows, n_ex = self._schedule(exercise_steps)
+        rc = self._lib.hadi_bermudan_timestepping(self._h, C.byref(p), n_ex, ex.ctypes.data_as(_ip), rows)
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return U
+
+    def compute_base_prices_bermudan(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                     num_strikes, deviceGrids, workspace, exercise_steps, variant=EU, U_0=None, dividends=None,
+                                     per_instance=None, scheme=0):
+        """compute_base_prices* (the v-grid rebuilt for V_0 or per_instance['V_0_i']) of Bermudan options: [n] prices at
+        (S_0, V_0).  workspace.U is the initial condition (and the payoff where U_0 is None) and receives the field."""
+        option_type, strikes = self._option(per_instance)
+        if total_size != (m1 + 1) * (m2 + 1):
+            raise ValueError("total_size != (m1+1)*(m2+1)")
+        if deviceGrids.Vec_s.shape[0] != num_strikes:
+            raise ValueError("num_strikes does not match the grid batch")
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=workspace.U,
+                          U_0=U_0, dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
+                          option_type=option_type, strikes=strikes)
+        ex, rows, n_ex = self._schedule(exercise_steps)
+        out, optr = self._out(num_strikes, 1, workspace.U)
+        rc = self._lib.hadi_compute_base_prices_bermudan(self._h, C.byref(p), float(S_0), float(V_0), n_ex,
+                                                         ex.ctypes.data_as(_ip), rows, optr)
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return out
+
+    def compute_jacobian_bermudan(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                  num_strikes, deviceGrids, U_0, exercise_steps, eps=1e-6, variant=EU, dividends=None,
+                                  per_instance=None, scheme=0):
+        """compute_jacobian* of Bermudan options: (J [n][5], base_prices [n]); the six solves of an instance share its
+        schedule, U_0 is the initial condition and the payoff."""
+        if total_size != (m1 + 1) * (m2 + 1):
+            raise ValueError("total_size != (m1+1)*(m2+1)")
+        option_type, strikes = self._option(per_instance)
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=None, U_0=U_0,
+                          dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
+                          option_type=option_type, strikes=strikes)
+        ex, rows, n_ex = self._schedule(exercise_steps)
+        J, jptr = self._out(num_strikes, 5, U_0)
+        base, bptr = self._out(num_strikes, 1, U_0)
+        rc = self._lib.hadi_compute_jacobian_bermudan(self._h, C.byref(p), float(S_0), float(V_0), float(eps), n_ex,
+                                                      ex.ctypes.data_as(_ip), rows, jptr, bptr)
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return J, base
+
     # ---- compute_base_prices* (src/jacobian_computation.cpp:368, 629, 922, 1232) ---------------
     def _base_prices(self, variant, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N,
                      theta, delta_t, num_strikes, deviceGrids, workspace, U_0=None, dividends=None,
@@ -531,6 +603,24 @@ class HestonADI:
         return self._base_prices(AM_DIV, S_0, V_0, None, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N,
                                  theta, dt, total_calibration_size, deviceGrids, workspace, U_0=U_0,
                                  dividends=dividends, per_instance=per)
+
+
+def exercise_steps(T, delta_t, dates):
+    """Step indices of calendar exercise dates: date t (time from the valuation date, 0 <= t < T) is time to maturity T - t,
+    i.e. step (T - t) / delta_t of the sweep; t = 0 is step N.  Returns them strictly increasing.  Raises ValueError when a
+    date is further than 1e-9 T from a step, outside [0, T), or listed twice."""
+    steps = []
+    for t in dates:
+        x = (float(T) - float(t)) / float(delta_t)
+        n = int(round(x))
+        if abs(n * float(delta_t) - (float(T) - float(t))) > 1e-9 * float(T):
+            raise ValueError("exercise date %r is not on the time grid (T = %r, delta_t = %r)" % (t, T, delta_t))
+        if n < 1 or n * float(delta_t) > float(T) * (1 + 1e-9):
+            raise ValueError("exercise date %r is outside [0, T)" % (t,))
+        steps.append(n)
+    if len(set(steps)) != len(steps):
+        raise ValueError("an exercise date is listed twice")
+    return sorted(steps)
 
 
 # ---- LM linear algebra (host; jacobian_computation.cpp:20-195) -------------------------------------
