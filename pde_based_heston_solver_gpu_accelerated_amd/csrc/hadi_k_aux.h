@@ -106,29 +106,8 @@ __global__ void __launch_bounds__(256) hadi_dividend_kernel(HadiLayout L, int n_
         const double amount = div_amounts[dv], pct = div_pcts[dv];
         const double *__restrict__ s = vec_s + inst * (m1 + 1);
         const double *__restrict__ src = UT + inst * L.inst_stride + (size_t)j * L.rowp;
-        const double old_s = s[i];
-        const double new_s = old_s * (1.0 - pct) - amount;
-        // ex-dividend spot <= 0: a call is worth 0 (device_solver.hpp:499-503), a put its s = 0 value
-        double out = ipar[inst].put ? src[hadi_pos(L, 0)] : 0.0;
-        if (new_s > 0) {
-            // idx = first k in [0, m1] with s[k] > new_s, 0 if none
-            int lo = 0, hi = m1 + 1;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (s[mid] > new_s) hi = mid;
-                else lo = mid + 1;
-            }
-            const int idx = (lo <= m1) ? lo : 0;
-            if (idx > 0) {
-                const double s_low = s[idx - 1], s_high = s[idx];
-                const double weight = (new_s - s_low) / (s_high - s_low);
-                const double val_low = src[hadi_pos(L, idx - 1)], val_high = src[hadi_pos(L, idx)];
-                out = (1.0 - weight) * val_low + weight * val_high;
-            } else {
-                out = src[hadi_pos(L, 0)];
-            }
-        }
-        U[inst * L.inst_stride + (size_t)j * L.rowp + hadi_pos(L, i)] = out;
+        U[inst * L.inst_stride + (size_t)j * L.rowp + hadi_pos(L, i)] =
+            hadi_dividend_jump(s, m1, amount, pct, ipar[inst].put, i, [&](int k) { return src[hadi_pos(L, k)]; });
     }
 }
 

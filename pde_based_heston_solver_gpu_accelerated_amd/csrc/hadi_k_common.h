@@ -485,3 +485,32 @@ HADI_DEV HADI_FORCEINLINE void hadi_lds_row(const double *lrow, int lane, double
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// Discrete dividend jump (device_solver.hpp:448-504): the value of node i of a v-row after the jump, from the row BEFORE it.
+// vs: the instance's s-grid (m1 + 1 ascending nodes); val(k): the pre-jump value of node k of the same row, wherever the
+// caller keeps its copy.  The ex-dividend spot is new_s = s_i (1 - pct) - amount; the reference's linear search "first k with
+// s_k > new_s" is a binary search; the value is interpolated linearly between nodes k - 1 and k, and is node 0's where no node
+// lies above new_s or new_s lies below node 0.  new_s <= 0: a call is worth 0 (device_solver.hpp:499-503), a put its s = 0 value.
+template <class Val>
+HADI_HD inline double hadi_dividend_jump(const double *vs, int m1, double amount, double pct, int put, int i, Val val) {
+    const double new_s = vs[i] * (1.0 - pct) - amount;
+    double out = put ? val(0) : 0.0;
+    if (new_s > 0) {
+        int lo = 0, hi = m1 + 1;  // first k in [0, m1] with s[k] > new_s (m1 + 1 if none)
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (vs[mid] > new_s) hi = mid;
+            else lo = mid + 1;
+        }
+        const int idx = (lo <= m1) ? lo : 0;
+        if (idx > 0) {
+            const double s_low = vs[idx - 1], s_high = vs[idx];
+            const double weight = (new_s - s_low) / (s_high - s_low);
+            out = (1.0 - weight) * val(idx - 1) + weight * val(idx);
+        } else {
+            out = val(0);
+        }
+    }
+    return out;
+}

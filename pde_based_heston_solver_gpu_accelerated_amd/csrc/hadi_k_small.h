@@ -1,4 +1,8 @@
-// hadi_k_small.h -- LDS-resident kernels of the calibration-size grids (hadi_small_kernel, hadi_small_seq_kernel, hadi_small_seq2_kernel).
+// hadi_k_small.h -- LDS-resident kernels of the calibration-size grids: hadi_small_kernel (a block of 4 or 8 wavefronts per
+// instance, the big-grid row step on LDS rows) and hadi_small_seq_kernel / hadi_small_seq2_kernel (one wavefront per instance /
+// per pair of instances, lines solved sequentially).  The two sequential kernels include one row sweep (hadi_k_lds_row_body.h) and
+// take the rest from hadi_k_lds_seq.h (stage-in / stage-out, the lane's row-table entry, the back substitution, the column
+// sweep); the dividend jump's value of all three is hadi_dividend_jump (hadi_k_common.h).
 // Part of libhadi's device code: include through hadi_kernels.h (which fixes the order).
 #pragma once
 
@@ -130,25 +134,8 @@ __global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, Had
             for (int e = tid; e < nrows * (m1 + 1); e += NT) {
                 const int j = e / (m1 + 1), i = e - j * (m1 + 1);
                 const double *src = Yl + (size_t)j * rowp;
-                const double new_s = vs[i] * (1.0 - pct) - amount;
-                double out = ip.put ? src[c0slot] : 0.0;  // ex-dividend spot <= 0: a call is worth 0 (device_solver.hpp:499-503), a put its s = 0 value
-                if (new_s > 0) {
-                    int lo = 0, hi = m1 + 1;  // first k with s[k] > new_s (0 if none)
-                    while (lo < hi) {
-                        const int mid = (lo + hi) >> 1;
-                        if (vs[mid] > new_s) hi = mid;
-                        else lo = mid + 1;
-                    }
-                    const int idx = (lo <= m1) ? lo : 0;
-                    if (idx > 0) {
-                        const double s_low = vs[idx - 1], s_high = vs[idx];
-                        const double weight = (new_s - s_low) / (s_high - s_low);
-                        out = (1.0 - weight) * src[hadi_pos(B, G, idx - 1)] + weight * src[hadi_pos(B, G, idx)];
-                    } else {
-                        out = src[c0slot];
-                    }
-                }
-                Ul[(size_t)j * rowp + hadi_pos(B, G, i)] = out;
+                Ul[(size_t)j * rowp + hadi_pos(B, G, i)] =
+                    hadi_dividend_jump(vs, m1, amount, pct, ip.put, i, [&](int k) { return src[hadi_pos(B, G, k)]; });
             }
             __syncthreads();
         }
@@ -302,41 +289,19 @@ __global__ void __launch_bounds__(64) hadi_small_seq_kernel(HadiSweepArgs a, Had
     double *coefl = smem + Ls.off_coef;  // [i][4]: Bm, Bp, Dm, Dp of node i
     double *b2l = smem + Ls.off_b2;
     double *ptab = smem + Ls.off_ptab;   // [k][5]: L, L2, Q, C, C2
-    double *__restrict__ Ug = a.U + (size_t)inst * a.L.inst_stride;
 
     for (int e = lane; e < Ls.total; e += 64) smem[e] = 0.0;
     __syncthreads();
-    for (int e = lane; e < nrows * (m1 + 1); e += 64) {
-        const int j = e / (m1 + 1), i = e - j * (m1 + 1);
-        Ul[j * PL + i] = Ug[(size_t)j * rowp + hadi_pos(B, 1, i)];
-    }
-    {
-        const double *__restrict__ sc = a.scoef + (size_t)inst * 4 * 64 * B;
-        for (int e = lane; e < 4 * (m1 + 1); e += 64) {
-            const int i = e >> 2, k = e & 3;
-            coefl[e] = (i >= 1) ? sc[k * 64 * B + hadi_pos(B, 1, i)] : 0.0;
-        }
-        const double *__restrict__ b2g = a.b2row + (size_t)inst * rowp;
-        for (int i = lane; i <= m1; i += 64) b2l[i] = b2g[hadi_pos(B, 1, i)];
-        const double *__restrict__ pg = a.pb + (size_t)inst * a.L.nrows_pad * HADI_PBW;
-        for (int e = lane; e < nrows * 5; e += 64) ptab[e] = pg[(e / 5) * HADI_PBW + e % 5];
-    }
+    hadi_lds_stage_in<B>(smem, Ls, a, inst, lane);
     // this lane's v-row: its table entry stays in registers for the whole time loop
     const int j = lane;
     const bool act = j < nrows;
     const bool last = (j == nrows - 1);
-    double v = 0.0, wm = 0.0, wz = 0.0, wp = 0.0, a2l2 = 0.0, a2l1 = 0.0, a2m = 0.0, a2u1 = 0.0, a2u2 = 0.0, b1val = 0.0;
-    int b1col = -1;
-    bool b1_at0 = false;
-    if (act) {
-        const double *__restrict__ rc = a.rowc + ((size_t)inst * nrows + j) * HADI_RC;
-        v = rc[RC_V]; wm = rc[RC_WM]; wz = rc[RC_WZ]; wp = rc[RC_WP];
-        a2l2 = rc[RC_L2]; a2l1 = rc[RC_L1]; a2m = rc[RC_M]; a2u1 = rc[RC_U1]; a2u2 = rc[RC_U2];
-        b1val = rc[RC_B1VAL];
-        const int b1raw = (int)rc[RC_B1COL];
-        b1_at0 = b1raw == 0 || b1raw >= HADI_B1_BOTH;  // (two entries on one v-row: m2 > m1 only)
-        b1col = b1raw >= HADI_B1_BOTH ? b1raw - HADI_B1_BOTH : b1raw;
-    }
+    const HadiLdsRowTab tab = hadi_lds_row_table(a, inst, j, act);
+    const double v = tab.v, wm = tab.wm, wz = tab.wz, wp = tab.wp, a2l2 = tab.a2l2, a2l1 = tab.a2l1, a2m = tab.a2m, a2u1 = tab.a2u1,
+                 a2u2 = tab.a2u2, b1val = tab.b1val;
+    const int b1col = tab.b1col;
+    const bool b1_at0 = tab.b1_at0;
     const double dt = ip.dt, thdt = ip.thdt, qd = ip.q, half_rd = ip.half_rd;
     const double inv0 = 1.0 / (1.0 + ip.thdt * ip.hr0);
     const double *urow = Ul + (act ? j : 0) * PL;  // (idle lanes walk row 0 and store nothing)
@@ -369,25 +334,8 @@ __global__ void __launch_bounds__(64) hadi_small_seq_kernel(HadiSweepArgs a, Had
             for (int e = lane; e < nrows * (m1 + 1); e += 64) {
                 const int jj = e / (m1 + 1), i = e - jj * (m1 + 1);
                 const double *src = Yl + jj * PL;
-                const double new_s = vs[i] * (1.0 - pct) - amount;
-                double out = ip.put ? src[0] : 0.0;  // ex-dividend spot <= 0: a call is worth 0 (device_solver.hpp:499-503), a put its s = 0 value
-                if (new_s > 0) {
-                    int lo = 0, hi = m1 + 1;  // first k with s[k] > new_s (0 if none)
-                    while (lo < hi) {
-                        const int mid = (lo + hi) >> 1;
-                        if (vs[mid] > new_s) hi = mid;
-                        else lo = mid + 1;
-                    }
-                    const int idx = (lo <= m1) ? lo : 0;
-                    if (idx > 0) {
-                        const double s_low = vs[idx - 1], s_high = vs[idx];
-                        const double weight = (new_s - s_low) / (s_high - s_low);
-                        out = (1.0 - weight) * src[idx - 1] + weight * src[idx];
-                    } else {
-                        out = src[0];
-                    }
-                }
-                Ul[jj * PL + i] = out;
+                Ul[jj * PL + i] =
+                    hadi_dividend_jump(vs, m1, amount, pct, ip.put, i, [&](int k) { return src[k]; });
             }
             __syncthreads();
         }
@@ -406,197 +354,11 @@ __global__ void __launch_bounds__(64) hadi_small_seq_kernel(HadiSweepArgs a, Had
         const bool rowrun = act;
 #endif
         if (rowrun) {
-        // column i = 0 (A0 and A1 rows are zero there; only A2 and the boundary act)
-        const double c00 = urow[0];
-        double c0m2, c0m1, c0p1, c0p2;
-        col5(c00, c0m2, c0m1, c0p1, c0p2);
-        // first interior column, raw: rows j-2 .. j+2
-        double r_0 = urow[1], r_m2, r_m1, r_p1, r_p2;
-        col5(r_0, r_m2, r_m1, r_p1, r_p2);
-        double yout_c0, x0;
-        {
-            const double a2c0 = a2l2 * c0m2 + a2l1 * c0m1 + a2m * c00 + a2u1 * c0p1 + a2u2 * c0p2;
-            const double b1c0 = b1_at0 ? b1val : 0.0;
-            const double b2c0 = b2p[0];
-            const double a1c0 = -ip.hr0 * c00;  // A1 row 0: empty for the call (hr0 = 0), the reaction term for the put
-            double y0c0 = c00 + dt * (a2c0 + a1c0 + (b1c0 + b2c0) * e_nm1);
-            y0c0 = y0c0 + thdt * (b1c0 * e_n - (a1c0 + b1c0 * e_nm1));
-            const double c2c0 = thdt * (b2c0 * e_n - (a2c0 + b2c0 * e_nm1));
-            x0 = y0c0 * inv0;  // A1 row 0 is decoupled: the identity for the call (hes_a1_kernels.hpp:56-61)
-            yout_c0 = x0 + c2c0;
-        }
-        hadi_wave_rendezvous();  // (emulator: everyone has read column 0 and 1 before c' overwrites column 0)
-        double u_prev = c00, u_cur = r_0;
-        double t_prev = wm * c0m1 + wz * c00 + wp * c0p1;
-        double t_cur = wm * r_m1 + wz * r_0 + wp * r_p1;
-        double a2u_cur = fma(a2u2, r_p2, fma(a2l2, r_m2, a2l1 * r_m1 + a2m * r_0 + a2u1 * r_p1));
-        double b2c = b2p[1];
-        double corr_cur = thdt * (b2c * e_n - (a2u_cur + b2c * e_nm1));
-        // raw values of column 2 (column m1 + 1 is the zero spare)
-        r_0 = urow[2];
-        col5(r_0, r_m2, r_m1, r_p1, r_p2);
-        // x_0 is known and moves to the right-hand side of node 1: with ys_0 = x_0 and c'_0 = 0 the general step does exactly
-        // that (pivot im - il 0, right-hand side y - il x_0)
-        double cp_prev = 0.0, ys_prev = x0;
-        // One node of the sweep.  On entry r_* hold the raw column i + 1; `cB`, `cD` are node i's coefficients, `b2n` the b2
-        // entry of node i + 1.  The caller refills r_* with column i + 2 afterwards.
-        auto node = [&](int i, const double2 cB, const double2 cD, const double b2n) {
-            const double u_next = r_0;
-            const double t_next = wm * r_m1 + wz * r_0 + wp * r_p1;
-            const double a2u_next = fma(a2u2, r_p2, fma(a2l2, r_m2, a2l1 * r_m1 + a2m * r_0 + a2u1 * r_p1));
-            const double lo = fma(v, cD.x, qd * cB.x);
-            const double up = fma(v, cD.y, qd * cB.y);
-            const double mn = -((lo + up) + half_rd);
-            const double A1U = lo * u_prev + mn * u_cur + up * u_next;
-            const double A0U = cB.x * t_prev - (cB.x + cB.y) * t_cur + cB.y * t_next;
-            // Y0 = U + dt (A0U + A1U + A2U + b e_{n-1}) + theta dt (b1 e_n - (A1U + b1 e_{n-1})), device_solver.hpp:236-250
-            double S = A0U + A1U + a2u_cur;
-            S += b2c * e_nm1;
-            double y = fma(dt, S, u_cur);
-            y = fma(-thdt, A1U, y);
-            y += (i == b1col) ? b1l : 0.0;
-            const double il = -thdt * lo;
-            const double im = 1.0 - thdt * mn;
-            const double iu = -thdt * up;
-            const double inv = hadi_rcp(fma(-il, cp_prev, im));
-            const double cp = iu * inv;
-            const double ys = fma(-il, ys_prev, y) * inv;
-            const double corr_next = thdt * (b2n * e_n - (a2u_next + b2n * e_nm1));
-            yrow[i] = ys + corr_cur + cp * corr_next;  // g_i  (c'_{m1} = 0: the row ends there)
-            crow[i - 1] = cp;
-            u_prev = u_cur; u_cur = u_next;
-            t_prev = t_cur; t_cur = t_next;
-            a2u_cur = a2u_next; corr_cur = corr_next; b2c = b2n;
-            cp_prev = cp; ys_prev = ys;
-        };
-        // Rounds of FOUR nodes: the own-row values of the columns i + 2 .. i + 5, the four nodes' coefficients and b2 entries
-        // are all read first -- 16 independent LDS reads behind ONE wait -- then the four dependent steps run without touching
-        // the LDS return path.  (Round 2 read five rows' values per node and waited for each node's coefficient and b2 reads:
-        // ~900 LDS instructions per time step, and at the six wavefronts per CU that the 26 KB of an instance allow, the CU's
-        // one LDS pipe was the busiest unit.)  Column indices reach i + 5 <= m1 + 2: the two zero spare columns of the pitch.
-        int i = 1;
-        for (; i + 3 <= m1; i += 4) {
-            double Rm2[4], Rm1[4], R0[4], Rp1[4], Rp2[4], b2q[4];
-            double2 cBq[4], cDq[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                R0[q] = urow[i + 2 + q];
-                cBq[q] = *reinterpret_cast<const double2 *>(coefl + 4 * (i + q));
-                cDq[q] = *reinterpret_cast<const double2 *>(coefl + 4 * (i + q) + 2);
-                b2q[q] = b2p[i + 1 + q];  // (entry m1 + 1 is zero)
-            }
-#if !defined(HADI_EMU)
-            asm volatile("" ::: "memory");  // (the reads stay in front of the four steps' stores)
-#endif
-            hadi_wave_rendezvous();  // (emulator: every lane has read its columns before anybody's c' lands in them)
-#pragma unroll
-            for (int q = 0; q < 4; q++) col5(R0[q], Rm2[q], Rm1[q], Rp1[q], Rp2[q]);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                node(i + q, cBq[q], cDq[q], b2q[q]);
-                r_m2 = Rm2[q]; r_m1 = Rm1[q]; r_0 = R0[q]; r_p1 = Rp1[q]; r_p2 = Rp2[q];
-                hadi_wave_rendezvous();  // (emulator: the lanes walk in lock step on the GPU)
-            }
-        }
-        for (; i <= m1; i++) {  // the last m1 mod 4 nodes, one at a time
-            const double n_0 = urow[i + 2];  // (column <= m1 + 2: a zero column)
-            double n_m2, n_m1, n_p1, n_p2;
-            col5(n_0, n_m2, n_m1, n_p1, n_p2);
-            const double2 cB = *reinterpret_cast<const double2 *>(coefl + 4 * i);      // Bm, Bp
-            const double2 cD = *reinterpret_cast<const double2 *>(coefl + 4 * i + 2);  // Dm, Dp
-            const double b2n = b2p[i + 1];
-            hadi_wave_rendezvous();
-            node(i, cB, cD, b2n);
-            r_m2 = n_m2; r_m1 = n_m1; r_0 = n_0; r_p1 = n_p1; r_p2 = n_p2;
-            hadi_wave_rendezvous();  // (emulator: the lanes walk in lock step on the GPU)
-        }
-        // back substitution on the output itself: Y_i = g_i - c'_i Y_{i+1}
-        {   // (idle lanes walk their dummy row)
-            double Yn = yrow[m1];
-            int i = m1 - 1;
-            for (; i >= 8; i -= 8) {  // eight nodes per round: 16 independent LDS reads, then the dependent FMAs
-                double g[8], cq[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) { g[q] = yrow[i - q]; cq[q] = crow[i - q - 1]; }
-#if !defined(HADI_EMU)
-                asm volatile("" ::: "memory");
-#endif
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    Yn = fma(-cq[q], Yn, g[q]);
-                    yrow[i - q] = Yn;
-                }
-            }
-            for (; i >= 1; i--) {
-                Yn = fma(-crow[i - 1], Yn, yrow[i]);
-                yrow[i] = Yn;
-            }
-            yrow[0] = yout_c0;
-        }
+#include "hadi_k_lds_row_body.h"
         }  // (rowrun)
         __syncthreads();
-        // ---- column pass: lane <-> s-column, sequential pentadiagonal sweeps (hes_a2_shuffled_kernels.hpp:243-299) ----
-        // (measured and left out, 50x25 x3000: fetching a node's coefficients one iteration ahead 2.64 -> 2.72 ms; the column
-        // held in 33 registers with all loads up front 2.64 -> 2.88 ms)
-        for (int col = lane; col <= m1; col += 64) {
-            // eight rows per round: the independent LDS reads first, then the dependent recurrence
-            double ym1 = 0.0, ym2 = 0.0;
-            int k = 0;
-            for (; k + 8 <= nrows; k += 8) {
-                double yv[8], tL[8], tL2[8], tQ[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) {  // (the round's table entries with its column values: 32 reads, one wait)
-                    const double *t = ptab + (k + q) * 5;
-                    yv[q] = Yl[(k + q) * PL + col];
-                    tL[q] = t[PB_L]; tL2[q] = t[PB_L2]; tQ[q] = t[PB_Q];
-                }
-#if !defined(HADI_EMU)
-                asm volatile("" ::: "memory");
-#endif
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const double yk = (yv[q] - tL[q] * ym1 - tL2[q] * ym2) * tQ[q];
-                    Yl[(k + q) * PL + col] = yk;
-                    ym2 = ym1;
-                    ym1 = yk;
-                }
-            }
-            for (; k < nrows; k++) {
-                const double *t = ptab + k * 5;
-                const double yk = (Yl[k * PL + col] - t[PB_L] * ym1 - t[PB_L2] * ym2) * t[PB_Q];
-                Yl[k * PL + col] = yk;
-                ym2 = ym1;
-                ym1 = yk;
-            }
-            double xp1 = 0.0, xp2 = 0.0;
-            k = nrows - 1;
-            for (; k >= 7; k -= 8) {
-                double yv[8], tC[8], tC2[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const double *t = ptab + (k - q) * 5;
-                    yv[q] = Yl[(k - q) * PL + col];
-                    tC[q] = t[PB_C]; tC2[q] = t[PB_C2];
-                }
-#if !defined(HADI_EMU)
-                asm volatile("" ::: "memory");
-#endif
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const double xk = yv[q] - tC[q] * xp1 - tC2[q] * xp2;
-                    xp2 = xp1;
-                    xp1 = xk;
-                    Ul[(k - q) * PL + col] = xk;
-                }
-            }
-            for (; k >= 0; k--) {
-                const double *t = ptab + k * 5;
-                const double xk = Yl[k * PL + col] - t[PB_C] * xp1 - t[PB_C2] * xp2;
-                xp2 = xp1;
-                xp1 = xk;
-                Ul[k * PL + col] = xk;
-            }
-        }
+        // ---- column pass: lane <-> s-column ----
+        hadi_lds_penta_cols(Yl, Ul, ptab, PL, nrows, m1, lane);
         __syncthreads();
         if (hadi_ex_listed(sm.ex_flag, sm.ex_stride, inst, n)) {  // Bermudan exercise at the end of the step (wave-uniform)
             hadi_exercise_lds<B>(Ul, PL, true, a.U0 + (size_t)inst * a.L.inst_stride, nrows, m1, rowp, lane, 64);
@@ -608,10 +370,7 @@ __global__ void __launch_bounds__(64) hadi_small_seq_kernel(HadiSweepArgs a, Had
             hadi_snap_advance(sm, snap);
         }
     }
-    for (int e = lane; e < nrows * (m1 + 1); e += 64) {
-        const int jj = e / (m1 + 1), i = e - jj * (m1 + 1);
-        Ug[(size_t)jj * rowp + hadi_pos(B, 1, i)] = Ul[jj * PL + i];
-    }
+    hadi_lds_stage_out<B>(Ul, PL, a, inst, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -623,7 +382,8 @@ __global__ void __launch_bounds__(64) hadi_small_seq_kernel(HadiSweepArgs a, Had
 // per instance.  LDS: two instances' arrays per wavefront (52 KB for 50x25: three wavefronts = six instances per CU, as
 // before), but a wavefront now retires two instances' time steps in little more than the time of one.  Instances with
 // different numbers of time steps (multi-maturity batches, dispatched longest first) simply stop at their own N.
-// Needs nrows <= 32.  Same arithmetic, operation by operation, as hadi_small_seq_kernel: the results are bit-identical.
+// Needs nrows <= 32.  The row sweep is the very text hadi_small_seq_kernel compiles (hadi_k_lds_row_body.h): the results are
+// bit-identical.
 template <int B>
 __global__ void __launch_bounds__(64) hadi_small_seq2_kernel(HadiSweepArgs a, HadiSmallArgs sm) {
     HADI_DYN_SMEM(double, smem);
@@ -654,40 +414,17 @@ __global__ void __launch_bounds__(64) hadi_small_seq2_kernel(HadiSweepArgs a, Ha
 
     for (int e = lane; e < 2 * Ls.total; e += 64) smem[e] = 0.0;
     __syncthreads();
-    for (int h = 0; h < (has1 ? 2 : 1); h++) {         // (uniform loops: all 64 lanes copy one instance, then the other)
-        const int ih = h ? inst1 : inst0;
-        double *bh = h ? base1 : base0;
-        const double *__restrict__ Ug = a.U + (size_t)ih * a.L.inst_stride;
-        for (int e = lane; e < nrows * (m1 + 1); e += 64) {
-            const int j = e / (m1 + 1), i = e - j * (m1 + 1);
-            bh[j * PL + i] = Ug[(size_t)j * rowp + hadi_pos(B, 1, i)];
-        }
-        const double *__restrict__ sc = a.scoef + (size_t)ih * 4 * 64 * B;
-        for (int e = lane; e < 4 * (m1 + 1); e += 64) {
-            const int i = e >> 2, k = e & 3;
-            bh[Ls.off_coef + e] = (i >= 1) ? sc[k * 64 * B + hadi_pos(B, 1, i)] : 0.0;
-        }
-        const double *__restrict__ b2g = a.b2row + (size_t)ih * rowp;
-        for (int i = lane; i <= m1; i += 64) bh[Ls.off_b2 + i] = b2g[hadi_pos(B, 1, i)];
-        const double *__restrict__ pg = a.pb + (size_t)ih * a.L.nrows_pad * HADI_PBW;
-        for (int e = lane; e < nrows * 5; e += 64) bh[Ls.off_ptab + e] = pg[(e / 5) * HADI_PBW + e % 5];
-    }
+    for (int h = 0; h < (has1 ? 2 : 1); h++)           // (uniform loops: all 64 lanes copy one instance, then the other)
+        hadi_lds_stage_in<B>(h ? base1 : base0, Ls, a, h ? inst1 : inst0, lane);
     // this lane's v-row of its instance: the table entry stays in registers for the whole time loop
     const int j = jl;
     const bool act = j < nrows && (half == 0 || has1);
     const bool last = (j == nrows - 1);
-    double v = 0.0, wm = 0.0, wz = 0.0, wp = 0.0, a2l2 = 0.0, a2l1 = 0.0, a2m = 0.0, a2u1 = 0.0, a2u2 = 0.0, b1val = 0.0;
-    int b1col = -1;
-    bool b1_at0 = false;
-    if (act) {
-        const double *__restrict__ rc = a.rowc + ((size_t)inst * nrows + j) * HADI_RC;
-        v = rc[RC_V]; wm = rc[RC_WM]; wz = rc[RC_WZ]; wp = rc[RC_WP];
-        a2l2 = rc[RC_L2]; a2l1 = rc[RC_L1]; a2m = rc[RC_M]; a2u1 = rc[RC_U1]; a2u2 = rc[RC_U2];
-        b1val = rc[RC_B1VAL];
-        const int b1raw = (int)rc[RC_B1COL];
-        b1_at0 = b1raw == 0 || b1raw >= HADI_B1_BOTH;
-        b1col = b1raw >= HADI_B1_BOTH ? b1raw - HADI_B1_BOTH : b1raw;
-    }
+    const HadiLdsRowTab tab = hadi_lds_row_table(a, inst, j, act);
+    const double v = tab.v, wm = tab.wm, wz = tab.wz, wp = tab.wp, a2l2 = tab.a2l2, a2l1 = tab.a2l1, a2m = tab.a2m, a2u1 = tab.a2u1,
+                 a2u2 = tab.a2u2, b1val = tab.b1val;
+    const int b1col = tab.b1col;
+    const bool b1_at0 = tab.b1_at0;
     const double dt = ip.dt, thdt = ip.thdt, qd = ip.q, half_rd = ip.half_rd;
     const double inv0 = 1.0 / (1.0 + ip.thdt * ip.hr0);
     const double *urow = Ul + (act ? j : 0) * PL;  // (idle lanes walk row 0 and store nothing)
@@ -718,25 +455,8 @@ __global__ void __launch_bounds__(64) hadi_small_seq2_kernel(HadiSweepArgs a, Ha
                 for (int e = lane; e < nrows * (m1 + 1); e += 64) {
                     const int jj = e / (m1 + 1), i = e - jj * (m1 + 1);
                     const double *src = Yh + jj * PL;
-                    const double new_s = vs[i] * (1.0 - pct) - amount;
-                    double out = put_h ? src[0] : 0.0;
-                    if (new_s > 0) {
-                        int lo = 0, hi = m1 + 1;  // first k with s[k] > new_s (0 if none)
-                        while (lo < hi) {
-                            const int mid = (lo + hi) >> 1;
-                            if (vs[mid] > new_s) hi = mid;
-                            else lo = mid + 1;
-                        }
-                        const int idx = (lo <= m1) ? lo : 0;
-                        if (idx > 0) {
-                            const double s_low = vs[idx - 1], s_high = vs[idx];
-                            const double weight = (new_s - s_low) / (s_high - s_low);
-                            out = (1.0 - weight) * src[idx - 1] + weight * src[idx];
-                        } else {
-                            out = src[0];
-                        }
-                    }
-                    Uh[jj * PL + i] = out;
+                    Uh[jj * PL + i] =
+                        hadi_dividend_jump(vs, m1, amount, pct, put_h, i, [&](int k) { return src[k]; });
                 }
                 __syncthreads();
             }
@@ -756,120 +476,7 @@ __global__ void __launch_bounds__(64) hadi_small_seq2_kernel(HadiSweepArgs a, Ha
         const bool rowrun = live;
 #endif
         if (rowrun) {
-        // ---- row pass: lane <-> v-row of its instance (hadi_small_seq_kernel, operation by operation) ----
-        const double c00 = urow[0];
-        double c0m2, c0m1, c0p1, c0p2;
-        col5(c00, c0m2, c0m1, c0p1, c0p2);
-        double r_0 = urow[1], r_m2, r_m1, r_p1, r_p2;
-        col5(r_0, r_m2, r_m1, r_p1, r_p2);
-        double yout_c0, x0;
-        {
-            const double a2c0 = a2l2 * c0m2 + a2l1 * c0m1 + a2m * c00 + a2u1 * c0p1 + a2u2 * c0p2;
-            const double b1c0 = b1_at0 ? b1val : 0.0;
-            const double b2c0 = b2p[0];
-            const double a1c0 = -ip.hr0 * c00;
-            double y0c0 = c00 + dt * (a2c0 + a1c0 + (b1c0 + b2c0) * e_nm1);
-            y0c0 = y0c0 + thdt * (b1c0 * e_n - (a1c0 + b1c0 * e_nm1));
-            const double c2c0 = thdt * (b2c0 * e_n - (a2c0 + b2c0 * e_nm1));
-            x0 = y0c0 * inv0;
-            yout_c0 = x0 + c2c0;
-        }
-        hadi_wave_rendezvous();
-        double u_prev = c00, u_cur = r_0;
-        double t_prev = wm * c0m1 + wz * c00 + wp * c0p1;
-        double t_cur = wm * r_m1 + wz * r_0 + wp * r_p1;
-        double a2u_cur = fma(a2u2, r_p2, fma(a2l2, r_m2, a2l1 * r_m1 + a2m * r_0 + a2u1 * r_p1));
-        double b2c = b2p[1];
-        double corr_cur = thdt * (b2c * e_n - (a2u_cur + b2c * e_nm1));
-        r_0 = urow[2];
-        col5(r_0, r_m2, r_m1, r_p1, r_p2);
-        double cp_prev = 0.0, ys_prev = x0;
-        auto node = [&](int i, const double2 cB, const double2 cD, const double b2n) {
-            const double u_next = r_0;
-            const double t_next = wm * r_m1 + wz * r_0 + wp * r_p1;
-            const double a2u_next = fma(a2u2, r_p2, fma(a2l2, r_m2, a2l1 * r_m1 + a2m * r_0 + a2u1 * r_p1));
-            const double lo = fma(v, cD.x, qd * cB.x);
-            const double up = fma(v, cD.y, qd * cB.y);
-            const double mn = -((lo + up) + half_rd);
-            const double A1U = lo * u_prev + mn * u_cur + up * u_next;
-            const double A0U = cB.x * t_prev - (cB.x + cB.y) * t_cur + cB.y * t_next;
-            double S = A0U + A1U + a2u_cur;
-            S += b2c * e_nm1;
-            double y = fma(dt, S, u_cur);
-            y = fma(-thdt, A1U, y);
-            y += (i == b1col) ? b1l : 0.0;
-            const double il = -thdt * lo;
-            const double im = 1.0 - thdt * mn;
-            const double iu = -thdt * up;
-            const double inv = hadi_rcp(fma(-il, cp_prev, im));
-            const double cp = iu * inv;
-            const double ys = fma(-il, ys_prev, y) * inv;
-            const double corr_next = thdt * (b2n * e_n - (a2u_next + b2n * e_nm1));
-            yrow[i] = ys + corr_cur + cp * corr_next;
-            crow[i - 1] = cp;
-            u_prev = u_cur; u_cur = u_next;
-            t_prev = t_cur; t_cur = t_next;
-            a2u_cur = a2u_next; corr_cur = corr_next; b2c = b2n;
-            cp_prev = cp; ys_prev = ys;
-        };
-        int i = 1;
-        for (; i + 3 <= m1; i += 4) {
-            double Rm2[4], Rm1[4], R0[4], Rp1[4], Rp2[4], b2q[4];
-            double2 cBq[4], cDq[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                R0[q] = urow[i + 2 + q];
-                cBq[q] = *reinterpret_cast<const double2 *>(coefl + 4 * (i + q));
-                cDq[q] = *reinterpret_cast<const double2 *>(coefl + 4 * (i + q) + 2);
-                b2q[q] = b2p[i + 1 + q];
-            }
-#if !defined(HADI_EMU)
-            asm volatile("" ::: "memory");
-#endif
-            hadi_wave_rendezvous();
-#pragma unroll
-            for (int q = 0; q < 4; q++) col5(R0[q], Rm2[q], Rm1[q], Rp1[q], Rp2[q]);
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                node(i + q, cBq[q], cDq[q], b2q[q]);
-                r_m2 = Rm2[q]; r_m1 = Rm1[q]; r_0 = R0[q]; r_p1 = Rp1[q]; r_p2 = Rp2[q];
-                hadi_wave_rendezvous();
-            }
-        }
-        for (; i <= m1; i++) {
-            const double n_0 = urow[i + 2];
-            double n_m2, n_m1, n_p1, n_p2;
-            col5(n_0, n_m2, n_m1, n_p1, n_p2);
-            const double2 cB = *reinterpret_cast<const double2 *>(coefl + 4 * i);
-            const double2 cD = *reinterpret_cast<const double2 *>(coefl + 4 * i + 2);
-            const double b2n = b2p[i + 1];
-            hadi_wave_rendezvous();
-            node(i, cB, cD, b2n);
-            r_m2 = n_m2; r_m1 = n_m1; r_0 = n_0; r_p1 = n_p1; r_p2 = n_p2;
-            hadi_wave_rendezvous();
-        }
-        {   // back substitution on the output itself: Y_i = g_i - c'_i Y_{i+1}
-            double Yn = yrow[m1];
-            int ib = m1 - 1;
-            for (; ib >= 8; ib -= 8) {
-                double g[8], cq[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) { g[q] = yrow[ib - q]; cq[q] = crow[ib - q - 1]; }
-#if !defined(HADI_EMU)
-                asm volatile("" ::: "memory");
-#endif
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    Yn = fma(-cq[q], Yn, g[q]);
-                    yrow[ib - q] = Yn;
-                }
-            }
-            for (; ib >= 1; ib--) {
-                Yn = fma(-crow[ib - 1], Yn, yrow[ib]);
-                yrow[ib] = Yn;
-            }
-            yrow[0] = yout_c0;
-        }
+#include "hadi_k_lds_row_body.h"
         }  // (rowrun)
         __syncthreads();
         // ---- column pass, instance by instance: lane <-> s-column (hes_a2_shuffled_kernels.hpp:243-299) ----
@@ -877,64 +484,7 @@ __global__ void __launch_bounds__(64) hadi_small_seq2_kernel(HadiSweepArgs a, Ha
             if (n > (h ? N1 : N0)) continue;  // (wave-uniform)
             double *Uh = h ? base1 : base0, *Yh = Uh + Ls.off_y;
             const double *ptab = Uh + Ls.off_ptab;   // [k][5]: L, L2, Q, C, C2
-            for (int col = lane; col <= m1; col += 64) {
-                double ym1 = 0.0, ym2 = 0.0;
-                int k = 0;
-                for (; k + 8 <= nrows; k += 8) {
-                    double yv[8], tL[8], tL2[8], tQ[8];
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        const double *t = ptab + (k + q) * 5;
-                        yv[q] = Yh[(k + q) * PL + col];
-                        tL[q] = t[PB_L]; tL2[q] = t[PB_L2]; tQ[q] = t[PB_Q];
-                    }
-#if !defined(HADI_EMU)
-                    asm volatile("" ::: "memory");
-#endif
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        const double yk = (yv[q] - tL[q] * ym1 - tL2[q] * ym2) * tQ[q];
-                        Yh[(k + q) * PL + col] = yk;
-                        ym2 = ym1;
-                        ym1 = yk;
-                    }
-                }
-                for (; k < nrows; k++) {
-                    const double *t = ptab + k * 5;
-                    const double yk = (Yh[k * PL + col] - t[PB_L] * ym1 - t[PB_L2] * ym2) * t[PB_Q];
-                    Yh[k * PL + col] = yk;
-                    ym2 = ym1;
-                    ym1 = yk;
-                }
-                double xp1 = 0.0, xp2 = 0.0;
-                k = nrows - 1;
-                for (; k >= 7; k -= 8) {
-                    double yv[8], tC[8], tC2[8];
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        const double *t = ptab + (k - q) * 5;
-                        yv[q] = Yh[(k - q) * PL + col];
-                        tC[q] = t[PB_C]; tC2[q] = t[PB_C2];
-                    }
-#if !defined(HADI_EMU)
-                    asm volatile("" ::: "memory");
-#endif
-#pragma unroll
-                    for (int q = 0; q < 8; q++) {
-                        const double xk = yv[q] - tC[q] * xp1 - tC2[q] * xp2;
-                        xp2 = xp1;
-                        xp1 = xk;
-                        Uh[(k - q) * PL + col] = xk;
-                    }
-                }
-                for (; k >= 0; k--) {
-                    const double *t = ptab + k * 5;
-                    const double xk = Yh[k * PL + col] - t[PB_C] * xp1 - t[PB_C2] * xp2;
-                    xp2 = xp1;
-                    xp1 = xk;
-                    Uh[k * PL + col] = xk;
-                }
-            }
+            hadi_lds_penta_cols(Yh, Uh, ptab, PL, nrows, m1, lane);
         }
         __syncthreads();
         // Bermudan exercise at the end of the step, instance by instance: each on its own schedule and within its own N
@@ -952,14 +502,6 @@ __global__ void __launch_bounds__(64) hadi_small_seq2_kernel(HadiSweepArgs a, Ha
             hadi_snap_advance(sm, snap);
         }
     }
-    for (int h = 0; h < (has1 ? 2 : 1); h++) {
-        const int ih = h ? inst1 : inst0;
-        const double *bh = h ? base1 : base0;
-        double *__restrict__ Ug = a.U + (size_t)ih * a.L.inst_stride;
-        for (int e = lane; e < nrows * (m1 + 1); e += 64) {
-            const int jj = e / (m1 + 1), i = e - jj * (m1 + 1);
-            Ug[(size_t)jj * rowp + hadi_pos(B, 1, i)] = bh[jj * PL + i];
-        }
-    }
+    for (int h = 0; h < (has1 ? 2 : 1); h++) hadi_lds_stage_out<B>(h ? base1 : base0, PL, a, h ? inst1 : inst0, lane);
 }
 

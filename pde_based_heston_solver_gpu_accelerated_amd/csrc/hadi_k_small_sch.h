@@ -63,6 +63,10 @@ __global__ void __launch_bounds__(64) hadi_small_sch_kernel(HadiSweepArgs a, Had
 
     for (int e = lane; e < Ls.total; e += 64) smem[e] = 0.0;
     __syncthreads();
+    // Stage-in, the row-table load and the stage-out below are hadi_lds_stage_in / hadi_lds_row_table / hadi_lds_stage_out
+    // (hadi_k_lds_seq.h) written out: through the helpers this kernel's register allocation changed (<1,CS> 171 -> 245 VGPRs,
+    // one more wait in the MCS time loop) and MCS measured 0.6 % slower; written out the stream is the earlier one
+    // ("Small-grid kernels on shared pieces").
     for (int e = lane; e < nrows * (m1 + 1); e += 64) {
         const int j = e / (m1 + 1), i = e - j * (m1 + 1);
         Ul[j * PL + i] = Ug[(size_t)j * rowp + hadi_pos(B, 1, i)];
@@ -249,90 +253,10 @@ __global__ void __launch_bounds__(64) hadi_small_sch_kernel(HadiSweepArgs a, Had
             r_m2 = n_m2; r_m1 = n_m1; r_0 = n_0; r_p1 = n_p1; r_p2 = n_p2;
             hadi_wave_rendezvous();  // (emulator: the lanes walk in lock step on the GPU)
         }
-        // back substitution on the output itself: Y_i = g_i - c'_i Y_{i+1}
-        double Yn = yrow[m1];
-        int ib = m1 - 1;
-        for (; ib >= 8; ib -= 8) {  // eight nodes per round: 16 independent LDS reads, then the dependent FMAs
-            double g[8], cq[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) { g[q] = yrow[ib - q]; cq[q] = crow[ib - q - 1]; }
-#if !defined(HADI_EMU)
-            asm volatile("" ::: "memory");
-#endif
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                Yn = fma(-cq[q], Yn, g[q]);
-                yrow[ib - q] = Yn;
-            }
-        }
-        for (; ib >= 1; ib--) {
-            Yn = fma(-crow[ib - 1], Yn, yrow[ib]);
-            yrow[ib] = Yn;
-        }
-        yrow[0] = yout_c0;
+        hadi_lds_back_subst(yrow, crow, m1, yout_c0);
     };
-    // ---- one column sweep: lane <-> s-column, sequential pentadiagonal sweeps, Y -> UV (hadi_small_seq_kernel's) ------------
-    auto cols = [&]() {
-        for (int col = lane; col <= m1; col += 64) {
-            // eight rows per round: the independent LDS reads first, then the dependent recurrence
-            double ym1 = 0.0, ym2 = 0.0;
-            int k = 0;
-            for (; k + 8 <= nrows; k += 8) {
-                double yv[8], tL[8], tL2[8], tQ[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const double *t = ptab + (k + q) * 5;
-                    yv[q] = Yl[(k + q) * PL + col];
-                    tL[q] = t[PB_L]; tL2[q] = t[PB_L2]; tQ[q] = t[PB_Q];
-                }
-#if !defined(HADI_EMU)
-                asm volatile("" ::: "memory");
-#endif
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const double yk = (yv[q] - tL[q] * ym1 - tL2[q] * ym2) * tQ[q];
-                    Yl[(k + q) * PL + col] = yk;
-                    ym2 = ym1;
-                    ym1 = yk;
-                }
-            }
-            for (; k < nrows; k++) {
-                const double *t = ptab + k * 5;
-                const double yk = (Yl[k * PL + col] - t[PB_L] * ym1 - t[PB_L2] * ym2) * t[PB_Q];
-                Yl[k * PL + col] = yk;
-                ym2 = ym1;
-                ym1 = yk;
-            }
-            double xp1 = 0.0, xp2 = 0.0;
-            k = nrows - 1;
-            for (; k >= 7; k -= 8) {
-                double yv[8], tC[8], tC2[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const double *t = ptab + (k - q) * 5;
-                    yv[q] = Yl[(k - q) * PL + col];
-                    tC[q] = t[PB_C]; tC2[q] = t[PB_C2];
-                }
-#if !defined(HADI_EMU)
-                asm volatile("" ::: "memory");
-#endif
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const double xk = yv[q] - tC[q] * xp1 - tC2[q] * xp2;
-                    xp2 = xp1;
-                    xp1 = xk;
-                    Ul[(k - q) * PL + col] = xk;
-                }
-            }
-            for (; k >= 0; k--) {
-                const double *t = ptab + k * 5;
-                const double xk = Yl[k * PL + col] - t[PB_C] * xp1 - t[PB_C2] * xp2;
-                xp2 = xp1;
-                xp1 = xk;
-                Ul[k * PL + col] = xk;
-            }
-        }
-    };
+    // ---- one column sweep: lane <-> s-column, Y -> UV ----
+    auto cols = [&]() { hadi_lds_penta_cols(Yl, Ul, ptab, PL, nrows, m1, lane); };
 
     // Only the lanes that own a v-row run the row sweeps (the wave shifts deliver 0 from a switched-off lane).  The emulator's
     // lane threads all have to take part in its collective shuffles, so there every lane runs.

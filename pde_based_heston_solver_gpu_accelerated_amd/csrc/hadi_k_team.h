@@ -246,25 +246,7 @@ __global__ void __launch_bounds__(512, 2) hadi_team_kernel(HadiSweepArgs a, Hadi
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #endif
                     auto jump = [&](int i) -> double {
-                        const double new_s = sgrid[i] * (1.0 - pct) - amount;
-                        double out = ip.put ? drow[c0slot] : 0.0;  // ex-dividend spot <= 0: a call is worth 0, a put its s = 0 value
-                        if (new_s > 0) {
-                            int lo = 0, hi = m1 + 1;  // first k in [0, m1] with s[k] > new_s, 0 if none
-                            while (lo < hi) {
-                                const int mid = (lo + hi) >> 1;
-                                if (sgrid[mid] > new_s) hi = mid;
-                                else lo = mid + 1;
-                            }
-                            const int idx = (lo <= m1) ? lo : 0;
-                            if (idx > 0) {
-                                const double s_low = sgrid[idx - 1], s_high = sgrid[idx];
-                                const double weight = (new_s - s_low) / (s_high - s_low);
-                                out = (1.0 - weight) * drow[hadi_pos(B, 1, idx - 1)] + weight * drow[hadi_pos(B, 1, idx)];
-                            } else {
-                                out = drow[c0slot];
-                            }
-                        }
-                        return out;
+                        return hadi_dividend_jump(sgrid, m1, amount, pct, ip.put, i, [&](int k) { return drow[hadi_pos(B, 1, k)]; });
                     };
                     double nv[B];
 #pragma unroll

@@ -114,5 +114,5 @@ for n, N, m1, m2 in SHAPES:
         if scheme == H.SCHEME_CRAIG_SNEYD:
             base = best
         rel = "" if base is None or scheme < H.SCHEME_CRAIG_SNEYD else "  %+.1f %% vs CS" % (100.0 * (best / base - 1.0))
-        print("%dx%d x%d %-12s %.4f ms per step%s | %s" % (m1, m2, n, name, best / N, rel, s.describe_last_sweep()), flush=True)
+        print("%dx%d x%d %-12s %.6f ms per step%s | %s" % (m1, m2, n, name, best / N, rel, s.describe_last_sweep()), flush=True)
 s.close()
