@@ -28,6 +28,8 @@
  *                                      (a whole maturity ladder per strike on a shared delta_t)
  *   hadi_bermudan_timestepping, hadi_compute_{base_prices,jacobian}_bermudan <- no counterpart: the European sweep with exercise
  *                                      on chosen steps (U <- max(U, payoff) at their end)
+ *   hadi_barrier_timestepping, hadi_compute_{base_prices,jacobian}_barrier <- no counterpart: the European sweep with a knock-out
+ *                                      on chosen monitoring steps (U <- rebate at or beyond a barrier, at their end)
  *   hadi_make_grid / hadi_rebuild_variance <- Grid::Grid (src/grid.cpp:16-61),
  *                                      GridViews::rebuild_variance_views (src/grid_pod.hpp:25-73)
  *
@@ -218,7 +220,7 @@ int hadi_get_timing(const hadi_ctx *ctx, hadi_timing *out);
  *                 (profiles/r08_small_sch_ab.txt)
  *   "graph"       hipGraph replay of the time loop for small batches (default 1).  The handle caches up to 8 captured loops,
  *                 keyed by everything their nodes bake in: the launch geometry of every sub-batch, the scheme, variant and
- *                 precision, the steps that carry a dividend, the snapshot steps of a ladder call, the exercise steps of a Bermudan call, and every device address the loop uses (the library's buffers --
+ *                 precision, the steps that carry a dividend, the snapshot steps of a ladder call, the exercise steps of a Bermudan call, the monitoring steps of a barrier call, and every device address the loop uses (the library's buffers --
  *                 rs_tab and the fp64 packed U of an fp32-state sweep among them -- and the caller's s-grid).  Whenever a call
  *                 frees a buffer to grow it, the whole cache is dropped first, so a replay never touches freed memory.
  *                 Read-only counters, cumulative over the handle's life (hadi_get_tuning only; hadi_set_tuning returns
@@ -404,6 +406,41 @@ int hadi_compute_base_prices_bermudan(hadi_ctx *ctx, const hadi_problem *p, doub
                                       int ex_rows, double *base_prices);
 int hadi_compute_jacobian_bermudan(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, int n_ex,
                                    const int *ex_steps, int ex_rows, double *J, double *base_prices);
+
+/* Discretely monitored knock-out barrier options -- NOT a reference feature.  A barrier sweep is the sweep of hadi_DO_timestepping
+ * (variant HADI_EU or HADI_DIV) with one addition: after the last pass of every listed monitoring step n, every node (i, j) of every
+ * instance k that lists n is knocked if its spot node satisfies s_i <= lower_k or s_i >= upper_k -- touching knocks out; the
+ * comparison is on the instance's own vec_s, in fp64 -- and a knocked node takes U <- rebate_k, in every v-row, boundary rows
+ * included.  The rebate is paid at the knock-out: no discounting is applied.  Step n is time to maturity n delta_t_k on the
+ * instance's own clock; n = N_k is the valuation date.  A dividend acts at the START of its step, the barrier at its END; a step may
+ * carry both.  With a predictor-corrector scheme the knock-out follows the corrector's column pass.
+ * MODELLING STATEMENT: the boundary data of the sweep stay the vanilla option's (the Dirichlet data at s_max and the v-edges are
+ * those of the European call or put); between two monitoring dates the contract is alive everywhere.
+ * The initial condition is the caller's: monitoring AT maturity is applied to the payoff by the caller.
+ *   lower_i, upper_i, rebate_i  host arrays [n] or NULL.  NULL = no barrier on that side (-inf / +inf are allowed in the arrays and
+ *             mean the same) / a rebate of 0.  An instance may have no live node at all.
+ *   mon_steps host array [mon_rows][n_mon], the rules of ex_steps above: mon_rows is 1 or n_instances, each row strictly increasing
+ *             within 1 .. N_k and zero-padded; with one shared row every entry must be <= every instance's N_k.  n_mon == 0 is
+ *             the plain European call: same route, same bits.
+ * hadi_barrier_timestepping reads and writes p exactly as hadi_bermudan_timestepping does; the two launchers rebuild the v-grid and
+ * honour V_0_i as the Bermudan launchers do, and the six groups of a Jacobian share their instance's barrier, rebate and schedule.
+ * The LDS-resident whole-loop kernels (hadi_small_sch_kernel among them) knock their field inside the time loop; the streaming
+ * kernels are followed by hadi_knockout_kernel on the steps that some instance lists.  A barrier call never takes
+ * hadi_sweep_resident or hadi_team_kernel.
+ * Errors: HADI_AM / HADI_AM_DIV or HADI_STATE_FP32: HADI_ERR_UNSUPPORTED; a schedule that breaks the rules, a NULL barrier struct,
+ * NaN in any array, lower_k >= upper_k, both arrays NULL with n_mon > 0, a non-finite rebate, a NULL output: HADI_ERR_INVALID;
+ * everything the underlying entry point refuses keeps its status. */
+typedef struct hadi_barrier {
+    const double *lower_i, *upper_i, *rebate_i; /* host [n] or NULL */
+    int n_mon;
+    const int *mon_steps;
+    int mon_rows; /* [mon_rows][n_mon], the rules of ex_steps */
+} hadi_barrier;
+int hadi_barrier_timestepping(hadi_ctx *ctx, const hadi_problem *p, const hadi_barrier *barrier);
+int hadi_compute_base_prices_barrier(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, const hadi_barrier *barrier,
+                                     double *base_prices);
+int hadi_compute_jacobian_barrier(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps,
+                                  const hadi_barrier *barrier, double *J, double *base_prices);
 
 /* v-grid rebuilt from (V_0, V = 5.0, d = 5.0/500) exactly as every call site of the reference
  * does (jacobian_computation.cpp:253); p->vec_v / p->delta_v are ignored. */

@@ -265,6 +265,59 @@ inline void compute_jacobian_bermudan(Handle &h, double S_0, double V_0, double 
                                                     J.data(), base_prices.data()));
 }
 
+// Discretely monitored knock-out barriers (hadi_barrier_timestepping and its two launchers; NOT in the reference): the European or
+// dividend sweep with U <- rebate on the nodes at or beyond a barrier (s <= lower or s >= upper) at the end of the monitoring
+// steps.  lower / upper / rebate: one value per instance, or empty = no barrier on that side / no rebate.  mon_steps:
+// [mon_rows][mon_steps.size() / mon_rows], the rules of ex_steps above.  workspace.U is the caller's initial condition
+// (monitoring at maturity is applied to it by the caller) and receives the field.
+struct Barrier {
+    std::vector<double> lower, upper, rebate;
+    std::vector<int> mon_steps;
+    int mon_rows = 1;
+    hadi_barrier view(int num_strikes) const {
+        if (mon_rows < 1 || mon_steps.size() % (size_t)mon_rows) throw std::runtime_error("mon_steps is not [mon_rows][n_mon]");
+        for (const std::vector<double> *a : {&lower, &upper, &rebate})
+            if (!a->empty() && a->size() != (size_t)num_strikes) throw std::runtime_error("a barrier array is not [num_strikes]");
+        return hadi_barrier{lower.empty() ? nullptr : lower.data(), upper.empty() ? nullptr : upper.data(),
+                            rebate.empty() ? nullptr : rebate.data(), (int)(mon_steps.size() / mon_rows), mon_steps.data(), mon_rows};
+    }
+};
+inline void barrier_timestepping(Handle &h, int m1, int m2, int N, double delta_t, double theta, double r_d, double r_f, double rho,
+                                 double sigma, double kappa, double eta, int num_strikes, const GridViews &deviceGrids,
+                                 DO_Workspace &workspace, const Barrier &barrier, int variant = HADI_EU, const Dividends *div = nullptr,
+                                 const PutStrikes *put = nullptr) {
+    const hadi_barrier b = barrier.view(num_strikes);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  workspace.U.data(), nullptr, div, put);
+    detail::check(h, hadi_barrier_timestepping(h.ctx, &p, &b));
+}
+// ... with the v-grid rebuilt for V_0 and the price pick, as compute_base_prices does
+inline void compute_base_prices_barrier(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho,
+                                        double sigma, double kappa, double eta, int m1, int m2, int /*total_size*/, int N,
+                                        double theta, double delta_t, int num_strikes, const GridViews &deviceGrids,
+                                        DO_Workspace &workspace, const Barrier &barrier, std::vector<double> &base_prices,
+                                        int variant = HADI_EU, const Dividends *div = nullptr, const PutStrikes *put = nullptr) {
+    const hadi_barrier b = barrier.view(num_strikes);
+    base_prices.resize(num_strikes);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  workspace.U.data(), nullptr, div, put);
+    detail::check(h, hadi_compute_base_prices_barrier(h.ctx, &p, S_0, V_0, &b, base_prices.data()));
+}
+// J: [num_strikes][5], base_prices: [num_strikes]; the six solves of an instance share its barriers, rebate and schedule
+inline void compute_jacobian_barrier(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho,
+                                     double sigma, double kappa, double eta, int m1, int m2, int /*total_size*/, int N, double theta,
+                                     double delta_t, int num_strikes, const GridViews &deviceGrids, const std::vector<double> &U_0,
+                                     const Barrier &barrier, std::vector<double> &J, std::vector<double> &base_prices,
+                                     double eps = 1e-6, int variant = HADI_EU, const Dividends *div = nullptr,
+                                     const PutStrikes *put = nullptr) {
+    const hadi_barrier b = barrier.view(num_strikes);
+    J.resize((size_t)num_strikes * 5);
+    base_prices.resize(num_strikes);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  nullptr, U_0.data(), div, put);
+    detail::check(h, hadi_compute_jacobian_barrier(h.ctx, &p, S_0, V_0, eps, &b, J.data(), base_prices.data()));
+}
+
 // jacobian_computation.cpp:204-364 and the three variants.  J: [num_strikes][5], columns kappa, eta, sigma, rho, v0.
 inline void compute_jacobian(Handle &h, double S_0, double V_0, double, double r_d, double r_f, double rho, double sigma,
                              double kappa, double eta, int m1, int m2, int, int N, double theta, double delta_t,

@@ -51,6 +51,11 @@ class Problem(C.Structure):
     ]
 
 
+class Barrier(C.Structure):
+    """struct hadi_barrier (include/hadi.h)."""
+    _fields_ = [("lower_i", _dp), ("upper_i", _dp), ("rebate_i", _dp), ("n_mon", C.c_int), ("mon_steps", _ip), ("mon_rows", C.c_int)]
+
+
 class Timing(C.Structure):
     """struct hadi_timing (include/hadi.h)."""
     _fields_ = [
@@ -70,6 +75,7 @@ EXPORTS = [
     "hadi_DO_timestepping", "hadi_parallel_DO_solve", "hadi_compute_greeks",
     "hadi_maturity_ladder", "hadi_compute_base_prices_ladder", "hadi_compute_jacobian_ladder",
     "hadi_bermudan_timestepping", "hadi_compute_base_prices_bermudan", "hadi_compute_jacobian_bermudan",
+    "hadi_barrier_timestepping", "hadi_compute_base_prices_barrier", "hadi_compute_jacobian_barrier",
     "hadi_compute_base_prices", "hadi_compute_base_prices_american",
     "hadi_compute_base_prices_dividends", "hadi_compute_base_prices_american_dividends",
     "hadi_compute_jacobian", "hadi_compute_jacobian_american",
@@ -146,6 +152,12 @@ def _load(LIB_PATH):
                                                         C.c_void_p]
         L.hadi_compute_jacobian_bermudan.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_double, C.c_int, _ip,
                                                      C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(L, "hadi_barrier_timestepping"):  # (likewise: a build from before the barrier entry points)
+        _bp = C.POINTER(Barrier)
+        L.hadi_barrier_timestepping.argtypes = [C.c_void_p, C.POINTER(Problem), _bp]
+        L.hadi_compute_base_prices_barrier.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, _bp, C.c_void_p]
+        L.hadi_compute_jacobian_barrier.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_double, _bp, C.c_void_p,
+                                                    C.c_void_p]
     for sfx in ("", "_american", "_dividends", "_american_dividends"):
         getattr(L, "hadi_compute_base_prices" + sfx).argtypes = [
             C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_void_p]

@@ -60,6 +60,9 @@ struct Ctx {
     DevBuf pay_mis;  // American: per-instance payoff-shape flags (hadi_payoff_shape_kernel)
     DevBuf order;    // small-grid path: dispatch order of the instances (multi-maturity batches)
     DevBuf ex_flag;  // Bermudan: the exercise table, one row of Nmax flags (shared) or one per instance
+    // knock-out barrier: the monitoring table (as ex_flag), the bounds [n][2], the live index ranges [n][2] (hadi_barrier_locate_kernel)
+    // and the rebates [n]
+    DevBuf ko_flag, ko_bounds, ko_iab, ko_rebate;
     DevBuf snap_steps, snap_node, snap_out;  // maturity ladder: the snapshot steps, the instances' price nodes, the snapshots [n][n_snap]
     // Sticky device error word: one int in host-pinned, device-visible memory.  Kernels OR a HADI_DEVERR_* code into it
     // (system-scope atomic, only ever on a failure path); finish_timing reads it after the stream synchronisation every
@@ -234,6 +237,12 @@ struct SweepDesc {
     // 1 = one schedule for the batch, else one row per source instance (instance k reads row k % n_src: a Jacobian's groups share)
     int n_ex = 0, ex_rows = 0;
     const int *ex_steps = nullptr;
+    // Knock-out barrier (hadi_barrier_timestepping and its launchers): n_mon > 0 = mon_steps [mon_rows][n_mon], the rules of ex_steps,
+    // lists the steps at whose end an instance is monitored; ko_lower / ko_upper / ko_rebate: host [n_src] or null (validated; null =
+    // -inf / +inf / 0).  Instance k reads entry k % n_src of all four.
+    int n_mon = 0, mon_rows = 0;
+    const int *mon_steps = nullptr;
+    const double *ko_lower = nullptr, *ko_upper = nullptr, *ko_rebate = nullptr;
 };
 
 // A Bermudan schedule as the entry points receive it.
@@ -260,6 +269,8 @@ struct Sweep {
     std::vector<int> snap_q;     // step -> snapshot index of a ladder call, or -1
     std::vector<char> ex_step;   // step -> somebody may be exercised at its end (Bermudan)
     int ex_stride = 0;           // exercise table: one shared row (0) or a row of Nmax flags per instance
+    std::vector<char> mon_step;  // step -> somebody is monitored at its end (knock-out barrier)
+    int mon_stride = 0;          // monitoring table: one shared row (0) or a row of Nmax flags per instance
     int flag_stride = 0;         // dividend table: one shared row (0) or a row of Nmax flags per instance
     bool amp = false;            // American sweeps in the P representation (hadi_row_step, AMER == 2)
     HadiSweepArgs a, av;         // whole-batch arguments; Craig-Sneyd: the predictor's column pass writes V (= Y2), the
@@ -286,6 +297,16 @@ void mark_exercise_steps(Sweep &w) {
     w.in.n_ex_steps = (int)std::count(w.ex_step.begin(), w.ex_step.end(), (char)1);
 }
 
+// Barrier: the steps of the time loop behind which hadi_knockout_kernel is launched, and their number for the route.
+void mark_monitoring_steps(Sweep &w) {
+    const SweepDesc &d = w.d;
+    w.mon_step.assign(d.Nmax + 1, 0);
+    w.mon_stride = d.mon_rows > 1 ? d.Nmax : 0;
+    for (size_t e = 0; e < (size_t)d.mon_rows * d.n_mon; e++)
+        if (d.mon_steps[e] > 0) w.mon_step[d.mon_steps[e]] = 1;
+    w.in.n_mon_steps = (int)std::count(w.mon_step.begin(), w.mon_step.end(), (char)1);
+}
+
 // The choice, the launch geometry and the words are hadi_dispatch.h's (the rules: DESIGN.md section 4.1); this launches it.
 int launch_pass(Ctx *c, const HadiSel &sel, hipStream_t q, const HadiSweepArgs &ar, int nstep) {
     if (!sel.k) return fail(c, HADI_ERR_INTERNAL, "no kernel for this pass (grid %dx%d)", ar.L.m1, ar.L.m2);
@@ -303,6 +324,9 @@ int grow_buffers(Ctx *c, Sweep &w) {
     if (r.need_lam_u0 && ((rc = ensure(c, c->LAM, st)) || (rc = ensure(c, c->U0, st)))) return rc;
     if (r.need_u0 && (rc = ensure(c, c->U0, st))) return rc;
     if (r.bermudan && (rc = ensure(c, c->ex_flag, sizeof(int) * (size_t)(w.ex_stride ? d.n : 1) * d.Nmax))) return rc;
+    if (r.barrier && ((rc = ensure(c, c->ko_flag, sizeof(int) * (size_t)(w.mon_stride ? d.n : 1) * d.Nmax)) || (rc = ensure(c, c->ko_bounds, 16 * n)) ||
+                      (rc = ensure(c, c->ko_iab, 2 * sizeof(int) * n)) || (rc = ensure(c, c->ko_rebate, 8 * n))))
+        return rc;
     if (r.need_ut && (rc = ensure(c, c->UT, st))) return rc;
     if (r.need_f32 && ((rc = ensure(c, c->Uf, st / 2)) || (rc = ensure(c, c->Yf, st / 2)))) return rc;
     if (r.need_v_r1_c2 && ((rc = ensure(c, c->V, st)) || (rc = ensure(c, c->R1, st)) || (rc = ensure(c, c->C2, st)))) return rc;
@@ -366,6 +390,34 @@ int stage_exercise(Ctx *c, const Sweep &w) {
     return stage_to_device(c, c->ex_flag.p, flags.data(), flags.size() * sizeof(int));
 }
 
+// Barrier: the monitoring table (built as the exercise table), the bounds and the rebates of all n instances, then the live index
+// ranges from the device s-grids (hadi_barrier_locate_kernel).
+int stage_barrier(Ctx *c, const Sweep &w) {
+    const SweepDesc &d = w.d;
+    const int rows = w.mon_stride ? d.n : 1;
+    std::vector<int> flags((size_t)rows * d.Nmax, 0);
+    for (int k = 0; k < rows; k++) {
+        const int *row = d.mon_steps + (size_t)(w.mon_stride ? k % d.n_src : 0) * d.n_mon;
+        for (int q = 0; q < d.n_mon; q++)
+            if (row[q] > 0) flags[(size_t)k * d.Nmax + row[q] - 1] = 1;
+    }
+    std::vector<double> bounds((size_t)2 * d.n), rebate(d.n);
+    for (int k = 0; k < d.n; k++) {
+        const int src = k % d.n_src;
+        bounds[2 * (size_t)k] = d.ko_lower ? d.ko_lower[src] : -INFINITY;
+        bounds[2 * (size_t)k + 1] = d.ko_upper ? d.ko_upper[src] : INFINITY;
+        rebate[k] = d.ko_rebate ? d.ko_rebate[src] : 0.0;
+    }
+    int rc;
+    if ((rc = stage_to_device(c, c->ko_flag.p, flags.data(), flags.size() * sizeof(int))) ||
+        (rc = stage_to_device(c, c->ko_bounds.p, bounds.data(), bounds.size() * 8)) ||
+        (rc = stage_to_device(c, c->ko_rebate.p, rebate.data(), rebate.size() * 8)))
+        return rc;
+    hipLaunchKernelGGL(hadi_barrier_locate_kernel, dim3((d.n + 63) / 64), dim3(64), 0, c->stream, w.r.pl.L, d.n, d.d_vec_s,
+                       ptr<double>(c->ko_bounds), ptr<int>(c->ko_iab));
+    return HADI_OK;
+}
+
 // Parameters and dividend tables to the device, the operator tables (setup), the ladder's price nodes (locate), the packed
 // state and, for American sweeps, the payoff and its shape -- which decides w.amp.
 int stage_inputs(Ctx *c, Sweep &w) {
@@ -402,6 +454,7 @@ int stage_inputs(Ctx *c, Sweep &w) {
                            d.d_natU0 ? d.d_natU0 : d.d_natU, ptr<double>(c->U0));
         if ((rc = stage_exercise(c, w))) return rc;
     }
+    if (r.barrier && (rc = stage_barrier(c, w))) return rc;
     if (r.american) {
         hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src,
                            d.d_natU0 ? d.d_natU0 : d.d_natU, ptr<double>(c->U0));
@@ -478,6 +531,10 @@ int small_args(Ctx *c, const Sweep &w, HadiSmallArgs &sm) {
     }
     if (w.r.bermudan) {
         sm.ex_flag = ptr<int>(c->ex_flag); sm.ex_stride = w.ex_stride;
+    }
+    if (w.r.barrier) {
+        sm.ko_flag = ptr<int>(c->ko_flag); sm.ko_stride = w.mon_stride;
+        sm.ko_iab = ptr<int>(c->ko_iab); sm.ko_rebate = ptr<double>(c->ko_rebate);
     }
     if (w.r.ladder) {
         sm.snap_steps = ptr<int>(c->snap_steps); sm.n_snap = d.n_snap;
@@ -642,6 +699,12 @@ int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
             hipLaunchKernelGGL(hadi_exercise_kernel, dim3((unsigned)nsb * bpi), dim3(HADI_EX_THREADS), 0, q, L, nsb, bpi, Ub, U0b,
                                ptr<int>(c->ex_flag) + (size_t)o * w.ex_stride, w.ex_stride, nstep);
         }
+        if (r.barrier && w.mon_step[nstep]) {  // knock-out behind the step's last column pass (European sweeps, fp64 state: U is explicit)
+            const int bpi = hadi_exercise_bpi(L);
+            hipLaunchKernelGGL(hadi_knockout_kernel, dim3((unsigned)nsb * bpi), dim3(HADI_EX_THREADS), 0, q, L, nsb, bpi, Ub,
+                               ptr<int>(c->ko_flag) + (size_t)o * w.mon_stride, w.mon_stride, ptr<int>(c->ko_iab) + 2 * (size_t)o,
+                               ptr<double>(c->ko_rebate) + o, nstep);
+        }
         if (r.ladder && w.snap_q[nstep] >= 0)  // (U is explicit here: a ladder call never runs in the P representation)
             hipLaunchKernelGGL(hadi_snap_kernel, dim3((nsb + 63) / 64), dim3(64), 0, q, L, nsb, Ub, ptr<int>(c->snap_node) + o,
                                ptr<double>(c->snap_out) + (size_t)o * d.n_snap, d.n_snap, w.snap_q[nstep]);
@@ -728,6 +791,13 @@ std::string graph_key(const Ctx *c, const Sweep &w) {
         put(&w.ex_stride, sizeof(int));
         put(w.ex_step.data(), w.ex_step.size());
     }
+    if (w.r.barrier) {  // the tables are re-uploaded and the index ranges located again every call; the node list only depends on
+                        // which steps carry a knock-out launch, on the tables' addresses and on the stride
+        const void *ko[] = {c->ko_flag.p, c->ko_iab.p, c->ko_rebate.p};
+        put(ko, sizeof(ko));
+        put(&w.mon_stride, sizeof(int));
+        put(w.mon_step.data(), w.mon_step.size());
+    }
     if (w.r.have_div) {  // amounts / percentages / per-instance tables are re-uploaded every call; the node list
                          // only depends on which steps carry a dividend launch
         put(&w.flag_stride, sizeof(int));
@@ -793,6 +863,7 @@ int run_streaming(Ctx *c, Sweep &w, bool team_fell_back) {
 int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     Sweep w{d, route_in(c, d)};
     mark_exercise_steps(w);
+    mark_monitoring_steps(w);
     w.r = hadi_route(w.in);
     if (w.r.status == HADI_ROUTE_BAD_GRID)
         return fail(c, HADI_ERR_UNSUPPORTED, "grid %dx%d not supported (need m1 >= 2, m2 >= 3 and (m1 + 16)(m2 + 1) < 2^28)", d.m1, d.m2);
@@ -966,6 +1037,25 @@ int check_bermudan(Ctx *c, const hadi_problem *p, const ExSched &ex) {
     return HADI_OK;
 }
 
+// What the barrier entry points ask beyond check_problem (which has passed).  The schedule follows the rules of ex_steps.
+int check_barrier(Ctx *c, const hadi_problem *p, const hadi_barrier *b) {
+    if (p->variant == HADI_AM || p->variant == HADI_AM_DIV)
+        return fail(c, HADI_ERR_UNSUPPORTED, "a barrier sweep is the European sweep (HADI_EU or HADI_DIV) with monitoring steps");
+    if (p->state_precision == HADI_STATE_FP32) return fail(c, HADI_ERR_UNSUPPORTED, "barrier sweeps need the fp64 state");
+    const int n = p->n_instances;
+    for (int k = 0; k < n; k++) {
+        const double lo = b->lower_i ? b->lower_i[k] : -INFINITY, up = b->upper_i ? b->upper_i[k] : INFINITY;
+        if (std::isnan(lo) || std::isnan(up)) return fail(c, HADI_ERR_INVALID, "instance %d: a barrier is NaN", k);
+        if (lo >= up) return fail(c, HADI_ERR_INVALID, "instance %d: lower barrier %g is not below the upper barrier %g", k, lo, up);
+        if (b->rebate_i && !std::isfinite(b->rebate_i[k])) return fail(c, HADI_ERR_INVALID, "instance %d: the rebate is not finite", k);
+    }
+    if (b->n_mon > 0 && !b->lower_i && !b->upper_i) return fail(c, HADI_ERR_INVALID, "monitoring steps without a barrier on either side");
+    const ExSched mon{b->n_mon, b->mon_rows, b->mon_steps};
+    const int rc = check_bermudan(c, p, mon);
+    if (rc == HADI_ERR_INVALID) c->err = "mon_steps (the rules of ex_steps): " + c->err;
+    return rc;
+}
+
 // Fills the per-instance parameter rows for `groups` copies of the caller's batch.
 void fill_par(const hadi_problem *p, SweepDesc &d, int groups) {
     const int n0 = p->n_instances;
@@ -1018,10 +1108,11 @@ int rebuild_v_device(Ctx *c, int n, int m2, const std::vector<double> &v0i) {
 // took on the way; p->U and p->lambda_bar are not written.
 int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, double S_0, double V_0, double *prices_out,
                  int debug = 0, int debug_step = 1, double *debug_out = nullptr, int n_snap = 0, const int *snap_steps = nullptr,
-                 const ExSched *ex = nullptr) {
+                 const ExSched *ex = nullptr, const hadi_barrier *ko = nullptr) {
     int rc = check_problem(c, p, true, !rebuild_v);
     if (rc) return rc;
     if (ex && (rc = check_bermudan(c, p, *ex))) return rc;
+    if (ko && (rc = check_barrier(c, p, ko))) return rc;
     const bool ladder = n_snap > 0 || snap_steps;
     if (ladder && (rc = check_ladder(c, p, n_snap, snap_steps, prices_out))) return rc;
     if (debug && !debug_out) return fail(c, HADI_ERR_INVALID, "output array missing");
@@ -1077,6 +1168,10 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
         d.d_v0_i = per_inst_v0 ? ptr<double>(c->v0_i) : nullptr;
     }
     if (ex && ex->n_ex > 0) { d.n_ex = ex->n_ex; d.ex_rows = ex->rows; d.ex_steps = ex->steps; }
+    if (ko && ko->n_mon > 0) {
+        d.n_mon = ko->n_mon; d.mon_rows = ko->mon_rows; d.mon_steps = ko->mon_steps;
+        d.ko_lower = ko->lower_i; d.ko_upper = ko->upper_i; d.ko_rebate = ko->rebate_i;
+    }
 
     HadiPlan pl;
     if ((rc = run_sweep(c, d, pl))) return rc;
@@ -1248,10 +1343,11 @@ int jacobian_grids(Ctx *c, const hadi_problem *p, int G, double V_0, double eps,
 // group 0 = base, 1..4 = kappa, eta, sigma, rho + eps, 5 = v-grid rebuilt for V_0 + eps.
 // Ladder (n_snap > 0; hadi_compute_jacobian_ladder): J [n][n_snap][5] and base_prices [n][n_snap] from the snapshots of the 6n solves.
 int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double eps, double *J, double *base_prices,
-                    int n_snap = 0, const int *snap_steps = nullptr, const ExSched *ex = nullptr) {
+                    int n_snap = 0, const int *snap_steps = nullptr, const ExSched *ex = nullptr, const hadi_barrier *ko = nullptr) {
     int rc = check_problem(c, p, false, false);
     if (rc) return rc;
     if (ex && (rc = check_bermudan(c, p, *ex))) return rc;
+    if (ko && (rc = check_barrier(c, p, ko))) return rc;
     const bool ladder = n_snap > 0 || snap_steps;
     if (ladder && (rc = check_ladder(c, p, n_snap, snap_steps, (J && base_prices) ? J : nullptr))) return rc;
     DeviceGuard guard(c->device);
@@ -1282,6 +1378,10 @@ int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, doubl
         d.n_snap = n_snap; d.snap_steps = snap_steps; d.S_0 = S_0; d.V_0 = V_0; d.d_v0_i = ptr<double>(c->v0_i);
     }
     if (ex && ex->n_ex > 0) { d.n_ex = ex->n_ex; d.ex_rows = ex->rows; d.ex_steps = ex->steps; }
+    if (ko && ko->n_mon > 0) {
+        d.n_mon = ko->n_mon; d.mon_rows = ko->mon_rows; d.mon_steps = ko->mon_steps;
+        d.ko_lower = ko->lower_i; d.ko_upper = ko->upper_i; d.ko_rebate = ko->rebate_i;
+    }
 
     HadiPlan pl;
     if ((rc = run_sweep(c, d, pl))) return rc;
@@ -1331,7 +1431,8 @@ void release_handle(Ctx *c) {
                       &c->rinv, &c->rwork, &c->ipar, &c->par8, &c->g_s, &c->g_v, &c->g_ds, &c->g_dv, &c->src_v,
                       &c->src_dv, &c->sel_a, &c->sel_b, &c->v0_i, &c->natU, &c->natU0, &c->natOut, &c->prices,
                       &c->status, &c->div_flag, &c->div_amt, &c->div_pct, &c->V, &c->R1, &c->C2, &c->pay_mis, &c->Uf, &c->Yf,
-                      &c->order, &c->lm31, &c->team, &c->rs_tab, &c->snap_steps, &c->snap_node, &c->snap_out, &c->ex_flag};
+                      &c->order, &c->lm31, &c->team, &c->rs_tab, &c->snap_steps, &c->snap_node, &c->snap_out, &c->ex_flag,
+                      &c->ko_flag, &c->ko_bounds, &c->ko_iab, &c->ko_rebate};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &g : c->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
@@ -1647,6 +1748,27 @@ int hadi_compute_jacobian_bermudan(hadi_ctx *ctx, const hadi_problem *p, double 
                                    const int *ex_steps, int ex_rows, double *J, double *base_prices) {
     const ExSched ex{n_ex, ex_rows, ex_steps};
     return jacobian_common(reinterpret_cast<Ctx *>(ctx), p, S_0, V_0, eps, J, base_prices, 0, nullptr, &ex);
+}
+
+// ---- knock-out barrier: the European sweep with U <- rebate beyond the barriers at the end of the monitoring steps ----------
+int hadi_barrier_timestepping(hadi_ctx *ctx, const hadi_problem *p, const hadi_barrier *barrier) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && !barrier) return fail(c, HADI_ERR_INVALID, "barrier description missing");
+    return solve_common(c, p, false, false, 0.0, 0.0, nullptr, 0, 1, nullptr, 0, nullptr, nullptr, barrier);
+}
+
+int hadi_compute_base_prices_barrier(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, const hadi_barrier *barrier,
+                                     double *base_prices) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && (!barrier || !base_prices)) return fail(c, HADI_ERR_INVALID, "%s missing", barrier ? "base_prices" : "barrier description");
+    return solve_common(c, p, true, true, S_0, V_0, base_prices, 0, 1, nullptr, 0, nullptr, nullptr, barrier);
+}
+
+int hadi_compute_jacobian_barrier(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, const hadi_barrier *barrier,
+                                  double *J, double *base_prices) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && !barrier) return fail(c, HADI_ERR_INVALID, "barrier description missing");
+    return jacobian_common(c, p, S_0, V_0, eps, J, base_prices, 0, nullptr, nullptr, barrier);
 }
 
 HADI_VARIANT_WRAPPERS(american, HADI_AM)

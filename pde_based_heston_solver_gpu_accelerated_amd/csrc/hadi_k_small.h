@@ -34,6 +34,13 @@ struct HadiSmallArgs {
     // where ex_flag[k*ex_stride + n-1] != 0 (ex_stride 0 = one shared row).  The payoff is HadiSweepArgs::U0 (packed, global).
     const int *ex_flag = nullptr;
     int ex_stride = 0;
+    // Knock-out barrier (hadi_barrier_timestepping; nullptr = none): at the END of step n where ko_flag[k*ko_stride + n-1] != 0
+    // (ko_stride 0 = one shared row) instance k takes U <- ko_rebate[k] on the nodes outside ko_iab[2k] .. ko_iab[2k+1], the live
+    // index range that hadi_barrier_locate_kernel wrote
+    const int *ko_flag = nullptr;
+    int ko_stride = 0;
+    const int *ko_iab = nullptr;
+    const double *ko_rebate = nullptr;
 };
 
 // The ladder's running cursor of a whole-loop kernel: wave-uniform (kernel arguments and the step counter only).  `next` is the
@@ -221,6 +228,10 @@ __global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, Had
                 hadi_exercise_lds<B>(Ul, rowp, false, a.U0 + (size_t)inst * a.L.inst_stride, nrows, m1, rowp, tid, NT);
                 __syncthreads();
             }
+            if (hadi_ex_listed(sm.ko_flag, sm.ko_stride, inst, n)) {  // knock-out at the end of a monitoring step (block-uniform)
+                hadi_knock_lds<B>(Ul, rowp, false, sm.ko_iab[2 * inst], sm.ko_iab[2 * inst + 1], sm.ko_rebate[inst], nrows, m1, tid, NT);
+                __syncthreads();
+            }
         }
         // maturity ladder: nothing writes U before the next barrier (the row pass reads it, a dividend copies it to Y first)
         if (n == snap.next) {
@@ -364,6 +375,10 @@ __global__ void __launch_bounds__(64) hadi_small_seq_kernel(HadiSweepArgs a, Had
             hadi_exercise_lds<B>(Ul, PL, true, a.U0 + (size_t)inst * a.L.inst_stride, nrows, m1, rowp, lane, 64);
             __syncthreads();
         }
+        if (hadi_ex_listed(sm.ko_flag, sm.ko_stride, inst, n)) {  // knock-out at the end of a monitoring step (wave-uniform)
+            hadi_knock_lds<B>(Ul, PL, true, sm.ko_iab[2 * inst], sm.ko_iab[2 * inst + 1], sm.ko_rebate[inst], nrows, m1, lane, 64);
+            __syncthreads();
+        }
         // maturity ladder: lane 0 reads the node before it stores anything of the next step (one wavefront: nobody else has yet)
         if (n == snap.next) {
             if (lane == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
@@ -492,6 +507,10 @@ __global__ void __launch_bounds__(64) hadi_small_seq2_kernel(HadiSweepArgs a, Ha
             const int ih = h ? inst1 : inst0, Nh = h ? N1 : N0;
             if (n <= Nh && hadi_ex_listed(sm.ex_flag, sm.ex_stride, ih, n)) {  // (wave-uniform)
                 hadi_exercise_lds<B>(h ? base1 : base0, PL, true, a.U0 + (size_t)ih * a.L.inst_stride, nrows, m1, rowp, lane, 64);
+                __syncthreads();
+            }
+            if (n <= Nh && hadi_ex_listed(sm.ko_flag, sm.ko_stride, ih, n)) {  // knock-out, per half as the exercise (wave-uniform)
+                hadi_knock_lds<B>(h ? base1 : base0, PL, true, sm.ko_iab[2 * ih], sm.ko_iab[2 * ih + 1], sm.ko_rebate[ih], nrows, m1, lane, 64);
                 __syncthreads();
             }
         }

@@ -283,6 +283,10 @@ __global__ void __launch_bounds__(64) hadi_small_sch_kernel(HadiSweepArgs a, Had
             hadi_exercise_lds<B>(Ul, PL, true, a.U0 + (size_t)inst * a.L.inst_stride, nrows, m1, rowp, lane, 64);
             __syncthreads();
         }
+        if (hadi_ex_listed(sm.ko_flag, sm.ko_stride, inst, n)) {  // knock-out behind the corrector's column pass (wave-uniform)
+            hadi_knock_lds<B>(Ul, PL, true, sm.ko_iab[2 * inst], sm.ko_iab[2 * inst + 1], sm.ko_rebate[inst], nrows, m1, lane, 64);
+            __syncthreads();
+        }
         // maturity ladder: lane 0 reads the node before it stores anything of the next step (one wavefront: nobody else has yet)
         if (n == snap.next) {
             if (lane == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");

@@ -478,6 +478,83 @@ class HestonADI:
             self._raise(rc)
         return J, base
 
+    # ---- knock-out barrier options (hadi_barrier_timestepping and its launchers; no reference counterpart) ------
+    @classmethod
+    def _barrier(cls, n, monitor_steps, lower, upper, rebate):
+        """(struct hadi_barrier, the arrays it points into) -- host arrays [n] from scalars or sequences, None = NULL."""
+        keep = []
+
+        def arr(x):
+            if x is None:
+                return None
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (n,)))
+            keep.append(a)
+            return a.ctypes.data_as(nat._dp)
+
+        mon, rows, n_mon = cls._schedule(monitor_steps)
+        keep.append(mon)
+        b = nat.Barrier(arr(lower), arr(upper), arr(rebate), n_mon, mon.ctypes.data_as(_ip), rows)
+        return b, keep
+
+    def barrier_timestepping(self, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U, monitor_steps,
+                             lower=None, upper=None, rebate=None, variant=EU, dividends=None, per_instance=None, scheme=0,
+                             option_type=CALL, strikes=None):
+        """DO_timestepping (variant EU or DIV) of discretely monitored knock-out options: after the last pass of every step of
+        `monitor_steps` every node of the instances that list it whose spot is at or beyond a barrier (s <= lower or
+        s >= upper) takes U <- rebate, undiscounted.  monitor_steps: as exercise_steps of bermudan_timestepping (one list, or
+        one list per instance; monitoring_steps maps calendar dates to steps).  lower / upper / rebate: a scalar, one value per
+        instance, or None (no barrier on that side / no rebate).  U is the caller's initial condition -- monitoring at maturity
+        is knock_out_payoff -- and is updated in place."""
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U=U, dividends=dividends,
+                          per_instance=per_instance, scheme=scheme, option_type=option_type, strikes=strikes)
+        b, keep = self._barrier(p.n_instances, monitor_steps, lower, upper, rebate)
+        rc = self._lib.hadi_barrier_timestepping(self._h, C.byref(p), C.byref(b))
+        del keep
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return U
+
+    def compute_base_prices_barrier(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                    num_strikes, deviceGrids, workspace, monitor_steps, lower=None, upper=None, rebate=None,
+                                    variant=EU, dividends=None, per_instance=None, scheme=0):
+        """compute_base_prices* (the v-grid rebuilt for V_0 or per_instance['V_0_i']) of knock-out options: [n] prices at
+        (S_0, V_0).  workspace.U is the initial condition and receives the field."""
+        option_type, strikes = self._option(per_instance)
+        if total_size != (m1 + 1) * (m2 + 1):
+            raise ValueError("total_size != (m1+1)*(m2+1)")
+        if deviceGrids.Vec_s.shape[0] != num_strikes:
+            raise ValueError("num_strikes does not match the grid batch")
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=workspace.U,
+                          dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
+                          option_type=option_type, strikes=strikes)
+        b, keep = self._barrier(num_strikes, monitor_steps, lower, upper, rebate)
+        out, optr = self._out(num_strikes, 1, workspace.U)
+        rc = self._lib.hadi_compute_base_prices_barrier(self._h, C.byref(p), float(S_0), float(V_0), C.byref(b), optr)
+        del keep
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return out
+
+    def compute_jacobian_barrier(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                 num_strikes, deviceGrids, U_0, monitor_steps, lower=None, upper=None, rebate=None, eps=1e-6,
+                                 variant=EU, dividends=None, per_instance=None, scheme=0):
+        """compute_jacobian* of knock-out options: (J [n][5], base_prices [n]); the six solves of an instance share its
+        barriers, rebate and schedule; U_0 is the initial condition."""
+        if total_size != (m1 + 1) * (m2 + 1):
+            raise ValueError("total_size != (m1+1)*(m2+1)")
+        option_type, strikes = self._option(per_instance)
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=None, U_0=U_0,
+                          dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
+                          option_type=option_type, strikes=strikes)
+        b, keep = self._barrier(num_strikes, monitor_steps, lower, upper, rebate)
+        J, jptr = self._out(num_strikes, 5, U_0)
+        base, bptr = self._out(num_strikes, 1, U_0)
+        rc = self._lib.hadi_compute_jacobian_barrier(self._h, C.byref(p), float(S_0), float(V_0), float(eps), C.byref(b), jptr, bptr)
+        del keep
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return J, base
+
     # ---- compute_base_prices* (src/jacobian_computation.cpp:368, 629, 922, 1232) ---------------
     def _base_prices(self, variant, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N,
                      theta, delta_t, num_strikes, deviceGrids, workspace, U_0=None, dividends=None,
@@ -621,6 +698,24 @@ def exercise_steps(T, delta_t, dates):
     if len(set(steps)) != len(steps):
         raise ValueError("an exercise date is listed twice")
     return sorted(steps)
+
+
+def monitoring_steps(T, delta_t, dates):
+    """Step indices of calendar monitoring dates of a barrier option: exercise_steps for dates in [0, T).  (A fixing at T itself
+    is monitoring at maturity: knock_out_payoff.)"""
+    return exercise_steps(T, delta_t, dates)
+
+
+def knock_out_payoff(grids, U, lower, upper, rebate=None):
+    """Monitoring at maturity, on the host: a copy of the payoff U [n][(m1+1)(m2+1)] in which every node whose spot is at or
+    beyond a barrier (Vec_s <= lower or Vec_s >= upper: the library's comparison) holds the rebate (default 0), in every v-row.
+    lower / upper / rebate: a scalar, one value per instance, or None."""
+    vs = np.asarray(grids.Vec_s, dtype=np.float64)
+    n, m1p = vs.shape
+    col = lambda x, default: np.broadcast_to(np.asarray(default if x is None else x, dtype=np.float64), (n,))[:, None]
+    knocked = (vs <= col(lower, -np.inf)) | (vs >= col(upper, np.inf))
+    field = np.asarray(U, dtype=np.float64).reshape(n, -1, m1p)
+    return np.where(knocked[:, None, :], col(rebate, 0.0)[:, :, None], field).reshape(n, -1)
 
 
 # ---- LM linear algebra (host; jacobian_computation.cpp:20-195) -------------------------------------
