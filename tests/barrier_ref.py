@@ -90,17 +90,20 @@ def per_instance(x, k, default):
 
 
 def solve_batch(m1, m2, N, dt, theta, r_d, r_f, rho, sigma, kappa, eta, vs, vv, ds, dv, U, mon_steps, lower=None, upper=None,
-                rebate=None, dividends=None, put_strikes=None, scheme=DOUGLAS, N_i=None, dt_i=None, rows=None):
+                rebate=None, dividends=None, put_strikes=None, scheme=DOUGLAS, N_i=None, dt_i=None, rows=None, models=None):
     """[n][m] fields, instance by instance.  mon_steps: one list for the batch or one list per instance; lower / upper / rebate:
-    a scalar, one value per instance, or None; N_i / dt_i: per-instance step grids; rows: solve these instances only (the others
-    stay NaN)."""
+    a scalar, one value per instance, or None; N_i / dt_i: per-instance step grids; models: one (rho, sigma, kappa, eta) per
+    instance; dividends: (dates, amounts, percentages) as tests/dividend_schedules.py builds them, dated on every instance's own
+    step grid; rows: solve these instances only (the others stay NaN)."""
     n = vs.shape[0]
     mon = list(mon_steps)
     shared = not (mon and np.ndim(mon[0]) == 1)
     out = np.full((n, (m1 + 1) * (m2 + 1)), np.nan)
+    assert models is None or len(models) == n
     for k in (range(n) if rows is None else rows):
+        mk = (rho, sigma, kappa, eta) if models is None else tuple(float(x) for x in models[k])
         out[k] = solve_one(m1, m2, int(N_i[k]) if N_i is not None else N, float(dt_i[k]) if dt_i is not None else dt, theta, r_d,
-                           r_f, rho, sigma, kappa, eta, vs[k], vv[k], ds[k], dv[k], U[k], mon if shared else mon[k],
+                           r_f, *mk, vs[k], vv[k], ds[k], dv[k], U[k], mon if shared else mon[k],
                            per_instance(lower, k, None), per_instance(upper, k, None), per_instance(rebate, k, 0.0), dividends,
                            None if put_strikes is None else float(put_strikes[k]), scheme)
     return out

@@ -104,18 +104,22 @@ def solve_one(m1, m2, N, dt, theta, r_d, r_f, rho, sigma, kappa, eta, vs, vv, ds
 
 
 def solve_batch(m1, m2, N, dt, theta, r_d, r_f, rho, sigma, kappa, eta, vs, vv, ds, dv, U, ex_steps, payoff=None,
-                dividends=None, put_strikes=None, scheme=DOUGLAS, N_i=None, dt_i=None, par_i=None, rows=None):
+                dividends=None, put_strikes=None, scheme=DOUGLAS, N_i=None, dt_i=None, par_i=None, rows=None, models=None):
     """[n][m] fields, instance by instance.  ex_steps: one list for the batch or one list per instance; N_i / dt_i: per-instance
-    step grids; par_i: {"rho_i": [...], ...} per-instance model parameters; rows: solve these instances only (the others stay
-    NaN)."""
+    step grids; par_i: {"rho_i": [...], ...} per-instance model parameters, or models: one (rho, sigma, kappa, eta) per
+    instance; dividends: (dates, amounts, percentages) as tests/dividend_schedules.py builds them, dated on every instance's own
+    step grid; rows: solve these instances only (the others stay NaN)."""
     n = vs.shape[0]
     ex = list(ex_steps)
     shared = not (ex and np.ndim(ex[0]) == 1)
     out = np.full((n, (m1 + 1) * (m2 + 1)), np.nan)
     par = par_i or {}
+    assert models is None or (not par and len(models) == n)
     for k in (range(n) if rows is None else rows):
         pk = [par[key][k] if par.get(key) is not None else val
               for key, val in (("rho_i", rho), ("sigma_i", sigma), ("kappa_i", kappa), ("eta_i", eta))]
+        if models is not None:
+            pk = [float(x) for x in models[k]]
         out[k] = solve_one(m1, m2, int(N_i[k]) if N_i is not None else N, float(dt_i[k]) if dt_i is not None else dt, theta, r_d,
                            r_f, pk[0], pk[1], pk[2], pk[3], vs[k], vv[k], ds[k], dv[k], U[k], ex if shared else ex[k],
                            None if payoff is None else payoff[k], dividends,

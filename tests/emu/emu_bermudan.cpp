@@ -11,11 +11,14 @@
 // hadi_small_seq2_kernel, 4 hadi_small_sch_kernel, 5 the streaming kernels (the plan's own choice; emu_set_tuning "strip" pins it).
 // scheme: enum hadi_scheme.  U: the initial field (not modified); U0: the payoff, or NULL = the initial field.  ex_steps
 // [ex_rows][n_ex], ex_rows 1 or n, rows zero-padded; n_ex = 0: no exercise table at all (the plain call).  U_out [n][m].
+// P_out (or NULL) [emu_bermudan_packed_size]: the packed state the sweep leaves; is_pad (or NULL), same size: 1 where the element
+// is no node (a pad slot, a slot of a node beyond m1, an identity row).
 // Returns 0, 1 (no plan), 2 (no such kernel), 3 (not admitted), 4 (device error word set).
-extern "C" int emu_bermudan(int n_inst, int m1, int m2, double theta, double r_d, double r_f, const double *par8,
-                            const double *vec_s, const double *vec_v, const double *delta_s, const double *delta_v,
-                            const double *U, const double *U0, int kind, int scheme, int ndiv, const double *ddates,
-                            const double *damounts, const double *dpcts, int n_ex, const int *ex_steps, int ex_rows, double *U_out) {
+static int bermudan_run(int n_inst, int m1, int m2, double theta, double r_d, double r_f, const double *par8,
+                        const double *vec_s, const double *vec_v, const double *delta_s, const double *delta_v,
+                        const double *U, const double *U0, int kind, int scheme, int ndiv, const double *ddates,
+                        const double *damounts, const double *dpcts, int n_ex, const int *ex_steps, int ex_rows, double *U_out,
+                        double *P_out, unsigned char *is_pad) {
     HadiPlan pl;
     if (hadi_make_plan(m1, m2, n_inst, 8 * 256, &pl, g_tune, 8)) return 1;
     if (hadi_no_strips(theta, r_d == r_f)) pl.use_strip = 0;
@@ -74,6 +77,17 @@ extern "C" int emu_bermudan(int n_inst, int m1, int m2, double theta, double r_d
     a.ipar = ipar.data(); a.L = L; a.n_inst = n_inst; a.R = pl.R; a.ntiles = pl.ntiles; a.ctiles = pl.ctiles; a.btpw = pl.btpw;
     a.bgroups = pl.bgroups; a.tile_il = g_tile_il; a.pos_m1 = pl.pos_m1; a.RS = pl.RS; a.sblocks = pl.sblocks;
     a.err = &g_err; a.debug = g_debug;
+    auto finish = [&]() {
+        emu::launch(8, 64, [&]() { hadi_unpack_kernel(L, n_inst, dU.data(), U_out); });
+        if (P_out) std::copy(dU.begin(), dU.end(), P_out);
+        if (is_pad)
+            for (size_t e = 0; e < st; e++) {
+                const size_t r = e % (size_t)L.inst_stride;
+                const int i = hadi_slot_to_i(L, (int)(r % L.rowp));
+                is_pad[e] = (i < 0 || i > L.m1 || (int)(r / L.rowp) >= L.nrows) ? 1 : 0;
+            }
+        return g_err ? 4 : 0;
+    };
     if (kind < 5) {
         HadiSmallArgs sm;
         sm.div_flag = dividend ? flags.data() : nullptr; sm.flag_stride = flag_stride; sm.div_amounts = damounts; sm.div_pcts = dpcts;
@@ -92,8 +106,7 @@ extern "C" int emu_bermudan(int n_inst, int m1, int m2, double theta, double r_d
             if (!sel.k) return 2;
             emu::launch(sel.grid, sel.block, [&]() { sel.k->loop(a, sm); }, sel.smem);
         }
-        emu::launch(8, 64, [&]() { hadi_unpack_kernel(L, n_inst, dU.data(), U_out); });
-        return g_err ? 4 : 0;
+        return finish();
     }
     // the streaming loop of enqueue_sub_batch (one sub-batch, European sweeps with the fp64 state)
     std::vector<double> dW(pl.row_seq ? st : 0);
@@ -121,8 +134,32 @@ extern "C" int emu_bermudan(int n_inst, int m1, int m2, double theta, double r_d
                 hadi_exercise_kernel(L, n_inst, bpi, dU.data(), dU0.data(), exf.data(), ex_stride, n);
             });
     }
-    emu::launch(8, 64, [&]() { hadi_unpack_kernel(L, n_inst, dU.data(), U_out); });
-    return g_err ? 4 : 0;
+    return finish();
+}
+
+extern "C" int emu_bermudan(int n_inst, int m1, int m2, double theta, double r_d, double r_f, const double *par8,
+                            const double *vec_s, const double *vec_v, const double *delta_s, const double *delta_v,
+                            const double *U, const double *U0, int kind, int scheme, int ndiv, const double *ddates,
+                            const double *damounts, const double *dpcts, int n_ex, const int *ex_steps, int ex_rows, double *U_out) {
+    return bermudan_run(n_inst, m1, m2, theta, r_d, r_f, par8, vec_s, vec_v, delta_s, delta_v, U, U0, kind, scheme, ndiv, ddates,
+                        damounts, dpcts, n_ex, ex_steps, ex_rows, U_out, nullptr, nullptr);
+}
+
+// Elements of the packed state of n_inst instances (0: no plan).
+extern "C" long long emu_bermudan_packed_size(int n_inst, int m1, int m2) {
+    HadiPlan pl;
+    if (hadi_make_plan(m1, m2, n_inst, 8 * 256, &pl, g_tune, 8)) return 0;
+    return (long long)pl.L.inst_stride * n_inst;
+}
+
+// emu_bermudan with the packed state it leaves and the mask of its non-node elements.
+extern "C" int emu_bermudan_state(int n_inst, int m1, int m2, double theta, double r_d, double r_f, const double *par8,
+                                  const double *vec_s, const double *vec_v, const double *delta_s, const double *delta_v,
+                                  const double *U, const double *U0, int kind, int scheme, int ndiv, const double *ddates,
+                                  const double *damounts, const double *dpcts, int n_ex, const int *ex_steps, int ex_rows,
+                                  double *U_out, double *P_out, unsigned char *is_pad) {
+    return bermudan_run(n_inst, m1, m2, theta, r_d, r_f, par8, vec_s, vec_v, delta_s, delta_v, U, U0, kind, scheme, ndiv, ddates,
+                        damounts, dpcts, n_ex, ex_steps, ex_rows, U_out, P_out, is_pad);
 }
 
 // emu_route (emu_driver.cpp) with the one input a Bermudan call adds: the number of its exercise steps.  o[16]: emu_route's 15

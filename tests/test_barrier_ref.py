@@ -117,3 +117,46 @@ def test_schemes_without_monitoring_are_scheme_ref(scheme):
     assert np.array_equal(ref(m1, m2, N, g, [], scheme=scheme, lower=LO * K, upper=UP * K), SR.solve_one(p, *g, scheme))
     U = ref(m1, m2, N, g, schedule(N), scheme=scheme, lower=LO * K, upper=UP * K)
     assert np.abs(U - ref(m1, m2, N, g, [], scheme=scheme)).max() / np.abs(U).max() >= 1e-4
+
+
+# ---- per-instance models and the dividend schedules of the event-domain tests --------------------------------------------------
+def test_per_instance_models_without_events_are_the_oracle_bit_for_bit():
+    import regimes as R
+    m1, m2, N, n = 50, 25, 6, 4
+    vs, vv, ds, dv, U0 = oracle_grids(m1, m2, [K] * n)
+    models = R.rotating_models(n, 1)
+    for put in (False, True):
+        U = put_payoff(vs, [K] * n, m2) if put else U0
+        kw = dict(lower=LO * K, upper=UP * K, rebate=3.0, put_strikes=[K] * n if put else None)
+        got = KR.solve_batch(m1, m2, N, T / N, THETA, R_D, R_F, RHO, SIGMA, KAPPA, ETA, vs, vv, ds, dv, U, [], models=models, **kw)
+        for k in range(n):
+            p = O.make_params(m1, m2, N, T / N, THETA, R_D, R_F, *models[k], O.EU, option_type=O.PUT if put else O.CALL, strikes=K if put else None)
+            assert np.array_equal(got[k], O.solve(p, vs[k], vv[k], ds[k], dv[k], U[k])[0]), (put, k)
+        same = KR.solve_batch(m1, m2, N, T / N, THETA, R_D, R_F, RHO, SIGMA, KAPPA, ETA, vs, vv, ds, dv, U, [], **kw)
+        assert not np.array_equal(got[1], same[1])  # (the models are read)
+        assert np.array_equal(same[0], KR.solve_batch(m1, m2, N, T / N, THETA, R_D, R_F, RHO, SIGMA, KAPPA, ETA, vs, vv, ds, dv, U, [],
+                                                      models=[(RHO, SIGMA, KAPPA, ETA)] * n, **kw)[0])
+
+
+@pytest.mark.parametrize("put", [False, True], ids=["call", "put"])
+def test_dividends_are_paid_on_exactly_the_steps_paying_steps_names(monkeypatch, put):
+    import dividend_schedules as D
+    import event_cases as E
+    from test_bermudan_ref import paying_steps_seen
+    m1, m2 = 50, 25
+    g = problem(m1, m2, put)
+    cases = E.schedules_near_dividends(20, T / 20, T)[:3] + E.schedules_near_dividends(10, T / 10, T)[-6:]
+    assert len(cases) == 9
+    for c in cases:
+        paid = D.paying_steps(c.N, c.dt, c.dividends[0])
+        assert paid and paid == E.check(c, g[0])[0]
+        lo, up = (E.floor_barrier(g[0][None])[0][0], None) if c.barrier == "floor" else (LO * K, UP * K)
+        run = lambda mon: KR.solve_batch(m1, m2, c.N, c.dt, THETA, R_D, R_F, RHO, SIGMA, KAPPA, ETA, *(x[None] for x in g), mon, lower=lo,
+                                         upper=up, rebate=2.0, dividends=c.dividends, put_strikes=[K] if put else None)[0]
+        seen = paying_steps_seen(monkeypatch, lambda: run(c.events))
+        monkeypatch.undo()
+        assert seen == [(n, c.dividends[1][q], c.dividends[2][q]) for n, q in sorted(paid.items())], (c.name, seen, paid)
+        # ... and without monitoring the stepper is the oracle's dividend sweep on that schedule, bit for bit
+        p = O.make_params(m1, m2, c.N, c.dt, THETA, R_D, R_F, RHO, SIGMA, KAPPA, ETA, O.DIV, c.dividends, option_type=O.PUT if put else O.CALL,
+                          strikes=K if put else None)
+        assert np.array_equal(run([]), O.solve(p, *g)[0]), c.name

@@ -99,3 +99,65 @@ def test_schemes_without_exercise_are_scheme_ref(scheme):
     assert np.array_equal(ref(m1, m2, N, g, [], False, False, scheme), SR.solve_one(p, *g, scheme))
     U = ref(m1, m2, N, g, schedule(N), False, False, scheme)
     assert np.abs(U - ref(m1, m2, N, g, [], False, False, scheme)).max() / np.abs(U).max() >= 1e-4
+
+
+# ---- per-instance models and the dividend schedules of the event-domain tests --------------------------------------------------
+def test_per_instance_models_without_events_are_the_oracle_bit_for_bit():
+    import regimes as R
+    m1, m2, N, n = 50, 25, 6, 4
+    vs, vv, ds, dv, U0 = oracle_grids(m1, m2, [K] * n)
+    models = R.rotating_models(n, 1)
+    for put in (False, True):
+        U = put_payoff(vs, [K] * n, m2) if put else U0
+        got = BR.solve_batch(m1, m2, N, T / N, THETA, R_D, R_F, RHO, SIGMA, KAPPA, ETA, vs, vv, ds, dv, U, [], models=models,
+                             put_strikes=[K] * n if put else None)
+        for k in range(n):
+            p = O.make_params(m1, m2, N, T / N, THETA, R_D, R_F, *models[k], O.EU, option_type=O.PUT if put else O.CALL, strikes=K if put else None)
+            assert np.array_equal(got[k], O.solve(p, vs[k], vv[k], ds[k], dv[k], U[k])[0]), (put, k)
+        same = BR.solve_batch(m1, m2, N, T / N, THETA, R_D, R_F, RHO, SIGMA, KAPPA, ETA, vs, vv, ds, dv, U, [], put_strikes=[K] * n if put else None)
+        assert not np.array_equal(got[1], same[1])  # (the models are read)
+        assert np.array_equal(same[0], BR.solve_batch(m1, m2, N, T / N, THETA, R_D, R_F, RHO, SIGMA, KAPPA, ETA, vs, vv, ds, dv, U, [],
+                                                      models=[(RHO, SIGMA, KAPPA, ETA)] * n, put_strikes=[K] * n if put else None)[0])
+
+
+def paying_steps_seen(monkeypatch, stepper):
+    """The steps at whose start `stepper` calls the jump, with the dividend it pays: every Douglas step makes five operator calls
+    (three products, two line solves), so the count of calls before a jump names its step."""
+    calls, seen = [0], []
+    op, jump = O.operator, BR.dividend_jump
+
+    def counting(*a, **kw):
+        calls[0] += 1
+        return op(*a, **kw)
+
+    def recording(vs, U, amount, pct, *a):
+        assert calls[0] % 5 == 0
+        seen.append((calls[0] // 5 + 1, amount, pct))
+        return jump(vs, U, amount, pct, *a)
+
+    monkeypatch.setattr(O, "operator", counting)
+    monkeypatch.setattr(BR, "dividend_jump", recording)
+    stepper()
+    return seen
+
+
+@pytest.mark.parametrize("put", [False, True], ids=["call", "put"])
+def test_dividends_are_paid_on_exactly_the_steps_paying_steps_names(monkeypatch, put):
+    import dividend_schedules as D
+    import event_cases as E
+    m1, m2 = 50, 25
+    g = problem(m1, m2, put)
+    cases = E.schedules_near_dividends(20, T / 20, T)[:3] + E.schedules_near_dividends(10, T / 10, T)[-6:]
+    assert len(cases) == 9
+    for c in cases:
+        paid = D.paying_steps(c.N, c.dt, c.dividends[0])
+        assert paid and paid == E.check(c, g[0])[0]
+        run = lambda ex: BR.solve_batch(m1, m2, c.N, c.dt, THETA, R_D, R_F, RHO, SIGMA, KAPPA, ETA, *(x[None] for x in g), ex,
+                                        dividends=c.dividends, put_strikes=[K] if put else None)[0]
+        seen = paying_steps_seen(monkeypatch, lambda: run(c.events))
+        monkeypatch.undo()
+        assert seen == [(n, c.dividends[1][q], c.dividends[2][q]) for n, q in sorted(paid.items())], (c.name, seen, paid)
+        # ... and without events the stepper is the oracle's dividend sweep on that schedule, bit for bit
+        p = O.make_params(m1, m2, c.N, c.dt, THETA, R_D, R_F, RHO, SIGMA, KAPPA, ETA, O.DIV, c.dividends, option_type=O.PUT if put else O.CALL,
+                          strikes=K if put else None)
+        assert np.array_equal(run([]), O.solve(p, *g)[0]), c.name
