@@ -26,6 +26,8 @@
  *                                      v-row of V_0, from the state the sweep leaves on the device
  *   hadi_maturity_ladder, hadi_compute_{base_prices,jacobian}_ladder <- no counterpart: the price node after chosen steps of ONE sweep
  *                                      (a whole maturity ladder per strike on a shared delta_t)
+ *   hadi_sample_ladder, hadi_compute_{base_prices,jacobian}_samples <- no counterpart: the ladder with the state of row V_0
+ *                                      evaluated at arbitrary spots (4-point interpolants) on the device, inside the time loop
  *   hadi_bermudan_timestepping, hadi_compute_{base_prices,jacobian}_bermudan <- no counterpart: the European sweep with exercise
  *                                      on chosen steps (U <- max(U, payoff) at their end)
  *   hadi_barrier_timestepping, hadi_compute_{base_prices,jacobian}_barrier <- no counterpart: the European sweep with a knock-out
@@ -220,7 +222,7 @@ int hadi_get_timing(const hadi_ctx *ctx, hadi_timing *out);
  *                 (profiles/r08_small_sch_ab.txt)
  *   "graph"       hipGraph replay of the time loop for small batches (default 1).  The handle caches up to 8 captured loops,
  *                 keyed by everything their nodes bake in: the launch geometry of every sub-batch, the scheme, variant and
- *                 precision, the steps that carry a dividend, the snapshot steps of a ladder call, the exercise steps of a Bermudan call, the monitoring steps of a barrier call, and every device address the loop uses (the library's buffers --
+ *                 precision, the steps that carry a dividend, the snapshot steps of a ladder call (and the sample count of a sample call: its taps are data, located again on every call), the exercise steps of a Bermudan call, the monitoring steps of a barrier call, and every device address the loop uses (the library's buffers --
  *                 rs_tab and the fp64 packed U of an fp32-state sweep among them -- and the caller's s-grid).  Whenever a call
  *                 frees a buffer to grow it, the whole cache is dropped first, so a replay never touches freed memory.
  *                 Read-only counters, cumulative over the handle's life (hadi_get_tuning only; hadi_set_tuning returns
@@ -382,6 +384,44 @@ int hadi_compute_base_prices_ladder(hadi_ctx *ctx, const hadi_problem *p, double
                                     double *prices /* [n][n_snap] */);
 int hadi_compute_jacobian_ladder(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, int n_snap,
                                  const int *snap_steps, double *J /* [n][n_snap][5] */, double *base_prices /* [n][n_snap] */);
+
+/* Sampled ladder -- NOT a reference feature.  The ladder returns one number per instance and snapshot: the node where S_0 sits.
+ * These three calls evaluate the state of the same v-row at n_samp arbitrary spots instead, inside the time loop, on the device;
+ * the field never leaves the GPU.  A sample call IS a ladder call: the same route and kernels, admitted and refused exactly where
+ * hadi_maturity_ladder / hadi_compute_base_prices_ladder / hadi_compute_jacobian_ladder are (American sweeps on the explicit
+ * pair, never the resident sweep or the team launch, HADI_STATE_FP32 and call data with r_f != 0: HADI_ERR_UNSUPPORTED, N_i:
+ * HADI_ERR_INVALID; delta_t_i, V_0_i, puts, dividends and the predictor-corrector schemes are allowed); wherever the ladder copies
+ * one node, a sample call evaluates n_samp interpolants.  snap_steps = {N} is the plain "sample at T" use.
+ *
+ * Definition of a sample.  For instance k the row is j0 by the ladder's rule: the first v-node within 1e-10 of V_0 (or V_0_i[k]),
+ * row 0 if there is none.  With s_0 < .. < s_m1 the nodes of the instance's own vec_s and x the spot:
+ *   node hit    if some |s_i - x| < 1e-10, the first such i is a single tap: the value is U(i, j0) bit for bit, times the scale.
+ *               With scale 1 and x = S_0 this is exactly what hadi_maturity_ladder returns.
+ *   off grid    if x is NaN, or x < s_0, or x > s_m1 beyond that tolerance, the entry is NaN and the call returns
+ *               HADI_ERR_NOT_ON_GRID (the ladder's status for S_0 off the s-grid); the other entries are valid.
+ *   interior    otherwise i is the largest index with s_i < x and the stencil starts at i0 = min(max(i - 1, 0), m1 - 3) (clamped at
+ *               both ends).  w_a = prod_{b != a} (x - s_{i0+b}) / prod_{b != a} (s_{i0+a} - s_{i0+b}), a = 0..3, numerator and
+ *               denominator each accumulated over increasing b, then one division.  The value is
+ *               fma(w3, U3, fma(w2, U2, fma(w1, U1, w0 * U0))) with U_a = U(i0 + a, j0), then one multiplication by the scale.
+ *   degenerate  a stencil with a zero interval (or m1 < 3) gives non-finite weights: the entry is NaN, the call returns
+ *               HADI_ERR_INVALID (which takes precedence over an off-grid sample of the same call).
+ * Cubic, because a linear interpolant adds Gamma ds^2 / 8, the same order as the scheme's own spatial error; the 4-point one does not.
+ * For a Jacobian the six groups' samples are located on the groups' own rebuilt v-grids: the v0 column samples its own row.
+ * Errors beyond the ladder's (which keep their status): a NULL struct, spots or output, n_samp outside 1..1024, rows other than 1
+ * or n_instances, a non-finite scale: HADI_ERR_INVALID.  Outputs follow p->memspace; spots / scales / snap_steps are host arrays. */
+typedef struct hadi_samples {
+    int n_samp;            /* 1 .. 1024 samples per instance */
+    const double *spots;   /* host [rows][n_samp]: spot x_q at which the state is evaluated */
+    const double *scales;  /* host [rows][n_samp] or NULL (= 1): out = scale_q * U(x_q, V_0) */
+    int rows;              /* 1 (one list for the batch) or n_instances */
+} hadi_samples;
+int hadi_sample_ladder(hadi_ctx *ctx, const hadi_problem *p, double V_0, const hadi_samples *samples, int n_snap,
+                       const int *snap_steps, double *out /* [n][n_snap][n_samp] */);
+int hadi_compute_base_prices_samples(hadi_ctx *ctx, const hadi_problem *p, double V_0, const hadi_samples *samples, int n_snap,
+                                     const int *snap_steps, double *out /* [n][n_snap][n_samp] */);
+int hadi_compute_jacobian_samples(hadi_ctx *ctx, const hadi_problem *p, double V_0, double eps, const hadi_samples *samples,
+                                  int n_snap, const int *snap_steps, double *J /* [n][n_snap][n_samp][5] */,
+                                  double *base /* [n][n_snap][n_samp] */);
 
 /* Bermudan options -- NOT a reference feature.  A Bermudan sweep is the European sweep of hadi_DO_timestepping (variant HADI_EU
  * or HADI_DIV) with one addition: after the last pass of every listed step n, every node of every instance that lists n takes

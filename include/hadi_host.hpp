@@ -221,6 +221,59 @@ inline void compute_jacobian_ladder(Handle &h, double S_0, double V_0, double /*
                                                   base_prices.data()));
 }
 
+// Sampled ladder (hadi_sample_ladder and its two launchers; NOT in the reference): the ladder's calls with the state of the v-row
+// of V_0 evaluated at arbitrary spots where the ladder copies the node of S_0 (hadi.h states the interpolant).  spots / scales:
+// [rows][spots.size() / rows], rows = 1 (one list for the batch) or num_strikes; scales empty = 1.
+struct Samples {
+    std::vector<double> spots, scales;
+    int rows = 1;
+    hadi_samples view() const {
+        if (rows < 1 || spots.empty() || spots.size() % (size_t)rows) throw std::runtime_error("spots is not [rows][n_samp]");
+        if (!scales.empty() && scales.size() != spots.size()) throw std::runtime_error("scales does not have the shape of spots");
+        return hadi_samples{(int)(spots.size() / rows), spots.data(), scales.empty() ? nullptr : scales.data(), rows};
+    }
+};
+// out: [num_strikes][snap_steps.size()][n_samp].  workspace.U holds the initial condition and is not modified.
+inline void sample_ladder(Handle &h, double V_0, double /*T*/, double r_d, double r_f, double rho, double sigma, double kappa,
+                          double eta, int m1, int m2, int /*total_size*/, int N, double theta, double delta_t, int num_strikes,
+                          const GridViews &deviceGrids, const DO_Workspace &workspace, const Samples &samples,
+                          const std::vector<int> &snap_steps, std::vector<double> &out, int variant = HADI_EU,
+                          const std::vector<double> *U_0 = nullptr, const Dividends *div = nullptr, const PutStrikes *put = nullptr) {
+    const hadi_samples s = samples.view();
+    out.resize((size_t)num_strikes * snap_steps.size() * s.n_samp);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  const_cast<double *>(workspace.U.data()), U_0 ? U_0->data() : nullptr, div, put);
+    detail::check(h, hadi_sample_ladder(h.ctx, &p, V_0, &s, (int)snap_steps.size(), snap_steps.data(), out.data()));
+}
+// ... with the v-grid rebuilt for V_0, as compute_base_prices does
+inline void compute_base_prices_samples(Handle &h, double V_0, double /*T*/, double r_d, double r_f, double rho, double sigma,
+                                        double kappa, double eta, int m1, int m2, int /*total_size*/, int N, double theta,
+                                        double delta_t, int num_strikes, const GridViews &deviceGrids, const DO_Workspace &workspace,
+                                        const Samples &samples, const std::vector<int> &snap_steps, std::vector<double> &out,
+                                        int variant = HADI_EU, const std::vector<double> *U_0 = nullptr, const Dividends *div = nullptr,
+                                        const PutStrikes *put = nullptr) {
+    const hadi_samples s = samples.view();
+    out.resize((size_t)num_strikes * snap_steps.size() * s.n_samp);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  const_cast<double *>(workspace.U.data()), U_0 ? U_0->data() : nullptr, div, put);
+    detail::check(h, hadi_compute_base_prices_samples(h.ctx, &p, V_0, &s, (int)snap_steps.size(), snap_steps.data(), out.data()));
+}
+// J: [num_strikes][snap_steps.size()][n_samp][5], base: [num_strikes][snap_steps.size()][n_samp]
+inline void compute_jacobian_samples(Handle &h, double V_0, double /*T*/, double r_d, double r_f, double rho, double sigma, double kappa,
+                                     double eta, int m1, int m2, int /*total_size*/, int N, double theta, double delta_t,
+                                     int num_strikes, const GridViews &deviceGrids, const std::vector<double> &U_0,
+                                     const Samples &samples, const std::vector<int> &snap_steps, std::vector<double> &J,
+                                     std::vector<double> &base, double eps = 1e-6, int variant = HADI_EU,
+                                     const Dividends *div = nullptr, const PutStrikes *put = nullptr) {
+    const hadi_samples s = samples.view();
+    J.resize((size_t)num_strikes * snap_steps.size() * s.n_samp * 5);
+    base.resize((size_t)num_strikes * snap_steps.size() * s.n_samp);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  nullptr, U_0.data(), div, put);
+    detail::check(h, hadi_compute_jacobian_samples(h.ctx, &p, V_0, eps, &s, (int)snap_steps.size(), snap_steps.data(), J.data(),
+                                                   base.data()));
+}
+
 // Bermudan options (hadi_bermudan_timestepping and its two launchers; NOT in the reference): the European or dividend sweep with
 // U <- max(U, payoff) at the end of the listed steps.  ex_steps: [ex_rows][ex_steps.size() / ex_rows], ex_rows = 1 (one schedule
 // for the batch) or num_strikes (rows strictly increasing within 1..N, zero-padded).  The payoff is U_0, or the initial

@@ -11,11 +11,13 @@ from ._native import (G_PRICE, G_DELTA, G_GAMMA, G_DV, G_DVV, G_DSV, G_THETA, G_
 from ._native import SCHEME_DOUGLAS, SCHEME_CRAIG_SNEYD, SCHEME_MCS, SCHEME_HV  # noqa: F401
 from .grid import Grid, GridViewsBatch  # noqa: F401
 from .solver import (HestonADI, DOWorkspace, Dividends, compute_parameter_update,  # noqa: F401
-                     exercise_steps, knock_out_payoff, lm_partials, lm_partials_device, lm_solve, monitoring_steps)
+                     exercise_steps, knock_out_payoff, lm_partials, lm_partials_device, lm_solve, monitoring_steps,
+                     strike_samples)
 from .distributed import Communicator, shard_range  # noqa: F401
 from .calibration import (CalibrationPoint, calibrate, calibrate_american, calibrate_american_dividends,  # noqa: F401
                           calibrate_american_dividends_multi_maturity, calibrate_bermudan, calibrate_dividends, calibrate_european,
-                          calibrate_european_maturity_ladder, calibrate_european_multi_maturity, clamp_parameters,
+                          calibrate_european_maturity_ladder, calibrate_european_multi_maturity, calibrate_european_surface,
+                          clamp_parameters,
                           export_calibration_csv, make_calibration_points, make_ladder_points)
 from . import market  # noqa: F401
 
@@ -26,6 +28,6 @@ __all__ = ["EU", "AM", "DIV", "AM_DIV", "CALL", "PUT", "lm_partials_device", "ST
            "calibrate_american", "calibrate_dividends", "calibrate_american_dividends",
            "calibrate_european_multi_maturity", "calibrate_american_dividends_multi_maturity",
            "make_calibration_points", "export_calibration_csv", "make_ladder_points", "calibrate_european_maturity_ladder",
-           "calibrate_bermudan", "exercise_steps", "knock_out_payoff", "monitoring_steps",
+           "calibrate_european_surface", "strike_samples", "calibrate_bermudan", "exercise_steps", "knock_out_payoff", "monitoring_steps",
            "G_PRICE", "G_DELTA", "G_GAMMA", "G_DV", "G_DVV", "G_DSV",
            "G_THETA", "G_LAMBDA", "N_GREEKS", "GREEK_NAMES"]

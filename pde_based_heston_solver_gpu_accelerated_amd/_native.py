@@ -56,6 +56,11 @@ class Barrier(C.Structure):
     _fields_ = [("lower_i", _dp), ("upper_i", _dp), ("rebate_i", _dp), ("n_mon", C.c_int), ("mon_steps", _ip), ("mon_rows", C.c_int)]
 
 
+class Samples(C.Structure):
+    """struct hadi_samples (include/hadi.h)."""
+    _fields_ = [("n_samp", C.c_int), ("spots", _dp), ("scales", _dp), ("rows", C.c_int)]
+
+
 class Timing(C.Structure):
     """struct hadi_timing (include/hadi.h)."""
     _fields_ = [
@@ -74,6 +79,7 @@ EXPORTS = [
     "hadi_make_grid", "hadi_rebuild_variance", "hadi_find_s_index", "hadi_find_v_index",
     "hadi_DO_timestepping", "hadi_parallel_DO_solve", "hadi_compute_greeks",
     "hadi_maturity_ladder", "hadi_compute_base_prices_ladder", "hadi_compute_jacobian_ladder",
+    "hadi_sample_ladder", "hadi_compute_base_prices_samples", "hadi_compute_jacobian_samples",
     "hadi_bermudan_timestepping", "hadi_compute_base_prices_bermudan", "hadi_compute_jacobian_bermudan",
     "hadi_barrier_timestepping", "hadi_compute_base_prices_barrier", "hadi_compute_jacobian_barrier",
     "hadi_compute_base_prices", "hadi_compute_base_prices_american",
@@ -158,6 +164,12 @@ def _load(LIB_PATH):
         L.hadi_compute_base_prices_barrier.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, _bp, C.c_void_p]
         L.hadi_compute_jacobian_barrier.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_double, _bp, C.c_void_p,
                                                     C.c_void_p]
+    if hasattr(L, "hadi_sample_ladder"):  # (likewise: a build from before the sampled ladder)
+        _sp = C.POINTER(Samples)
+        for name in ("hadi_sample_ladder", "hadi_compute_base_prices_samples"):
+            getattr(L, name).argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, _sp, C.c_int, _ip, C.c_void_p]
+        L.hadi_compute_jacobian_samples.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, _sp, C.c_int, _ip,
+                                                    C.c_void_p, C.c_void_p]
     for sfx in ("", "_american", "_dividends", "_american_dividends"):
         getattr(L, "hadi_compute_base_prices" + sfx).argtypes = [
             C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_void_p]

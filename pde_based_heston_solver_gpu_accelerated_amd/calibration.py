@@ -317,6 +317,62 @@ def calibrate_european_maturity_ladder(solver, S_0, r_d, r_f, kappa, eta, sigma,
                      scheme=scheme, launchers=launch, **kw)
 
 
+def _surface_launchers(solver, r_d, r_f, m1, m2, theta, delta_t, snap_steps, grids, U_0, spots, scales, scheme=0):
+    """The closures of calibrate() over the sample launchers: ONE instance, whose [1][maturity][strike] outputs are already in the
+    residual order m * len(strikes) + s."""
+    total_size = (m1 + 1) * (m2 + 1)
+    N = int(snap_steps[-1])
+    sch = {"scheme": scheme} if scheme else {}
+
+    def jac(k, e, s, r, v, eps):
+        J, base = solver.compute_jacobian_samples(spots, v, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t, 1, grids,
+                                                  U_0, snap_steps, scales=scales, eps=eps, **sch)
+        return J.reshape(-1, 5), base.reshape(-1)
+
+    def base(k, e, s, r, v):
+        ws = _WS()
+        ws.U = _clone(U_0)
+        return solver.compute_base_prices_samples(spots, v, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t, 1, grids,
+                                                  ws, snap_steps, scales=scales, **sch).reshape(-1)
+
+    return jac, base
+
+
+def calibrate_european_surface(solver, S_0, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, theta, base_strike, strikes, maturities,
+                               delta_t, grids, U_0, market_prices, max_iter=15, tol=None, delta_tol=None, n_total=None, scheme=0,
+                               **kw):
+    """calibrate_european_maturity_ladder with the strikes taken out of the batch as well: `grids` / `U_0` hold ONE instance, built
+    at `base_strike`, and every strike of every maturity is read off its sweep through strike_samples (the homogeneity of the Heston
+    problem in (s, K); solver.strike_samples states the claim and its limits) -- six sweeps per Jacobian and one per trial,
+    whatever the number of strikes, so the instance can afford a finer grid.  `strikes` are this rank's strikes (the partial-sum
+    all-reduce shards the rows as before); every maturity is a whole number of steps of delta_t (make_ladder_points raises
+    otherwise).  market_prices: [len(maturities) * len(strikes)] in the order m * len(strikes) + s, as the residuals.  S_0 K / K'
+    must lie on the base grid for every strike K' (HadiError, status 4, otherwise).  r_f must be 0 for calls (the ladder's rule).
+    `pde_solves` counts the sweeps actually run: six per Jacobian and one per trial.  The prices are those of the grid scaled per
+    strike, not of GridViewsBatch.for_strikes' grids: on the oracle the two differ by 1.5e-2 / 2.7e-3 / 1.1e-3 on 50x25 / 100x50 /
+    200x100 (strikes 80 .. 125 around K = 100), inside the grids' own discretisation error (4.4e-2 / 1.6e-2 / 1.1e-2 against the
+    semi-analytic price).
+    Measured on one MI355X (DESIGN.md "Sampled ladder", profiles/surface_ab.txt), ms per call, 10 maturities (10 .. 100 steps), the
+    ladder launchers with one 50x25 instance per strike -> this driver's launchers with one instance on 50x25 / 100x50 / 200x100:
+    500 strikes, Jacobian 3.72 -> 1.06 / 1.30 / 1.58 and base prices 1.26 -> 1.03 / 1.26 / 1.46; 50 strikes, Jacobian 1.26 -> 1.04 /
+    1.21 / 1.47 and base prices 1.03 -> 1.02 / 1.18 / 1.37.  It loses wherever the ladder call is already at its fixed cost of about
+    1 ms: the base-price calls on the finer grids and the 50-strike Jacobian on 200x100."""
+    pts = make_ladder_points(strikes, maturities, delta_t)
+    n_s, n_m = len(strikes), len(maturities)
+    if grids.Vec_s.shape[0] != 1:
+        raise ValueError("a surface takes ONE grid, built at base_strike (%d grids)" % grids.Vec_s.shape[0])
+    market = np.asarray(market_prices, dtype=np.float64).reshape(-1)
+    if market.size != n_s * n_m:
+        raise ValueError("market_prices must hold len(maturities) * len(strikes) prices, maturity by maturity")
+    spots, scales = _solver.strike_samples(S_0, base_strike, strikes)
+    snap_steps = [pts[m * n_s].time_steps for m in range(n_m)]
+    t, dtol = multi_maturity_tolerances(n_total or len(pts))
+    launch = _surface_launchers(solver, r_d, r_f, m1, m2, theta, delta_t, snap_steps, grids, U_0, spots, scales, scheme=scheme)
+    return calibrate(solver, EU, S_0, None, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, None, theta, grids, U_0, market,
+                     max_iter=max_iter, tol=t if tol is None else tol, delta_tol=dtol if delta_tol is None else delta_tol,
+                     scheme=scheme, launchers=launch, **kw)
+
+
 def _bermudan_launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, schedule, grids, U_0, dividends, scheme=0):
     """The closures of calibrate() over the Bermudan launchers: one instance per strike, as the single-maturity drivers."""
     n_loc = grids.Vec_s.shape[0]

@@ -64,6 +64,9 @@ struct Ctx {
     // and the rebates [n]
     DevBuf ko_flag, ko_bounds, ko_iab, ko_rebate;
     DevBuf snap_steps, snap_node, snap_out;  // maturity ladder: the snapshot steps, the instances' price nodes, the snapshots [n][n_snap]
+    // sampled ladder: the spots [n][n_samp] and behind them the scales [n][n_samp] as staged; the tap records [n][n_samp] and behind
+    // them the samples' flag words [n][n_samp] (hadi_sample_locate_kernel); the samples [n][n_snap][n_samp]
+    DevBuf samp_in, samp_tap, samp_out;
     // Sticky device error word: one int in host-pinned, device-visible memory.  Kernels OR a HADI_DEVERR_* code into it
     // (system-scope atomic, only ever on a failure path); finish_timing reads it after the stream synchronisation every
     // entry point ends with -- no copy, no extra launch -- and turns a non-zero word into HADI_ERR_INTERNAL.
@@ -232,6 +235,11 @@ struct SweepDesc {
     const int *snap_steps = nullptr;
     double S_0 = 0, V_0 = 0;
     const double *d_v0_i = nullptr;  // device [n] or null: per-instance V_0 of the node's v-row
+    // sampled ladder (hadi_sample_ladder and its launchers): n_samp > 0 = a ladder call that evaluates n_samp interpolants of the row
+    // of V_0 where the ladder copies one node (S_0 is not read).  spots / scales: host [samp_rows][n_samp] (validated; scales may be
+    // null = 1); samp_rows 1 = one list for the batch, else one row per source instance (instance k reads row k % n_src)
+    int n_samp = 0, samp_rows = 0;
+    const double *spots = nullptr, *scales = nullptr;
     // Bermudan (hadi_bermudan_timestepping and its launchers): n_ex > 0 = ex_steps [ex_rows][n_ex] (host array, validated: rows
     // strictly increasing within 1 .. N_k, zero-padded) lists the steps at whose end an instance takes U <- max(U, payoff); ex_rows
     // 1 = one schedule for the batch, else one row per source instance (instance k reads row k % n_src: a Jacobian's groups share)
@@ -282,7 +290,7 @@ HadiRouteIn route_in(const Ctx *c, const SweepDesc &d) {
     in.cu_count = c->cu_count;
     in.n = d.n; in.m1 = d.m1; in.m2 = d.m2; in.variant = d.variant; in.scheme = d.scheme; in.prec = d.prec;
     in.theta = d.theta; in.rates_equal = d.r_d == d.r_f;
-    in.debug = d.debug; in.profiling = c->profiling != 0; in.n_snap = d.n_snap; in.dividends = d.num_div > 0;
+    in.debug = d.debug; in.profiling = c->profiling != 0; in.n_snap = d.n_snap; in.n_samp = d.n_samp; in.dividends = d.num_div > 0;
     in.uniform_steps = d.uniform_steps; in.team_failed = c->team_failed != 0; in.t = c->t;
     return in;
 }
@@ -345,6 +353,10 @@ int grow_buffers(Ctx *c, Sweep &w) {
             (rc = ensure(c, c->snap_out, 8 * n * d.n_snap)) || (rc = ensure(c, c->status, sizeof(int) * n)))
             return rc;
         for (int q = 0; q < d.n_snap; q++) w.snap_q[d.snap_steps[q]] = q;
+        const size_t ns = n * d.n_samp;  // a sample call: the staged lists, the tap table with its flag words, the samples
+        if (ns && ((rc = ensure(c, c->samp_in, 2 * 8 * ns)) || (rc = ensure(c, c->samp_tap, (sizeof(HadiTap) + sizeof(int)) * ns)) ||
+                   (rc = ensure(c, c->samp_out, 8 * ns * d.n_snap))))
+            return rc;
     }
     return HADI_OK;
 }
@@ -418,6 +430,31 @@ int stage_barrier(Ctx *c, const Sweep &w) {
     return HADI_OK;
 }
 
+// Sampled ladder: the lists of all n instances to the device, then the tap records and flag words from the sweep's own device
+// grids (hadi_sample_locate_kernel) -- on every call, also before a replay: the taps are data, not part of a captured loop.
+// The single price node of the ladder is not used: every instance's entry reads "none".
+HadiTap *samp_taps(Ctx *c) { return ptr<HadiTap>(c->samp_tap); }
+int *samp_flags(Ctx *c, const SweepDesc &d) { return reinterpret_cast<int *>(samp_taps(c) + (size_t)d.n * d.n_samp); }
+int stage_samples(Ctx *c, const Sweep &w) {
+    const SweepDesc &d = w.d;
+    const size_t ns = (size_t)d.n * d.n_samp;
+    std::vector<double> in(2 * ns);
+    for (int k = 0; k < d.n; k++) {
+        const size_t row = (size_t)(d.samp_rows > 1 ? k % d.n_src : 0) * d.n_samp;
+        for (int q = 0; q < d.n_samp; q++) {
+            in[(size_t)k * d.n_samp + q] = d.spots[row + q];
+            in[ns + (size_t)k * d.n_samp + q] = d.scales ? d.scales[row + q] : 1.0;
+        }
+    }
+    int rc;
+    if ((rc = stage_to_device(c, c->samp_in.p, in.data(), in.size() * 8))) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->snap_node.p, 0xff, sizeof(int) * (size_t)d.n, c->stream));
+    hipLaunchKernelGGL(hadi_sample_locate_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, c->stream, w.r.pl.L, d.n, d.n_samp,
+                       d.d_vec_s, d.d_vec_v, d.d_v0_i, d.V_0, ptr<double>(c->samp_in), ptr<double>(c->samp_in) + ns, samp_taps(c),
+                       samp_flags(c, d));
+    return HADI_OK;
+}
+
 // Parameters and dividend tables to the device, the operator tables (setup), the ladder's price nodes (locate), the packed
 // state and, for American sweeps, the payoff and its shape -- which decides w.amp.
 int stage_inputs(Ctx *c, Sweep &w) {
@@ -444,8 +481,12 @@ int stage_inputs(Ctx *c, Sweep &w) {
     hipLaunchKernelGGL(hadi_setup_kernel, dim3(d.n), dim3(256), 0, s, sa);
     if (r.ladder) {
         if ((rc = stage_to_device(c, c->snap_steps.p, d.snap_steps, sizeof(int) * d.n_snap))) return rc;
-        hipLaunchKernelGGL(hadi_locate_kernel, dim3((d.n + 63) / 64), dim3(64), 0, s, L, d.n, d.d_vec_s, d.d_vec_v, d.S_0, d.d_v0_i, d.V_0,
-                           ptr<int>(c->snap_node), ptr<int>(c->status));
+        if (d.n_samp > 0) {
+            if ((rc = stage_samples(c, w))) return rc;
+        } else {
+            hipLaunchKernelGGL(hadi_locate_kernel, dim3((d.n + 63) / 64), dim3(64), 0, s, L, d.n, d.d_vec_s, d.d_vec_v, d.S_0, d.d_v0_i, d.V_0,
+                               ptr<int>(c->snap_node), ptr<int>(c->status));
+        }
     }
 
     hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src, d.d_natU, ptr<double>(c->U));
@@ -539,6 +580,9 @@ int small_args(Ctx *c, const Sweep &w, HadiSmallArgs &sm) {
     if (w.r.ladder) {
         sm.snap_steps = ptr<int>(c->snap_steps); sm.n_snap = d.n_snap;
         sm.snap_node = ptr<int>(c->snap_node); sm.snap_out = ptr<double>(c->snap_out);
+        if (d.n_samp > 0) {
+            sm.taps = samp_taps(c); sm.n_samp = d.n_samp; sm.samp_out = ptr<double>(c->samp_out);
+        }
     }
     return HADI_OK;
 }
@@ -705,7 +749,12 @@ int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
                                ptr<int>(c->ko_flag) + (size_t)o * w.mon_stride, w.mon_stride, ptr<int>(c->ko_iab) + 2 * (size_t)o,
                                ptr<double>(c->ko_rebate) + o, nstep);
         }
-        if (r.ladder && w.snap_q[nstep] >= 0)  // (U is explicit here: a ladder call never runs in the P representation)
+        if (r.ladder && w.snap_q[nstep] >= 0 && d.n_samp > 0) {  // a sample call: n_samp interpolants where the ladder copies one node
+            const size_t ns = (size_t)nsb * d.n_samp;
+            hipLaunchKernelGGL(hadi_sample_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, q, L, nsb, Ub,
+                               samp_taps(c) + (size_t)o * d.n_samp, ptr<double>(c->samp_out) + (size_t)o * d.n_snap * d.n_samp, d.n_snap,
+                               d.n_samp, w.snap_q[nstep]);
+        } else if (r.ladder && w.snap_q[nstep] >= 0)  // (U is explicit here: a ladder call never runs in the P representation)
             hipLaunchKernelGGL(hadi_snap_kernel, dim3((nsb + 63) / 64), dim3(64), 0, q, L, nsb, Ub, ptr<int>(c->snap_node) + o,
                                ptr<double>(c->snap_out) + (size_t)o * d.n_snap, d.n_snap, w.snap_q[nstep]);
         if (xstep)
@@ -783,6 +832,9 @@ std::string graph_key(const Ctx *c, const Sweep &w) {
         put(lad, sizeof(lad));
         put(&d.n_snap, sizeof(int));
         put(d.snap_steps, sizeof(int) * d.n_snap);
+        const void *smp[] = {c->samp_tap.p, c->samp_out.p};  // a sample call: hadi_sample_kernel in hadi_snap_kernel's place
+        put(&d.n_samp, sizeof(int));
+        if (d.n_samp > 0) put(smp, sizeof(smp));
     }
     if (w.r.bermudan) {  // the per-instance table is re-uploaded every call; the node list only depends on which steps carry an
                          // exercise launch, on the table's address and on its stride (the payoff's address is in both argument blocks)
@@ -1011,6 +1063,26 @@ int check_ladder(Ctx *c, const hadi_problem *p, int n_snap, const int *snap_step
     return HADI_OK;
 }
 
+// What the sample entry points ask beyond check_ladder (which has passed): they are refused exactly where the ladder is.
+int check_samples(Ctx *c, const hadi_problem *p, const hadi_samples *sp) {
+    if (!sp || !sp->spots) return fail(c, HADI_ERR_INVALID, "samples (struct or spots) missing");
+    if (sp->n_samp < 1 || sp->n_samp > 1024) return fail(c, HADI_ERR_INVALID, "n_samp must be within 1..1024 (is %d)", sp->n_samp);
+    if (sp->rows != 1 && sp->rows != p->n_instances) return fail(c, HADI_ERR_INVALID, "samples: rows must be 1 or n_instances");
+    if (sp->scales)
+        for (size_t e = 0; e < (size_t)sp->rows * sp->n_samp; e++)
+            if (!std::isfinite(sp->scales[e])) return fail(c, HADI_ERR_INVALID, "samples: scale %zu is not finite", e);
+    return HADI_OK;
+}
+// After the sweep of a sample call: the samples' flag words decide the status (they came back with the stream synchronisation).
+int samples_status(Ctx *c, const std::vector<int> &flags, int n_samp) {
+    for (size_t e = 0; e < flags.size(); e++)
+        if (flags[e] & HADI_SAMPLE_DEGENERATE)
+            return fail(c, HADI_ERR_INVALID, "sample %zu of instance %zu: degenerate stencil (an s-interval of length zero, or m1 < 3)", e % n_samp, e / n_samp);
+    for (size_t e = 0; e < flags.size(); e++)
+        if (flags[e]) return fail(c, HADI_ERR_NOT_ON_GRID, "sample %zu of instance %zu is off the s-grid", e % n_samp, e / n_samp);
+    return HADI_OK;
+}
+
 // What the Bermudan entry points ask beyond check_problem (which has passed).
 int check_bermudan(Ctx *c, const hadi_problem *p, const ExSched &ex) {
     if (p->variant == HADI_AM || p->variant == HADI_AM_DIV)
@@ -1108,13 +1180,15 @@ int rebuild_v_device(Ctx *c, int n, int m2, const std::vector<double> &v0i) {
 // took on the way; p->U and p->lambda_bar are not written.
 int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, double S_0, double V_0, double *prices_out,
                  int debug = 0, int debug_step = 1, double *debug_out = nullptr, int n_snap = 0, const int *snap_steps = nullptr,
-                 const ExSched *ex = nullptr, const hadi_barrier *ko = nullptr) {
+                 const ExSched *ex = nullptr, const hadi_barrier *ko = nullptr, const hadi_samples *const *smp = nullptr) {
     int rc = check_problem(c, p, true, !rebuild_v);
     if (rc) return rc;
     if (ex && (rc = check_bermudan(c, p, *ex))) return rc;
     if (ko && (rc = check_barrier(c, p, ko))) return rc;
     const bool ladder = n_snap > 0 || snap_steps;
     if (ladder && (rc = check_ladder(c, p, n_snap, snap_steps, prices_out))) return rc;
+    if (smp && (rc = check_samples(c, p, *smp))) return rc;
+    const int n_samp = smp ? (*smp)->n_samp : 0;  // (sampled ladder: prices_out is [n][n_snap][n_samp])
     if (debug && !debug_out) return fail(c, HADI_ERR_INVALID, "output array missing");
     if (debug && (p->scheme != HADI_SCHEME_DOUGLAS || p->state_precision != HADI_STATE_FP64))
         return fail(c, HADI_ERR_UNSUPPORTED, "diagnostics cover fp64 Douglas steps");
@@ -1166,6 +1240,7 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
     if (ladder) {
         d.n_snap = n_snap; d.snap_steps = snap_steps; d.S_0 = S_0; d.V_0 = V_0;
         d.d_v0_i = per_inst_v0 ? ptr<double>(c->v0_i) : nullptr;
+        if (smp) { d.n_samp = n_samp; d.samp_rows = (*smp)->rows; d.spots = (*smp)->spots; d.scales = (*smp)->scales; }
     }
     if (ex && ex->n_ex > 0) { d.n_ex = ex->n_ex; d.ex_rows = ex->rows; d.ex_steps = ex->steps; }
     if (ko && ko->n_mon > 0) {
@@ -1176,6 +1251,14 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
     HadiPlan pl;
     if ((rc = run_sweep(c, d, pl))) return rc;
 
+    if (ladder && n_samp > 0) {  // the samples and their flag words are all that leaves the device
+        if ((rc = from_device(c, p->memspace, prices_out, ptr<double>(c->samp_out), (size_t)n * n_snap * n_samp))) return rc;
+        std::vector<int> hf((size_t)n * n_samp);
+        HIP_TRY(c, hipMemcpyAsync(hf.data(), samp_flags(c, d), hf.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipGetLastError());
+        if ((rc = finish_timing(c, d))) return rc;
+        return samples_status(c, hf, n_samp);
+    }
     if (ladder) {  // the snapshots and the locate step's status words are all that leaves the device
         if ((rc = from_device(c, p->memspace, prices_out, ptr<double>(c->snap_out), (size_t)n * n_snap))) return rc;
         std::vector<int> hs(n);
@@ -1343,13 +1426,17 @@ int jacobian_grids(Ctx *c, const hadi_problem *p, int G, double V_0, double eps,
 // group 0 = base, 1..4 = kappa, eta, sigma, rho + eps, 5 = v-grid rebuilt for V_0 + eps.
 // Ladder (n_snap > 0; hadi_compute_jacobian_ladder): J [n][n_snap][5] and base_prices [n][n_snap] from the snapshots of the 6n solves.
 int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double eps, double *J, double *base_prices,
-                    int n_snap = 0, const int *snap_steps = nullptr, const ExSched *ex = nullptr, const hadi_barrier *ko = nullptr) {
+                    int n_snap = 0, const int *snap_steps = nullptr, const ExSched *ex = nullptr, const hadi_barrier *ko = nullptr,
+                    const hadi_samples *const *smp = nullptr) {
     int rc = check_problem(c, p, false, false);
     if (rc) return rc;
     if (ex && (rc = check_bermudan(c, p, *ex))) return rc;
     if (ko && (rc = check_barrier(c, p, ko))) return rc;
     const bool ladder = n_snap > 0 || snap_steps;
     if (ladder && (rc = check_ladder(c, p, n_snap, snap_steps, (J && base_prices) ? J : nullptr))) return rc;
+    if (smp && (rc = check_samples(c, p, *smp))) return rc;
+    const int n_samp = smp ? (*smp)->n_samp : 0;
+    const int n_col = n_snap * std::max(n_samp, 1);  // columns per instance: a sample call's [n_snap][n_samp] is the ladder's [n_snap]
     DeviceGuard guard(c->device);
     pin_rewind(c);
     if (!p->U_0) return fail(c, HADI_ERR_INVALID, "U_0 (initial condition) is required for the Jacobian");
@@ -1369,13 +1456,14 @@ int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, doubl
         d.par8[((size_t)3 * n0 + k) * 8 + 1] += eps;  // sigma
         d.par8[((size_t)4 * n0 + k) * 8 + 0] += eps;  // rho
     }
-    if ((rc = jacobian_grids(c, p, G, V_0, eps, n_snap, d))) return rc;
+    if ((rc = jacobian_grids(c, p, G, V_0, eps, n_col, d))) return rc;
     hipStream_t s = c->stream;
     // every solve starts from U_0 (jacobian_computation.cpp:307-309); payoff for American = U_0 too
     if ((rc = to_device(c, p->memspace, p->U_0, n0 * m, c->natU0, &d.d_natU))) return rc;
     d.d_natU0 = d.d_natU;
     if (ladder) {
         d.n_snap = n_snap; d.snap_steps = snap_steps; d.S_0 = S_0; d.V_0 = V_0; d.d_v0_i = ptr<double>(c->v0_i);
+        if (smp) { d.n_samp = n_samp; d.samp_rows = (*smp)->rows; d.spots = (*smp)->spots; d.scales = (*smp)->scales; }
     }
     if (ex && ex->n_ex > 0) { d.n_ex = ex->n_ex; d.ex_rows = ex->rows; d.ex_steps = ex->steps; }
     if (ko && ko->n_mon > 0) {
@@ -1393,12 +1481,12 @@ int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, doubl
     double *dJ = J, *db = base_prices;
     if (p->memspace == HADI_MEM_HOST) {
         dJ = ptr<double>(c->natOut);
-        db = dJ + (size_t)n0 * 5 * std::max(n_snap, 1);
+        db = dJ + (size_t)n0 * 5 * std::max(n_col, 1);
     }
-    const size_t nrow = (size_t)n0 * std::max(n_snap, 1);  // rows of J
-    if (ladder)
-        hipLaunchKernelGGL(hadi_jacobian_ladder_rows_kernel, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, s, n0, n_snap,
-                           ptr<double>(c->snap_out), eps, dJ, db);
+    const size_t nrow = (size_t)n0 * std::max(n_col, 1);  // rows of J
+    if (ladder)  // (a sample call: the same kernel with n_snap * n_samp columns)
+        hipLaunchKernelGGL(hadi_jacobian_ladder_rows_kernel, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, s, n0, n_col,
+                           n_samp > 0 ? ptr<double>(c->samp_out) : ptr<double>(c->snap_out), eps, dJ, db);
     else
         hipLaunchKernelGGL(hadi_jacobian_rows_kernel, dim3((n0 + 255) / 256), dim3(256), 0, s, n0, ptr<double>(c->prices), eps, dJ, db);
     if (p->memspace == HADI_MEM_HOST) {
@@ -1408,6 +1496,14 @@ int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, doubl
     std::vector<int> hs_fallback;
     int *hs = static_cast<int *>(pin_alloc(c, (size_t)n * sizeof(int)));  // (pinned: the copy does not block the host)
     if (!hs) { hs_fallback.resize(n); hs = hs_fallback.data(); }
+    if (n_samp > 0) {  // the flag words of all six groups' samples (the v0 group located its own row; the s-grids are the same)
+        std::vector<int> hf((size_t)n * n_samp);
+        HIP_TRY(c, hipMemcpyAsync(hf.data(), samp_flags(c, d), hf.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipGetLastError());
+        if ((rc = finish_timing(c, d))) return rc;
+        hf.resize((size_t)n0 * n_samp);
+        return samples_status(c, hf, n_samp);
+    }
     HIP_TRY(c, hipMemcpyAsync(hs, c->status.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipGetLastError());
     if ((rc = finish_timing(c, d))) return rc;
@@ -1431,7 +1527,7 @@ void release_handle(Ctx *c) {
                       &c->rinv, &c->rwork, &c->ipar, &c->par8, &c->g_s, &c->g_v, &c->g_ds, &c->g_dv, &c->src_v,
                       &c->src_dv, &c->sel_a, &c->sel_b, &c->v0_i, &c->natU, &c->natU0, &c->natOut, &c->prices,
                       &c->status, &c->div_flag, &c->div_amt, &c->div_pct, &c->V, &c->R1, &c->C2, &c->pay_mis, &c->Uf, &c->Yf,
-                      &c->order, &c->lm31, &c->team, &c->rs_tab, &c->snap_steps, &c->snap_node, &c->snap_out, &c->ex_flag,
+                      &c->order, &c->lm31, &c->team, &c->rs_tab, &c->snap_steps, &c->snap_node, &c->snap_out, &c->samp_in, &c->samp_tap, &c->samp_out, &c->ex_flag,
                       &c->ko_flag, &c->ko_bounds, &c->ko_iab, &c->ko_rebate};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
@@ -1769,6 +1865,28 @@ int hadi_compute_jacobian_barrier(hadi_ctx *ctx, const hadi_problem *p, double S
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && !barrier) return fail(c, HADI_ERR_INVALID, "barrier description missing");
     return jacobian_common(c, p, S_0, V_0, eps, J, base_prices, 0, nullptr, nullptr, barrier);
+}
+
+// ---- sampled ladder: the ladder's calls with n_samp interpolants of the row of V_0 in the single node's place --------------
+int hadi_sample_ladder(hadi_ctx *ctx, const hadi_problem *p, double V_0, const hadi_samples *samples, int n_snap, const int *snap_steps,
+                       double *out) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
+    return solve_common(c, p, false, true, 0.0, V_0, out, 0, 1, nullptr, n_snap, snap_steps, nullptr, nullptr, &samples);
+}
+
+int hadi_compute_base_prices_samples(hadi_ctx *ctx, const hadi_problem *p, double V_0, const hadi_samples *samples, int n_snap,
+                                     const int *snap_steps, double *out) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
+    return solve_common(c, p, true, true, 0.0, V_0, out, 0, 1, nullptr, n_snap, snap_steps, nullptr, nullptr, &samples);
+}
+
+int hadi_compute_jacobian_samples(hadi_ctx *ctx, const hadi_problem *p, double V_0, double eps, const hadi_samples *samples, int n_snap,
+                                  const int *snap_steps, double *J, double *base) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
+    return jacobian_common(c, p, 0.0, V_0, eps, J, base, n_snap, snap_steps, nullptr, nullptr, &samples);
 }
 
 HADI_VARIANT_WRAPPERS(american, HADI_AM)

@@ -41,6 +41,12 @@ struct HadiSmallArgs {
     int ko_stride = 0;
     const int *ko_iab = nullptr;
     const double *ko_rebate = nullptr;
+    // Sampled ladder (hadi_sample_ladder; n_samp 0 = none): on the snapshot steps above, instead of the one node, sample s of the
+    // instance -- the tap record taps[inst * n_samp + s] that hadi_sample_locate_kernel wrote -- goes to
+    // samp_out[(inst * n_snap + q) * n_samp + s]
+    const HadiTap *taps = nullptr;
+    int n_samp = 0;
+    double *samp_out = nullptr;
 };
 
 // The ladder's running cursor of a whole-loop kernel: wave-uniform (kernel arguments and the step counter only).  `next` is the
@@ -60,6 +66,19 @@ HADI_HD inline int hadi_snap_natural(const HadiLayout &L, int node, int PL) {
     if (node < 0) return -1;
     const int j = node / L.rowp, i = hadi_slot_to_i(L, node - j * L.rowp);
     return i < 0 ? -1 : j * PL + i;
+}
+// Sampled ladder: snapshot q of instance `inst` from its LDS field Ul -- packed as the global state is, or (natural) in natural
+// order with pitch PL.  Lanes first, first + stride, .. take the samples; the tap records are read from the global table here, on
+// snapshot steps only, as the Bermudan payoff is.  `on`: this lane serves the instance (the halves of the pairs kernel).
+HADI_DEV inline void hadi_sample_lds(const HadiSmallArgs &sm, const HadiLayout &L, const double *Ul, bool natural, int PL, int inst,
+                                     int q, int first, int stride, bool on) {
+    if (!on) return;
+    const HadiTap *__restrict__ tp = sm.taps + (size_t)inst * sm.n_samp;
+    double *__restrict__ out = sm.samp_out + ((size_t)inst * sm.n_snap + q) * sm.n_samp;
+    for (int s = first; s < sm.n_samp; s += stride) {
+        const HadiTap t = tp[s];
+        out[s] = hadi_tap_value(t, [&](int off) { return Ul[natural ? hadi_snap_natural(L, off, PL) : off]; });
+    }
 }
 
 template <int B, int W, bool AMER>
@@ -235,7 +254,10 @@ __global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, Had
         }
         // maturity ladder: nothing writes U before the next barrier (the row pass reads it, a dividend copies it to Y first)
         if (n == snap.next) {
-            if (tid == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
+            if (sm.n_samp > 0) {  // sampled ladder: W wavefronts read arbitrary nodes of U, which nothing writes before the next barrier either
+                hadi_sample_lds(sm, a.L, Ul, false, rowp, inst, snap.q, tid, NT, true);
+                __syncthreads();
+            } else if (tid == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
             hadi_snap_advance(sm, snap);
         }
     }
@@ -381,7 +403,10 @@ __global__ void __launch_bounds__(64) hadi_small_seq_kernel(HadiSweepArgs a, Had
         }
         // maturity ladder: lane 0 reads the node before it stores anything of the next step (one wavefront: nobody else has yet)
         if (n == snap.next) {
-            if (lane == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
+            if (sm.n_samp > 0) {  // sampled ladder: every lane reads before the row sweep of the next step parks c' in U
+                hadi_sample_lds(sm, a.L, Ul, true, PL, inst, snap.q, lane, 64, true);
+                __syncthreads();
+            } else if (lane == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
             hadi_snap_advance(sm, snap);
         }
     }
@@ -516,7 +541,10 @@ __global__ void __launch_bounds__(64) hadi_small_seq2_kernel(HadiSweepArgs a, Ha
         }
         // maturity ladder: one lane per instance reads its node before it stores anything of the next step
         if (n == snap.next) {
-            if (jl == 0 && (half == 0 || has1) && n <= Nl)
+            if (sm.n_samp > 0) {  // sampled ladder: the 32 lanes of a half take the samples of its instance
+                hadi_sample_lds(sm, a.L, Ul, true, PL, inst, snap.q, jl, 32, (half == 0 || has1) && n <= Nl);
+                __syncthreads();
+            } else if (jl == 0 && (half == 0 || has1) && n <= Nl)
                 sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
             hadi_snap_advance(sm, snap);
         }

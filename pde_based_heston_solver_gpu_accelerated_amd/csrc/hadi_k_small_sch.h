@@ -289,7 +289,10 @@ __global__ void __launch_bounds__(64) hadi_small_sch_kernel(HadiSweepArgs a, Had
         }
         // maturity ladder: lane 0 reads the node before it stores anything of the next step (one wavefront: nobody else has yet)
         if (n == snap.next) {
-            if (lane == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
+            if (sm.n_samp > 0) {  // sampled ladder: every lane reads before the row sweep of the next step parks c' in U
+                hadi_sample_lds(sm, a.L, Ul, true, PL, inst, snap.q, lane, 64, true);
+                __syncthreads();
+            } else if (lane == 0) sm.snap_out[(size_t)inst * sm.n_snap + snap.q] = snap_off >= 0 ? Ul[snap_off] : nan("");
             hadi_snap_advance(sm, snap);
         }
     }

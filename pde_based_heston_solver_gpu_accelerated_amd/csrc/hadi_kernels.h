@@ -35,6 +35,7 @@
 #include "hadi_k_team.h"
 #include "hadi_k_resident.h"
 #include "hadi_k_lds_seq.h"
+#include "hadi_k_sample.h"
 #include "hadi_k_small.h"
 #include "hadi_k_small_sch.h"
 #include "hadi_k_seq.h"

@@ -90,6 +90,8 @@ struct HadiRouteIn {
     int debug = 0;                            // diagnostics (hadi_debug_*): one pass of one step
     bool profiling = false;
     int n_snap = 0;                           // maturity ladder: snapshots asked for
+    int n_samp = 0;                           // sampled ladder: samples per instance and snapshot (0: the ladder's one node); a
+                                              // sample call is a ladder call -- the route does not depend on this, only its words do
     bool dividends = false;                   // num_dividends > 0
     bool uniform_steps = true;
     bool team_failed = false;                 // a team could not form or a team barrier timed out once on this handle
@@ -340,12 +342,15 @@ static inline std::string hadi_describe_route(const HadiRoute &r, const HadiRout
     const HadiLayout &L = r.pl.L;
     char buf[384];
     // what a ladder call adds
-    const std::string ladder_loop = r.ladder ? "; maturity ladder: " + std::to_string(in.n_snap) + " snapshots copied inside the time loop" : "";
+    const std::string samp_words = "; sampled ladder: " + std::to_string(in.n_snap) + " snapshots x " + std::to_string(in.n_samp) + " samples";
+    const std::string ladder_loop = !r.ladder ? "" : in.n_samp > 0 ? samp_words + " evaluated inside the time loop" :
+                                    "; maturity ladder: " + std::to_string(in.n_snap) + " snapshots copied inside the time loop";
     const std::string ex_loop = r.bermudan ? "; Bermudan: exercise at the end of " + std::to_string(in.n_ex_steps) + " steps inside the time loop" : "";
     const std::string ex_stream = r.bermudan ? "; Bermudan: hadi_exercise_kernel after each of " + std::to_string(in.n_ex_steps) + " exercise steps" : "";
     const std::string ko_loop = r.barrier ? "; barrier: knock-out at the end of " + std::to_string(in.n_mon_steps) + " steps inside the time loop" : "";
     const std::string ko_stream = r.barrier ? "; barrier: hadi_knockout_kernel after each of " + std::to_string(in.n_mon_steps) + " monitoring steps" : "";
-    const std::string ladder_stream = r.ladder ? "; maturity ladder: " + std::to_string(in.n_snap) + " snapshots, hadi_snap_kernel after each snapshot step" : "";
+    const std::string ladder_stream = !r.ladder ? "" : in.n_samp > 0 ? samp_words + ", hadi_sample_kernel after each snapshot step" :
+                                      "; maturity ladder: " + std::to_string(in.n_snap) + " snapshots, hadi_snap_kernel after each snapshot step";
     if (r.kind == HADI_ROUTE_SMALL_SCH) {
         const int sch = hadi_route_sch(in.scheme);
         snprintf(buf, sizeof buf, "hadi_small_sch_kernel<%d,%s>: whole time loop in one launch, one wavefront per instance, predictor and corrector lines solved sequentially in LDS (%zu B)",

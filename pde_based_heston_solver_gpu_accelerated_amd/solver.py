@@ -406,6 +406,91 @@ class HestonADI:
             self._raise(rc)
         return J.reshape(num_strikes, steps.size, 5), base.reshape(-1, steps.size)
 
+    # ---- sampled ladder (hadi_sample_ladder and its launchers; no reference counterpart) ---------------------
+    @staticmethod
+    def _samples(n, spots, scales):
+        """(struct hadi_samples, the arrays it points to, n_samp) of spots given as one list for the batch or one row per
+        instance; scales None = 1, else the shape of spots."""
+        sp = np.ascontiguousarray(np.asarray(spots, dtype=np.float64))
+        if sp.ndim == 1:
+            sp = sp.reshape(1, -1)
+        if sp.ndim != 2 or sp.shape[1] < 1 or sp.shape[0] not in (1, n):
+            raise ValueError("spots must be [n_samp] or [n][n_samp] with n_samp >= 1")
+        sc = None
+        if scales is not None:
+            sc = np.ascontiguousarray(np.asarray(scales, dtype=np.float64))
+            if sc.ndim == 1:
+                sc = sc.reshape(1, -1)
+            if sc.shape != sp.shape:
+                raise ValueError("scales must have the shape of spots")
+        st = nat.Samples(int(sp.shape[1]), sp.ctypes.data_as(nat._dp), sc.ctypes.data_as(nat._dp) if sc is not None else None,
+                         int(sp.shape[0]))
+        return st, (sp, sc), int(sp.shape[1])
+
+    def sample_ladder(self, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U, spots, V_0, snap_steps,
+                      scales=None, variant=EU, U_0=None, dividends=None, per_instance=None, scheme=0, option_type=CALL,
+                      strikes=None):
+        """maturity_ladder with the state of the v-row of V_0 evaluated at arbitrary spots where the ladder copies the node of S_0:
+        returns [n][len(snap_steps)][n_samp], entry (k, q, s) = scales[s] * U_k(spots[s], V_0) after step snap_steps[q].  spots /
+        scales: one list for the batch or one row per instance (host arrays).  A spot within 1e-10 of an s-node returns the node's
+        value bit for bit; otherwise a 4-point Lagrange interpolant on the instance's own s-grid, clamped at both ends (hadi.h
+        states the arithmetic).  A spot off the s-grid raises HadiError (status 4).  Admitted and refused as maturity_ladder is."""
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U=U, U_0=U_0,
+                          dividends=dividends, per_instance=per_instance, scheme=scheme, option_type=option_type,
+                          strikes=strikes)
+        n = grids.Vec_s.shape[0]
+        steps = self._snap(snap_steps)
+        st, keep, n_samp = self._samples(n, spots, scales)
+        out, optr = self._out(n, steps.size * n_samp, U)
+        rc = self._lib.hadi_sample_ladder(self._h, C.byref(p), float(V_0), C.byref(st), int(steps.size), steps.ctypes.data_as(_ip),
+                                          optr)
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return out.reshape(n, steps.size, n_samp)
+
+    def compute_base_prices_samples(self, spots, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                    num_strikes, deviceGrids, workspace, snap_steps, scales=None, variant=EU, U_0=None,
+                                    dividends=None, per_instance=None, scheme=0):
+        """compute_base_prices_ladder (the v-grid rebuilt for V_0 or per_instance['V_0_i']) with sample_ladder's output:
+        [n][len(snap_steps)][n_samp].  workspace.U is the initial condition and is not modified."""
+        option_type, strikes = self._option(per_instance)
+        if total_size != (m1 + 1) * (m2 + 1):
+            raise ValueError("total_size != (m1+1)*(m2+1)")
+        if deviceGrids.Vec_s.shape[0] != num_strikes:
+            raise ValueError("num_strikes does not match the grid batch")
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=workspace.U,
+                          U_0=U_0, dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
+                          option_type=option_type, strikes=strikes)
+        steps = self._snap(snap_steps)
+        st, keep, n_samp = self._samples(num_strikes, spots, scales)
+        out, optr = self._out(num_strikes, steps.size * n_samp, workspace.U)
+        rc = self._lib.hadi_compute_base_prices_samples(self._h, C.byref(p), float(V_0), C.byref(st), int(steps.size),
+                                                        steps.ctypes.data_as(_ip), optr)
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return out.reshape(num_strikes, steps.size, n_samp)
+
+    def compute_jacobian_samples(self, spots, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                 num_strikes, deviceGrids, U_0, snap_steps, scales=None, eps=1e-6, variant=EU, dividends=None,
+                                 per_instance=None, scheme=0):
+        """compute_jacobian_ladder with sample_ladder's outputs: (J [n][len(snap_steps)][n_samp][5], base [n][len(snap_steps)][n_samp])
+        from ONE sweep of the 6n solves; the v0 column samples the row of V_0 + eps of its own rebuilt v-grid."""
+        if total_size != (m1 + 1) * (m2 + 1):
+            raise ValueError("total_size != (m1+1)*(m2+1)")
+        option_type, strikes = self._option(per_instance)
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=None, U_0=U_0,
+                          dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
+                          option_type=option_type, strikes=strikes)
+        steps = self._snap(snap_steps)
+        st, keep, n_samp = self._samples(num_strikes, spots, scales)
+        J, jptr = self._out(num_strikes * steps.size * n_samp, 5, U_0)
+        base, bptr = self._out(num_strikes, steps.size * n_samp, U_0)
+        rc = self._lib.hadi_compute_jacobian_samples(self._h, C.byref(p), float(V_0), float(eps), C.byref(st), int(steps.size),
+                                                     steps.ctypes.data_as(_ip), jptr, bptr)
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+        return J.reshape(num_strikes, steps.size, n_samp, 5), base.reshape(num_strikes, steps.size, n_samp)
+
     # ---- Bermudan options (hadi_bermudan_timestepping and its launchers; no reference counterpart) --------------
     @staticmethod
     def _schedule(exercise_steps):
@@ -680,6 +765,24 @@ class HestonADI:
         return self._base_prices(AM_DIV, S_0, V_0, None, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N,
                                  theta, dt, total_calibration_size, deviceGrids, workspace, U_0=U_0,
                                  dividends=dividends, per_instance=per)
+
+
+def strike_samples(S_0, base_strike, strikes):
+    """(spots, scales) that price the strikes K' at spot S_0 from ONE sweep on grids built at `base_strike` K:
+    spots = S_0 K / K', scales = K' / K, so that scale * U_K(spot) = price of strike K' at S_0.
+
+    The Heston operators and both boundary classes are homogeneous of degree one in (s, K): solving on the grid scaled by
+    a = K'/K (s-nodes a s_i, payoff of strike K') gives a U_K, node by node, to round-off (measured on the oracle: at most 6e-15,
+    1.4e-14 and 5.4e-14 of max|U| on 50x25x20, 100x50x40 and 200x100x40).  So the price of strike K' at S_0 is a U_K(S_0 / a); S_0 / a
+    is in general no node, which is what sample_ladder's interpolants are for.  Limits: it holds for calls and puts (the put's
+    strike in per_instance must be base_strike) and for proportional dividends; a cash dividend AMOUNT breaks it (the jump
+    s -> s - D is not homogeneous).  The grids and the payoff must be built at base_strike, and the claim is stated for European
+    exercise.  The surface is the one of the scaled grids, not of the grids GridViewsBatch.for_strikes builds per strike: the two
+    differ by less than either grid's own discretisation error."""
+    K = np.asarray(strikes, dtype=np.float64).reshape(-1)
+    if not (base_strike > 0) or np.any(~(K > 0)):
+        raise ValueError("strikes must be positive")
+    return float(S_0) * float(base_strike) / K, K / float(base_strike)
 
 
 def exercise_steps(T, delta_t, dates):
