@@ -1,7 +1,8 @@
 // emu_samples.cpp -- TEST-ONLY.  The wave emulator's driver of the sampled ladder of the four whole-loop kernels: emu_ladder.cpp
 // (included whole, so the plain ladder is in the same library) plus one entry point that builds the tables, packs the initial
 // field, locates the samples as the library does (hadi_setup_kernel, hadi_pack_kernel, hadi_sample_locate_kernel), runs the
-// kernel's whole time loop with the snapshot list and the tap table, and returns the samples.  Never shipped.
+// kernel's whole time loop with the snapshot list and the tap table, and returns the samples.  emu_sample_field (below) runs the
+// streaming path's sample kernels on given fields, without a sweep.  Never shipped.
 #include "emu_ladder.cpp"
 
 // The arguments of emu_ladder with the samples in S_0's place: spots / scales [rows][n_samp] (scales may be NULL = 1), rows 1 or
@@ -79,4 +80,59 @@ extern "C" int emu_samples(int n_inst, int m1, int m2, double theta, double r_d,
     for (double x : snap_out)
         if (x != 0.0) return 5;
     return g_err ? 4 : 0;
+}
+
+// The streaming path's three sample kernels on ANY layout, without a sweep: the plan, hadi_pack_kernel on given fields,
+// hadi_sample_locate_kernel over the whole batch, then hadi_sample_kernel once per sub-batch and snapshot with the offsets
+// run_sweep (hadi_api.hip) gives a sub-batch of nsb instances starting at instance o: the state at o * inst_stride, the tap
+// records at o * n_samp, the samples at o * n_snap * n_samp.  fields [n_snap][n][m] in natural order: the state "after" snapshot
+// step q.  V0_i [n] or NULL (then V_0).  sub [n_sub]: the sub-batch sizes, summing to n_inst.  spots / scales [rows][n_samp], rows
+// 1 or n_inst (scales may be NULL).  out [n][n_snap][n_samp], flags [n][n_samp].  Returns 0, 1 (no plan), 3 (bad arguments).
+extern "C" int emu_sample_field(int m1, int m2, int n_inst, const double *vec_s, const double *vec_v, double V_0, const double *V0_i,
+                                const double *fields, const double *spots, const double *scales, int rows, int n_samp, int n_snap,
+                                const int *sub, int n_sub, double *out, int *flags) {
+    HadiPlan pl;
+    if (hadi_make_plan(m1, m2, n_inst, 8 * 256, &pl, g_tune, 8)) return 1;
+    const HadiLayout &L = pl.L;
+    if (n_samp < 1 || n_snap < 1 || (rows != 1 && rows != n_inst) || n_sub < 1) return 3;
+    int sum = 0;
+    for (int b = 0; b < n_sub; b++) {
+        if (sub[b] < 1) return 3;
+        sum += sub[b];
+    }
+    if (sum != n_inst) return 3;
+    const size_t ns = (size_t)n_inst * n_samp, m = (size_t)(m1 + 1) * (m2 + 1);
+    std::vector<double> in(2 * ns);
+    for (int k = 0; k < n_inst; k++)
+        for (int q = 0; q < n_samp; q++) {
+            const size_t src = (size_t)(rows > 1 ? k : 0) * n_samp + q;
+            in[(size_t)k * n_samp + q] = spots[src];
+            in[ns + (size_t)k * n_samp + q] = scales ? scales[src] : 1.0;
+        }
+    std::vector<HadiTap> taps(ns);
+    emu::launch((int)((ns + 255) / 256), 256, [&]() {
+        hadi_sample_locate_kernel(L, n_inst, n_samp, vec_s, vec_v, V0_i, V_0, in.data(), in.data() + ns, taps.data(), flags);
+    });
+    std::vector<double> dU((size_t)L.inst_stride * n_inst);
+    for (int q = 0; q < n_snap; q++) {
+        emu::launch(8, 256, [&]() { hadi_pack_kernel(L, n_inst, n_inst, fields + (size_t)q * n_inst * m, dU.data()); });
+        int o = 0;
+        for (int b = 0; b < n_sub; o += sub[b], b++) {
+            const int nsb = sub[b];
+            const size_t nsq = (size_t)nsb * n_samp;
+            const double *Ub = dU.data() + (size_t)o * L.inst_stride;
+            emu::launch((int)((nsq + 255) / 256), 256, [&]() {
+                hadi_sample_kernel(L, nsb, Ub, taps.data() + (size_t)o * n_samp, out + (size_t)o * n_snap * n_samp, n_snap, n_samp, q);
+            });
+        }
+    }
+    return 0;
+}
+
+// Layout words of the plan of a shape, for the tests' own assertions: B, G, rowp, nrows_pad.
+extern "C" int emu_sample_layout(int m1, int m2, int n_inst, int *o4) {
+    HadiPlan pl;
+    if (hadi_make_plan(m1, m2, n_inst, 8 * 256, &pl, g_tune, 8)) return 1;
+    o4[0] = pl.L.B; o4[1] = pl.L.G; o4[2] = pl.L.rowp; o4[3] = pl.L.nrows_pad;
+    return 0;
 }

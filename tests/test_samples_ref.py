@@ -11,6 +11,7 @@ import pytest
 from oracle import oracle as O
 
 import common as Cm
+import sample_cases as SC
 import samples_ref as R
 import pde_based_heston_solver_gpu_accelerated_amd.solver as Sv
 
@@ -50,6 +51,55 @@ def test_node_hit_is_the_node_and_off_grid_is_nan():
     s2 = s.copy()
     s2[6] = s2[5]
     assert R.sample_field(U, s2, vv, 0.5, [0.5 * (s2[6] + s2[7])])[2][0] == R.DEGENERATE
+
+
+@pytest.mark.parametrize("name,grid,cases", SC.LOCATE_EDGES, ids=[e[0].split(":")[0].replace(" ", "_") for e in SC.LOCATE_EDGES])
+def test_the_reference_on_the_locate_edges(name, grid, cases):
+    """The reference is not its own judge: sample_cases.LOCATE_EDGES states, by hand from include/hadi.h, what every spot is (the
+    node hit, the stencil's first node, off grid, degenerate); the weights of an interior spot are pinned by what they must do --
+    sum to 1 and reproduce the cubic through the four nodes' own values."""
+    s = np.array(grid)
+    for x, want in cases:
+        idx, w, flag = R.taps(s, x)
+        if want[0] == "hit":
+            assert flag == 0 and list(idx) == [want[1]] * 4 and list(w) == [1.0, 0.0, 0.0, 0.0], (name, x)
+        elif want[0] == "interior":
+            assert flag == 0 and list(idx) == list(range(want[1], want[1] + 4)), (name, x, idx)
+            assert np.isfinite(w).all() and abs(w.sum() - 1.0) <= 8 * np.finfo(float).eps * np.abs(w).sum(), (name, x, w)
+            for p in (1, 2, 3):  # (monomials about the spot: sum_a w_a (s_a - x)^p = 0 for every polynomial degree <= 3)
+                t = w * (s[idx] - x) ** p
+                assert abs(t.sum()) <= 16 * np.finfo(float).eps * np.abs(t).sum(), (name, x, p)
+        else:
+            assert flag == (R.OFF_GRID if want[0] == "off" else R.DEGENERATE) and (idx == -1).all(), (name, x, flag)
+    # through sample_field: a flagged entry is NaN and leaves the flags and values of the call's other entries alone
+    m1 = s.size - 1
+    U = np.arange(3 * (m1 + 1), dtype=np.float64) + 1.0
+    val, _, flags = R.sample_field(U, s, np.array([0.0, 0.04, 0.1]), 0.04, [x for x, _ in cases])
+    for q, (x, want) in enumerate(cases):
+        assert flags[q] == {"hit": 0, "interior": 0, "off": R.OFF_GRID, "deg": R.DEGENERATE}[want[0]]
+        assert np.isnan(val[q]) == (want[0] in ("off", "deg"))
+        if want[0] == "hit":
+            assert val[q] == U[m1 + 1 + want[1]]
+
+
+def test_domain_spots_name_their_entries_by_the_definition():
+    """sample_cases.domain_spots on a real grid: the tolerance block against the inequalities of include/hadi.h, written out."""
+    vs = SC.oracle_batch(50, 25, 1)[1][0]
+    spots, scales, kinds = SC.domain_spots(vs, Cm.S_0)
+    m1 = 50
+    assert spots.size <= 4 * m1 + 16 and kinds[0] == SC.S0 and spots[0] == Cm.S_0 and 0.0 < vs[0] < 1e-13
+    tol = spots[kinds >= SC.TOL_HIT]
+    t = int(np.argmin(np.abs(vs - tol[0])))
+    assert 1.0 <= vs[t] <= 200.0 and list(tol) == [vs[t] - 5e-11, vs[t] + 5e-11, vs[t] - 2e-10, vs[t] + 2e-10, 0.0, -5e-11, vs[m1] + 5e-11]
+    assert [abs(x - vs[t]) < 1e-10 for x in tol[:4]] == [True, True, False, False]
+    assert tol[4] < vs[0] and tol[5] < vs[0] and tol[6] > vs[m1] and abs(tol[5] - vs[0]) < 1e-10 and abs(tol[6] - vs[m1]) < 1e-10
+    assert list(R.taps(vs, tol[2])[0]) == list(range(t - 2, t + 2)) and list(R.taps(vs, tol[3])[0]) == list(range(t - 1, t + 3))
+    # one interior spot in every interval, and in the six intervals at the clamp the stencils the clamp gives
+    first = {int(np.searchsorted(vs, x)) - 1 for x in spots[kinds == SC.INTERIOR]}
+    assert first == set(range(m1))
+    for i, i0 in ((0, 0), (1, 0), (2, 1), (m1 - 3, m1 - 4), (m1 - 2, m1 - 3), (m1 - 1, m1 - 3)):
+        x = [x for x in spots[kinds == SC.INTERIOR] if vs[i] < x < vs[i + 1]][0]
+        assert R.taps(vs, x)[0][0] == i0
 
 
 def _solve(m1, m2, N, vs, vv, ds, dv, U0, put_strikes=None):
