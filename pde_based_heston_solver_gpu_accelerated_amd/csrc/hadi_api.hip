@@ -189,11 +189,8 @@ int stage_to_device(Ctx *c, void *dst, const void *src, size_t bytes) {
     return HADI_OK;
 }
 
-int grid1d(size_t n, int block = 256, int cap = 4096) {
-    size_t g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > (size_t)cap) g = cap;
-    return (int)g;
+int grid1d(size_t n) {  // blocks of 256 threads, at most 4096 of them (the kernels stride)
+    return (int)std::min<size_t>(std::max<size_t>((n + 255) / 256, 1), 4096);
 }
 
 // ---- host grid code (grid.cpp:16-61, grid_pod.hpp:25-87) ---------------------------------------
@@ -213,6 +210,14 @@ void build_v(int m2, double V_0, double V, double d, double *vec_v, double *delt
 }
 
 // ---- one batched sweep ----------------------------------------------------------------------------
+// A step schedule as the entry points receive it (exercise steps of a Bermudan call, monitoring steps of a barrier call): steps
+// [rows][n_ex], host array, validated (check_bermudan: rows strictly increasing within 1 .. N_k, zero-padded).  rows 1 = one
+// schedule for the batch, else one row per source instance (instance k reads row k % n_src: a Jacobian's groups share).
+struct ExSched {
+    int n_ex = 0, rows = 0;
+    const int *steps = nullptr;
+};
+
 struct SweepDesc {
     int n = 0;               // instances actually solved (6x the caller's for a Jacobian)
     int m1 = 0, m2 = 0, variant = 0, scheme = 0, prec = 0;
@@ -240,23 +245,12 @@ struct SweepDesc {
     // null = 1); samp_rows 1 = one list for the batch, else one row per source instance (instance k reads row k % n_src)
     int n_samp = 0, samp_rows = 0;
     const double *spots = nullptr, *scales = nullptr;
-    // Bermudan (hadi_bermudan_timestepping and its launchers): n_ex > 0 = ex_steps [ex_rows][n_ex] (host array, validated: rows
-    // strictly increasing within 1 .. N_k, zero-padded) lists the steps at whose end an instance takes U <- max(U, payoff); ex_rows
-    // 1 = one schedule for the batch, else one row per source instance (instance k reads row k % n_src: a Jacobian's groups share)
-    int n_ex = 0, ex_rows = 0;
-    const int *ex_steps = nullptr;
-    // Knock-out barrier (hadi_barrier_timestepping and its launchers): n_mon > 0 = mon_steps [mon_rows][n_mon], the rules of ex_steps,
-    // lists the steps at whose end an instance is monitored; ko_lower / ko_upper / ko_rebate: host [n_src] or null (validated; null =
-    // -inf / +inf / 0).  Instance k reads entry k % n_src of all four.
-    int n_mon = 0, mon_rows = 0;
-    const int *mon_steps = nullptr;
+    // Bermudan (hadi_bermudan_timestepping and its launchers): ex.n_ex > 0 = the steps at whose end an instance takes
+    // U <- max(U, payoff).  Knock-out barrier (hadi_barrier_timestepping and its launchers): mon.n_ex > 0 = the steps at whose end an
+    // instance is monitored; ko_lower / ko_upper / ko_rebate: host [n_src] or null (validated; null = -inf / +inf / 0), instance k
+    // reads entry k % n_src as it reads its schedule's row.
+    ExSched ex, mon;
     const double *ko_lower = nullptr, *ko_upper = nullptr, *ko_rebate = nullptr;
-};
-
-// A Bermudan schedule as the entry points receive it.
-struct ExSched {
-    int n_ex, rows;
-    const int *steps;
 };
 
 // Kernels whose dynamic LDS can exceed the 64 KiB default need the limit raised once (hadi_create: every kernel of
@@ -267,19 +261,23 @@ hipError_t raise_lds_limit(K kernel) {
 }
 
 // ---- run_sweep: plan and route (csrc/hadi_route.h), grow buffers, stage inputs, then one whole-loop launch or the time loop ----
+// What the host keeps of a per-step, per-instance flag table on the device (dividends, exercise, monitoring).
+struct StepTable {
+    std::vector<char> any;  // step -> some instance's flag is set: the time loop launches the table's kernel at that step
+    int stride = 0;         // the device table holds one shared row (0) or a row of Nmax flags per instance
+    size_t bytes(const SweepDesc &d) const { return sizeof(int) * (size_t)(stride ? d.n : 1) * d.Nmax; }
+};
+
 // Everything the steps below share.  The route is a pure function of `in`; `amp` is the one thing the device decides.
 struct Sweep {
     const SweepDesc &d;
     HadiRouteIn in;
     HadiRoute r;
     size_t tot = 0, st = 0;      // the packed state of the whole batch: elements, and bytes as fp64
-    std::vector<char> div_step;  // step -> somebody pays a dividend at its start
+    StepTable div;               // somebody pays a dividend at the step's start
+    StepTable ex;                // somebody may be exercised at the step's end (Bermudan)
+    StepTable mon;               // somebody is monitored at the step's end (knock-out barrier)
     std::vector<int> snap_q;     // step -> snapshot index of a ladder call, or -1
-    std::vector<char> ex_step;   // step -> somebody may be exercised at its end (Bermudan)
-    int ex_stride = 0;           // exercise table: one shared row (0) or a row of Nmax flags per instance
-    std::vector<char> mon_step;  // step -> somebody is monitored at its end (knock-out barrier)
-    int mon_stride = 0;          // monitoring table: one shared row (0) or a row of Nmax flags per instance
-    int flag_stride = 0;         // dividend table: one shared row (0) or a row of Nmax flags per instance
     bool amp = false;            // American sweeps in the P representation (hadi_row_step, AMER == 2)
     HadiSweepArgs a, av;         // whole-batch arguments; Craig-Sneyd: the predictor's column pass writes V (= Y2), the
                                  // corrector's row pass reads V (av.U)
@@ -295,24 +293,14 @@ HadiRouteIn route_in(const Ctx *c, const SweepDesc &d) {
     return in;
 }
 
-// Bermudan: the steps of the time loop behind which hadi_exercise_kernel is launched, and their number for the route.
-void mark_exercise_steps(Sweep &w) {
-    const SweepDesc &d = w.d;
-    w.ex_step.assign(d.Nmax + 1, 0);
-    w.ex_stride = d.ex_rows > 1 ? d.Nmax : 0;
-    for (size_t e = 0; e < (size_t)d.ex_rows * d.n_ex; e++)
-        if (d.ex_steps[e] > 0) w.ex_step[d.ex_steps[e]] = 1;
-    w.in.n_ex_steps = (int)std::count(w.ex_step.begin(), w.ex_step.end(), (char)1);
-}
-
-// Barrier: the steps of the time loop behind which hadi_knockout_kernel is launched, and their number for the route.
-void mark_monitoring_steps(Sweep &w) {
-    const SweepDesc &d = w.d;
-    w.mon_step.assign(d.Nmax + 1, 0);
-    w.mon_stride = d.mon_rows > 1 ? d.Nmax : 0;
-    for (size_t e = 0; e < (size_t)d.mon_rows * d.n_mon; e++)
-        if (d.mon_steps[e] > 0) w.mon_step[d.mon_steps[e]] = 1;
-    w.in.n_mon_steps = (int)std::count(w.mon_step.begin(), w.mon_step.end(), (char)1);
+// The steps of the time loop behind which a schedule's kernel is launched (hadi_exercise_kernel, hadi_knockout_kernel); returns
+// their number, for the route.
+int mark_steps(const SweepDesc &d, const ExSched &s, StepTable &t) {
+    t.any.assign(d.Nmax + 1, 0);
+    t.stride = s.rows > 1 ? d.Nmax : 0;
+    for (size_t e = 0; e < (size_t)s.rows * s.n_ex; e++)
+        if (s.steps[e] > 0) t.any[s.steps[e]] = 1;
+    return (int)std::count(t.any.begin(), t.any.end(), (char)1);
 }
 
 // The choice, the launch geometry and the words are hadi_dispatch.h's (the rules: DESIGN.md section 4.1); this launches it.
@@ -331,8 +319,8 @@ int grow_buffers(Ctx *c, Sweep &w) {
     if ((rc = ensure(c, c->U, st)) || (rc = ensure(c, c->Y, st))) return rc;
     if (r.need_lam_u0 && ((rc = ensure(c, c->LAM, st)) || (rc = ensure(c, c->U0, st)))) return rc;
     if (r.need_u0 && (rc = ensure(c, c->U0, st))) return rc;
-    if (r.bermudan && (rc = ensure(c, c->ex_flag, sizeof(int) * (size_t)(w.ex_stride ? d.n : 1) * d.Nmax))) return rc;
-    if (r.barrier && ((rc = ensure(c, c->ko_flag, sizeof(int) * (size_t)(w.mon_stride ? d.n : 1) * d.Nmax)) || (rc = ensure(c, c->ko_bounds, 16 * n)) ||
+    if (r.bermudan && (rc = ensure(c, c->ex_flag, w.ex.bytes(d)))) return rc;
+    if (r.barrier && ((rc = ensure(c, c->ko_flag, w.mon.bytes(d))) || (rc = ensure(c, c->ko_bounds, 16 * n)) ||
                       (rc = ensure(c, c->ko_iab, 2 * sizeof(int) * n)) || (rc = ensure(c, c->ko_rebate, 8 * n))))
         return rc;
     if (r.need_ut && (rc = ensure(c, c->UT, st))) return rc;
@@ -365,8 +353,8 @@ int grow_buffers(Ctx *c, Sweep &w) {
 // row when the batch has a single (N, delta_t)), plus the set of steps where anybody pays.
 int stage_dividends(Ctx *c, Sweep &w) {
     const SweepDesc &d = w.d;
-    w.div_step.assign(d.Nmax + 1, 0);
-    w.flag_stride = d.uniform_steps ? 0 : d.Nmax;
+    w.div.any.assign(d.Nmax + 1, 0);
+    w.div.stride = d.uniform_steps ? 0 : d.Nmax;
     if (!w.r.have_div) return HADI_OK;
     const int rows = d.uniform_steps ? 1 : d.n;
     std::vector<int> div_flags((size_t)rows * d.Nmax);
@@ -376,7 +364,7 @@ int stage_dividends(Ctx *c, Sweep &w) {
         int *f = div_flags.data() + (size_t)k * d.Nmax;
         hadi_dividend_steps(N, dt, d.num_div, d.div_dates, f, d.Nmax);
         for (int q = 0; q < d.Nmax; q++)
-            if (f[q] >= 0) w.div_step[q + 1] = 1;
+            if (f[q] >= 0) w.div.any[q + 1] = 1;
     }
     int rc;
     if ((rc = ensure(c, c->div_flag, div_flags.size() * sizeof(int))) || (rc = ensure(c, c->div_amt, d.num_div * 8)) ||
@@ -389,30 +377,23 @@ int stage_dividends(Ctx *c, Sweep &w) {
     return HADI_OK;
 }
 
-// Bermudan: host-built table "may instance k be exercised at the end of step n" (one shared row for one shared schedule).
-int stage_exercise(Ctx *c, const Sweep &w) {
-    const SweepDesc &d = w.d;
-    const int rows = w.ex_stride ? d.n : 1;
+// A schedule's table on the device: host-built "does the schedule of instance k list step n" (one shared row for one shared
+// schedule) -- may the instance be exercised at the end of the step (Bermudan), is it monitored there (barrier).
+int stage_step_flags(Ctx *c, const SweepDesc &d, const ExSched &s, const StepTable &t, DevBuf &table) {
+    const int rows = t.stride ? d.n : 1;
     std::vector<int> flags((size_t)rows * d.Nmax, 0);
     for (int k = 0; k < rows; k++) {
-        const int *row = d.ex_steps + (size_t)(w.ex_stride ? k % d.n_src : 0) * d.n_ex;
-        for (int q = 0; q < d.n_ex; q++)
+        const int *row = s.steps + (size_t)(t.stride ? k % d.n_src : 0) * s.n_ex;
+        for (int q = 0; q < s.n_ex; q++)
             if (row[q] > 0) flags[(size_t)k * d.Nmax + row[q] - 1] = 1;
     }
-    return stage_to_device(c, c->ex_flag.p, flags.data(), flags.size() * sizeof(int));
+    return stage_to_device(c, table.p, flags.data(), flags.size() * sizeof(int));
 }
 
-// Barrier: the monitoring table (built as the exercise table), the bounds and the rebates of all n instances, then the live index
-// ranges from the device s-grids (hadi_barrier_locate_kernel).
+// Barrier: behind the monitoring table, the bounds and the rebates of all n instances, then the live index ranges from the device
+// s-grids (hadi_barrier_locate_kernel).
 int stage_barrier(Ctx *c, const Sweep &w) {
     const SweepDesc &d = w.d;
-    const int rows = w.mon_stride ? d.n : 1;
-    std::vector<int> flags((size_t)rows * d.Nmax, 0);
-    for (int k = 0; k < rows; k++) {
-        const int *row = d.mon_steps + (size_t)(w.mon_stride ? k % d.n_src : 0) * d.n_mon;
-        for (int q = 0; q < d.n_mon; q++)
-            if (row[q] > 0) flags[(size_t)k * d.Nmax + row[q] - 1] = 1;
-    }
     std::vector<double> bounds((size_t)2 * d.n), rebate(d.n);
     for (int k = 0; k < d.n; k++) {
         const int src = k % d.n_src;
@@ -421,7 +402,7 @@ int stage_barrier(Ctx *c, const Sweep &w) {
         rebate[k] = d.ko_rebate ? d.ko_rebate[src] : 0.0;
     }
     int rc;
-    if ((rc = stage_to_device(c, c->ko_flag.p, flags.data(), flags.size() * sizeof(int))) ||
+    if ((rc = stage_step_flags(c, d, d.mon, w.mon, c->ko_flag)) ||
         (rc = stage_to_device(c, c->ko_bounds.p, bounds.data(), bounds.size() * 8)) ||
         (rc = stage_to_device(c, c->ko_rebate.p, rebate.data(), rebate.size() * 8)))
         return rc;
@@ -493,7 +474,7 @@ int stage_inputs(Ctx *c, Sweep &w) {
     if (r.bermudan) {  // the payoff, packed as the state is, and the exercise table
         hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src,
                            d.d_natU0 ? d.d_natU0 : d.d_natU, ptr<double>(c->U0));
-        if ((rc = stage_exercise(c, w))) return rc;
+        if ((rc = stage_step_flags(c, d, d.ex, w.ex, c->ex_flag))) return rc;
     }
     if (r.barrier && (rc = stage_barrier(c, w))) return rc;
     if (r.american) {
@@ -566,15 +547,15 @@ int small_args(Ctx *c, const Sweep &w, HadiSmallArgs &sm) {
         if ((rc = stage_to_device(c, c->order.p, order.data(), sizeof(int) * d.n))) return rc;
         sm.order = ptr<int>(c->order);
     }
-    sm.flag_stride = w.flag_stride;
+    sm.flag_stride = w.div.stride;
     if (w.r.have_div) {
         sm.div_flag = ptr<int>(c->div_flag); sm.div_amounts = ptr<double>(c->div_amt); sm.div_pcts = ptr<double>(c->div_pct);
     }
     if (w.r.bermudan) {
-        sm.ex_flag = ptr<int>(c->ex_flag); sm.ex_stride = w.ex_stride;
+        sm.ex_flag = ptr<int>(c->ex_flag); sm.ex_stride = w.ex.stride;
     }
     if (w.r.barrier) {
-        sm.ko_flag = ptr<int>(c->ko_flag); sm.ko_stride = w.mon_stride;
+        sm.ko_flag = ptr<int>(c->ko_flag); sm.ko_stride = w.mon.stride;
         sm.ko_iab = ptr<int>(c->ko_iab); sm.ko_rebate = ptr<double>(c->ko_rebate);
     }
     if (w.r.ladder) {
@@ -626,7 +607,7 @@ int run_team(Ctx *c, Sweep &w, bool *fell_back) {
     HIP_TRY(c, hipMemsetAsync(c->team.p, 0, 512 * sizeof(int), s));
     HadiTeamArgs ta;
     ta.form = ptr<int>(c->team); ta.bar = ptr<int>(c->team) + 64; ta.nb = c->cu_count / 8; ta.N = d.Nmax;
-    ta.div_flag = have_div ? ptr<int>(c->div_flag) : nullptr; ta.flag_stride = w.flag_stride;
+    ta.div_flag = have_div ? ptr<int>(c->div_flag) : nullptr; ta.flag_stride = w.div.stride;
     ta.div_amounts = have_div ? ptr<double>(c->div_amt) : nullptr; ta.div_pcts = have_div ? ptr<double>(c->div_pct) : nullptr;
     ta.vec_s = d.d_vec_s;
     ta.stamps = reinterpret_cast<unsigned long long *>(ptr<int>(c->team) + 384);
@@ -704,17 +685,17 @@ int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
     for (int nstep = n_first; nstep <= n_last; nstep++) {
         // P representation: the first step (the caller's initial U need not dominate the payoff) and dividend steps
         // (the jump acts on U alone) run on the explicit (U, lambda_bar) pair, converted on the way in and out
-        const bool xstep = amp && (nstep == 1 || (have_div && w.div_step[nstep]));
+        const bool xstep = amp && (nstep == 1 || (have_div && w.div.any[nstep]));
         if (xstep && nstep > 1)
             hipLaunchKernelGGL(hadi_am_materialise_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, nsb, a.ipar, U0b, Ub, LAMb, sp.pos_m1);
-        if (have_div && w.div_step[nstep]) {  // device_solver.hpp:426-517: U_temp <- U, U <- interpolated jump
+        if (have_div && w.div.any[nstep]) {  // device_solver.hpp:426-517: U_temp <- U, U <- interpolated jump
             if (f32)  // fp32 state: the jump works on the fp64 packed array -- widen, jump, round again (<= num_dividends steps)
                 hipLaunchKernelGGL(hadi_widen_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, reinterpret_cast<const float *>(a.U), Ub, tot);
             HIP_TRY(c, hipMemcpyAsync(UTb, Ub, st, hipMemcpyDeviceToDevice, q));
             const size_t npts = (size_t)nsb * L.nrows * (L.m1 + 1);
             hipLaunchKernelGGL(hadi_dividend_kernel, dim3(grid1d(npts)), dim3(256), 0, q, L, nsb, a.ipar,
-                               d.d_vec_s + (size_t)o * (L.m1 + 1), UTb, Ub, ptr<int>(c->div_flag) + (size_t)o * w.flag_stride,
-                               w.flag_stride, nstep, ptr<double>(c->div_amt), ptr<double>(c->div_pct));
+                               d.d_vec_s + (size_t)o * (L.m1 + 1), UTb, Ub, ptr<int>(c->div_flag) + (size_t)o * w.div.stride,
+                               w.div.stride, nstep, ptr<double>(c->div_amt), ptr<double>(c->div_pct));
             if (f32)
                 hipLaunchKernelGGL(hadi_narrow_kernel, dim3(grid1d(tot)), dim3(256), 0, q, L, Ub, reinterpret_cast<float *>(a.U), tot);
         }
@@ -738,15 +719,15 @@ int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
         if (cs) {  // corrector (profiling events cover the predictor's two passes only)
             if ((rc = launch_pass(c, hadi_select_row_pass(pc, 2), q, av, nstep)) || (rc = launch_pass(c, col, q, a, nstep))) return rc;
         }
-        if (r.bermudan && w.ex_step[nstep]) {  // Bermudan exercise behind the step's last column pass (European sweeps: U is explicit)
+        if (r.bermudan && w.ex.any[nstep]) {  // Bermudan exercise behind the step's last column pass (European sweeps: U is explicit)
             const int bpi = hadi_exercise_bpi(L);
             hipLaunchKernelGGL(hadi_exercise_kernel, dim3((unsigned)nsb * bpi), dim3(HADI_EX_THREADS), 0, q, L, nsb, bpi, Ub, U0b,
-                               ptr<int>(c->ex_flag) + (size_t)o * w.ex_stride, w.ex_stride, nstep);
+                               ptr<int>(c->ex_flag) + (size_t)o * w.ex.stride, w.ex.stride, nstep);
         }
-        if (r.barrier && w.mon_step[nstep]) {  // knock-out behind the step's last column pass (European sweeps, fp64 state: U is explicit)
+        if (r.barrier && w.mon.any[nstep]) {  // knock-out behind the step's last column pass (European sweeps, fp64 state: U is explicit)
             const int bpi = hadi_exercise_bpi(L);
             hipLaunchKernelGGL(hadi_knockout_kernel, dim3((unsigned)nsb * bpi), dim3(HADI_EX_THREADS), 0, q, L, nsb, bpi, Ub,
-                               ptr<int>(c->ko_flag) + (size_t)o * w.mon_stride, w.mon_stride, ptr<int>(c->ko_iab) + 2 * (size_t)o,
+                               ptr<int>(c->ko_flag) + (size_t)o * w.mon.stride, w.mon.stride, ptr<int>(c->ko_iab) + 2 * (size_t)o,
                                ptr<double>(c->ko_rebate) + o, nstep);
         }
         if (r.ladder && w.snap_q[nstep] >= 0 && d.n_samp > 0) {  // a sample call: n_samp interpolants where the ladder copies one node
@@ -836,25 +817,21 @@ std::string graph_key(const Ctx *c, const Sweep &w) {
         put(&d.n_samp, sizeof(int));
         if (d.n_samp > 0) put(smp, sizeof(smp));
     }
-    if (w.r.bermudan) {  // the per-instance table is re-uploaded every call; the node list only depends on which steps carry an
-                         // exercise launch, on the table's address and on its stride (the payoff's address is in both argument blocks)
-        const void *ex[] = {c->ex_flag.p};
-        put(ex, sizeof(ex));
-        put(&w.ex_stride, sizeof(int));
-        put(w.ex_step.data(), w.ex_step.size());
-    }
-    if (w.r.barrier) {  // the tables are re-uploaded and the index ranges located again every call; the node list only depends on
-                        // which steps carry a knock-out launch, on the tables' addresses and on the stride
-        const void *ko[] = {c->ko_flag.p, c->ko_iab.p, c->ko_rebate.p};
+    // A step table (dividends, exercise, monitoring) is re-uploaded every call; the node list only depends on the table's address,
+    // on its stride and on which steps carry the table's launch -- the three items this puts.  (The dividend table's address is
+    // among `own` above as well: it stands in the key twice.)
+    auto put_table = [&](const DevBuf &table, const StepTable &t) {
+        put(&table.p, sizeof(void *));
+        put(&t.stride, sizeof(int));
+        put(t.any.data(), t.any.size());
+    };
+    if (w.r.bermudan) put_table(c->ex_flag, w.ex);  // (the payoff's address is in both argument blocks)
+    if (w.r.barrier) {  // the index ranges are located again every call; the knock-out launches name them and the rebates
+        const void *ko[] = {c->ko_iab.p, c->ko_rebate.p};
         put(ko, sizeof(ko));
-        put(&w.mon_stride, sizeof(int));
-        put(w.mon_step.data(), w.mon_step.size());
+        put_table(c->ko_flag, w.mon);
     }
-    if (w.r.have_div) {  // amounts / percentages / per-instance tables are re-uploaded every call; the node list
-                         // only depends on which steps carry a dividend launch
-        put(&w.flag_stride, sizeof(int));
-        put(w.div_step.data(), w.div_step.size());
-    }
+    if (w.r.have_div) put_table(c->div_flag, w.div);  // (amounts / percentages: `own` above)
     return key;
 }
 
@@ -914,8 +891,8 @@ int run_streaming(Ctx *c, Sweep &w, bool team_fell_back) {
 
 int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     Sweep w{d, route_in(c, d)};
-    mark_exercise_steps(w);
-    mark_monitoring_steps(w);
+    w.in.n_ex_steps = mark_steps(d, d.ex, w.ex);
+    w.in.n_mon_steps = mark_steps(d, d.mon, w.mon);
     w.r = hadi_route(w.in);
     if (w.r.status == HADI_ROUTE_BAD_GRID)
         return fail(c, HADI_ERR_UNSUPPORTED, "grid %dx%d not supported (need m1 >= 2, m2 >= 3 and (m1 + 16)(m2 + 1) < 2^28)", d.m1, d.m2);
@@ -1074,11 +1051,11 @@ int check_samples(Ctx *c, const hadi_problem *p, const hadi_samples *sp) {
     return HADI_OK;
 }
 // After the sweep of a sample call: the samples' flag words decide the status (they came back with the stream synchronisation).
-int samples_status(Ctx *c, const std::vector<int> &flags, int n_samp) {
-    for (size_t e = 0; e < flags.size(); e++)
+int samples_status(Ctx *c, const int *flags, size_t count, int n_samp) {
+    for (size_t e = 0; e < count; e++)
         if (flags[e] & HADI_SAMPLE_DEGENERATE)
             return fail(c, HADI_ERR_INVALID, "sample %zu of instance %zu: degenerate stencil (an s-interval of length zero, or m1 < 3)", e % n_samp, e / n_samp);
-    for (size_t e = 0; e < flags.size(); e++)
+    for (size_t e = 0; e < count; e++)
         if (flags[e]) return fail(c, HADI_ERR_NOT_ON_GRID, "sample %zu of instance %zu is off the s-grid", e % n_samp, e / n_samp);
     return HADI_OK;
 }
@@ -1128,9 +1105,60 @@ int check_barrier(Ctx *c, const hadi_problem *p, const hadi_barrier *b) {
     return rc;
 }
 
-// Fills the per-instance parameter rows for `groups` copies of the caller's batch.
-void fill_par(const hadi_problem *p, SweepDesc &d, int groups) {
+// What a call may carry beyond the problem, as its entry point received it.  Every entry point fills the fields of its feature
+// by name and leaves the others as they are here.  A new per-call feature goes here, into check_extras and into apply_extras.
+struct CallExtras {
+    bool ladder = false;  // a ladder or sample entry point: prices after each of snap_steps[0 .. n_snap)
+    int n_snap = 0; const int *snap_steps = nullptr;
+    bool sampled = false; const hadi_samples *samples = nullptr;  // a sample entry point (NULL is not "absent": check_samples refuses it)
+    bool bermudan = false; ExSched ex;                            // a Bermudan entry point, with its exercise schedule
+    const hadi_barrier *barrier = nullptr;                        // a barrier entry point (each refuses NULL itself)
+    int debug = 0, debug_step = 1; double *debug_out = nullptr;   // diagnostics (hadi_debug_*): SweepDesc::debug, and where the pass's result goes
+};
+
+// Where a call's results go and what is picked.
+struct CallOut {
+    bool rebuild_v = false;  // the v-grids are rebuilt for V_0 (or V_0_i) instead of taken from the caller
+    bool pick = false;       // the prices of the node (S_0, V_0) go to `prices`
+    double S_0 = 0, V_0 = 0, eps = 0;
+    double *prices = nullptr;                      // solve_common: [n], or the ladder's [n][n_snap] / the samples' [n][n_snap][n_samp]
+    double *J = nullptr, *base_prices = nullptr;   // jacobian_common
+    double *greeks = nullptr, *ladder = nullptr;   // greeks_common
+};
+
+// The features' checks behind check_problem (which has passed), in this order.  ladder_out: where a ladder call's output goes.
+int check_extras(Ctx *c, const hadi_problem *p, const CallExtras &x, const void *ladder_out) {
+    int rc;
+    if (x.bermudan && (rc = check_bermudan(c, p, x.ex))) return rc;
+    if (x.barrier && (rc = check_barrier(c, p, x.barrier))) return rc;
+    if (x.ladder && (rc = check_ladder(c, p, x.n_snap, x.snap_steps, ladder_out))) return rc;
+    if (x.sampled && (rc = check_samples(c, p, x.samples))) return rc;
+    return HADI_OK;
+}
+
+// The (checked) extras into the sweep's description.  d_v0_i: the per-instance V_0 of a ladder's price nodes (device, or null).
+void apply_extras(SweepDesc &d, const CallExtras &x, const CallOut &o, const double *d_v0_i) {
+    d.debug = x.debug; d.debug_step = x.debug_step;
+    if (x.ladder) {
+        d.n_snap = x.n_snap; d.snap_steps = x.snap_steps; d.S_0 = o.S_0; d.V_0 = o.V_0; d.d_v0_i = d_v0_i;
+        if (x.sampled) { d.n_samp = x.samples->n_samp; d.samp_rows = x.samples->rows; d.spots = x.samples->spots; d.scales = x.samples->scales; }
+    }
+    if (x.bermudan && x.ex.n_ex > 0) d.ex = x.ex;
+    if (x.barrier && x.barrier->n_mon > 0) {
+        d.mon = ExSched{x.barrier->n_mon, x.barrier->mon_rows, x.barrier->mon_steps};
+        d.ko_lower = x.barrier->lower_i; d.ko_upper = x.barrier->upper_i; d.ko_rebate = x.barrier->rebate_i;
+    }
+}
+
+// The problem into the sweep's description, as `groups` copies of the caller's batch (a Jacobian: 6) with their parameter rows.
+void fill_desc(const hadi_problem *p, SweepDesc &d, int groups) {
     const int n0 = p->n_instances;
+    d.n = n0 * groups; d.n_src = n0;
+    d.m1 = p->m1; d.m2 = p->m2; d.variant = p->variant; d.scheme = p->scheme; d.prec = p->state_precision;
+    d.theta = p->theta; d.r_d = p->r_d; d.r_f = p->r_f;
+    const bool dividend = p->variant == HADI_DIV || p->variant == HADI_AM_DIV;
+    d.num_div = dividend ? p->num_dividends : 0;
+    d.div_dates = p->dividend_dates; d.div_amounts = p->dividend_amounts; d.div_pcts = p->dividend_percentages;
     d.par8.assign((size_t)n0 * groups * 8, 0.0);
     d.Nmax = 0;
     d.uniform_steps = !(p->N_i || p->delta_t_i);
@@ -1151,14 +1179,6 @@ void fill_par(const hadi_problem *p, SweepDesc &d, int groups) {
         }
 }
 
-void fill_common(const hadi_problem *p, SweepDesc &d) {
-    d.m1 = p->m1; d.m2 = p->m2; d.variant = p->variant; d.scheme = p->scheme; d.prec = p->state_precision;
-    d.theta = p->theta; d.r_d = p->r_d; d.r_f = p->r_f;
-    const bool dividend = p->variant == HADI_DIV || p->variant == HADI_AM_DIV;
-    d.num_div = dividend ? p->num_dividends : 0;
-    d.div_dates = p->dividend_dates; d.div_amounts = p->dividend_amounts; d.div_pcts = p->dividend_percentages;
-}
-
 // v-grids of all `n` instances rebuilt ON THE DEVICE, each for its own V_0 (v0i: host vector of n values): what every
 // team of the reference does in-kernel (rebuild_variance_views, grid_pod.hpp:25-73; call sites use V = 5, d = 5/500,
 // jacobian_computation.cpp:253).  Results in c->g_v / c->g_dv; c->v0_i keeps the per-instance V_0 for the price pick.
@@ -1174,22 +1194,88 @@ int rebuild_v_device(Ctx *c, int n, int m2, const std::vector<double> &v0i) {
     return HADI_OK;
 }
 
-// Shared driver of hadi_DO_timestepping / hadi_parallel_DO_solve / hadi_compute_base_prices* and the diagnostics
-// (debug != 0: p->U is input only, the pass's result goes to debug_out).
-// Ladder (n_snap > 0; hadi_maturity_ladder, hadi_compute_base_prices_ladder): prices_out is [n][n_snap], the snapshots the sweep
-// took on the way; p->U and p->lambda_bar are not written.
-int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, double S_0, double V_0, double *prices_out,
-                 int debug = 0, int debug_step = 1, double *debug_out = nullptr, int n_snap = 0, const int *snap_steps = nullptr,
-                 const ExSched *ex = nullptr, const hadi_barrier *ko = nullptr, const hadi_samples *const *smp = nullptr) {
-    int rc = check_problem(c, p, true, !rebuild_v);
+// v-grids built on the host (glibc sinh/asinh, bit-identical to the reference's host-side Grid) for the n_grids values v0[] and
+// broadcast to the n instances: instance k takes grid d_sel[k] (device selector; null: all take grid 0).  Results in c->g_v / c->g_dv.
+int rebuild_v_host(Ctx *c, int n, int m2, int n_grids, const double *v0, const int *d_sel) {
+    std::vector<double> hv((size_t)n_grids * (m2 + 1)), hdv((size_t)n_grids * m2);
+    for (int g = 0; g < n_grids; g++) build_v(m2, v0[g], 5.0, 5.0 / 500, hv.data() + (size_t)g * (m2 + 1), hdv.data() + (size_t)g * m2);
+    int rc;
+    if ((rc = ensure(c, c->src_v, hv.size() * 8)) || (rc = ensure(c, c->src_dv, hdv.size() * 8)) ||
+        (rc = ensure(c, c->g_v, (size_t)n * (m2 + 1) * 8)) || (rc = ensure(c, c->g_dv, (size_t)n * m2 * 8)))
+        return rc;
+    if ((rc = stage_to_device(c, c->src_v.p, hv.data(), hv.size() * 8)) || (rc = stage_to_device(c, c->src_dv.p, hdv.data(), hdv.size() * 8)))
+        return rc;
+    hipLaunchKernelGGL(hadi_bcast_rows_kernel, dim3(grid1d((size_t)n * (m2 + 1))), dim3(256), 0, c->stream, m2 + 1, n,
+                       ptr<double>(c->src_v), d_sel, ptr<double>(c->g_v));
+    hipLaunchKernelGGL(hadi_bcast_rows_kernel, dim3(grid1d((size_t)n * m2)), dim3(256), 0, c->stream, m2, n,
+                       ptr<double>(c->src_dv), d_sel, ptr<double>(c->g_dv));
+    return HADI_OK;
+}
+
+// The problem's own arrays to the device (host memory is staged into the library's buffers): the s-grids, the v-grids -- the
+// caller's or, with o.rebuild_v, rebuilt for V_0 / V_0_i --, then U and U_0.  *per_inst_v0: the v-grids were rebuilt on the
+// device, and c->v0_i holds every instance's V_0 for the price pick.
+int stage_problem(Ctx *c, const hadi_problem *p, const CallOut &o, SweepDesc &d, bool *per_inst_v0) {
+    const int n = p->n_instances, m1 = p->m1, m2 = p->m2;
+    const size_t m = (size_t)(m1 + 1) * (m2 + 1);
+    int rc;
+    if ((rc = to_device(c, p->memspace, p->vec_s, (size_t)n * (m1 + 1), c->g_s, &d.d_vec_s))) return rc;
+    if ((rc = to_device(c, p->memspace, p->delta_s, (size_t)n * m1, c->g_ds, &d.d_delta_s))) return rc;
+    *per_inst_v0 = o.rebuild_v && c->t.device_vgrid;
+    if (o.rebuild_v && !c->t.device_vgrid && p->V_0_i)
+        return fail(c, HADI_ERR_INVALID, "V_0_i needs the device v-grid rebuild (hadi_set_tuning \"device_vgrid\", 1)");
+    if (*per_inst_v0) {
+        std::vector<double> v0i(n);
+        for (int k = 0; k < n; k++) v0i[k] = p->V_0_i ? p->V_0_i[k] : o.V_0;
+        rc = rebuild_v_device(c, n, m2, v0i);
+    } else if (o.rebuild_v) {
+        rc = rebuild_v_host(c, n, m2, 1, &o.V_0, nullptr);
+    } else {
+        if ((rc = to_device(c, p->memspace, p->vec_v, (size_t)n * (m2 + 1), c->g_v, &d.d_vec_v))) return rc;
+        rc = to_device(c, p->memspace, p->delta_v, (size_t)n * m2, c->g_dv, &d.d_delta_v);
+    }
     if (rc) return rc;
-    if (ex && (rc = check_bermudan(c, p, *ex))) return rc;
-    if (ko && (rc = check_barrier(c, p, ko))) return rc;
-    const bool ladder = n_snap > 0 || snap_steps;
-    if (ladder && (rc = check_ladder(c, p, n_snap, snap_steps, prices_out))) return rc;
-    if (smp && (rc = check_samples(c, p, *smp))) return rc;
-    const int n_samp = smp ? (*smp)->n_samp : 0;  // (sampled ladder: prices_out is [n][n_snap][n_samp])
-    if (debug && !debug_out) return fail(c, HADI_ERR_INVALID, "output array missing");
+    if (o.rebuild_v) { d.d_vec_v = ptr<double>(c->g_v); d.d_delta_v = ptr<double>(c->g_dv); }
+    if ((rc = to_device(c, p->memspace, p->U, n * m, c->natU, &d.d_natU))) return rc;
+    return to_device(c, p->memspace, p->U_0, n * m, c->natU0, &d.d_natU0);
+}
+
+// What the status words that a call's last kernels leave on the device mean.
+enum StatusKind { STATUS_NONE, STATUS_NODE, STATUS_GREEKS, STATUS_SAMPLES };
+
+// The end of every call: the status words back (c->status, one per instance: hadi_locate_kernel, hadi_pick_kernel and
+// hadi_greeks_kernel; sample flags: one per instance and sample), finish_timing -- whose stream synchronisation completes the copy --
+// and then the first non-zero word of the leading n_count instances as the call's error (the groups of a Jacobian repeat the
+// caller's instances).  pinned: the words come back through the pinned arena, so that the copy does not block the host.
+int finish_call(Ctx *c, const SweepDesc &d, const CallOut &o, StatusKind kind, int n_count, bool pinned) {
+    const size_t per = kind == STATUS_SAMPLES ? d.n_samp : 1, words = kind == STATUS_NONE ? 0 : d.n * per;
+    std::vector<int> pageable;
+    int *hs = pinned ? static_cast<int *>(pin_alloc(c, words * sizeof(int))) : nullptr;
+    if (!hs) { pageable.resize(words); hs = pageable.data(); }
+    if (words)
+        HIP_TRY(c, hipMemcpyAsync(hs, kind == STATUS_SAMPLES ? samp_flags(c, d) : ptr<int>(c->status), words * sizeof(int),
+                                  hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipGetLastError());
+    const int rc = finish_timing(c, d);
+    if (rc || kind == STATUS_NONE) return rc;
+    if (kind == STATUS_SAMPLES) return samples_status(c, hs, n_count * per, d.n_samp);
+    for (int k = 0; k < n_count; k++) {
+        if (hs[k] && (hs[k] == 1 || kind == STATUS_NODE))
+            return fail(c, HADI_ERR_NOT_ON_GRID, "S_0 = %.17g is not a node of instance %d's s-grid", o.S_0, k);
+        if (hs[k]) return fail(c, HADI_ERR_NOT_ON_GRID, "V_0 = %.17g is not a node of instance %d's v-grid", o.V_0, k);
+    }
+    return HADI_OK;
+}
+
+// Shared driver of hadi_DO_timestepping / hadi_parallel_DO_solve / hadi_compute_base_prices* and the diagnostics
+// (x.debug != 0: p->U is input only, the pass's result goes to x.debug_out).
+// Ladder (x.ladder; hadi_maturity_ladder, hadi_compute_base_prices_ladder): o.prices is [n][n_snap], the snapshots the sweep
+// took on the way ([n][n_snap][n_samp] for a sample call); p->U and p->lambda_bar are not written.
+int solve_common(Ctx *c, const hadi_problem *p, const CallExtras &x, const CallOut &o) {
+    int rc = check_problem(c, p, true, !o.rebuild_v);
+    if (rc || (rc = check_extras(c, p, x, o.prices))) return rc;
+    const int debug = x.debug;
+    if (debug && !x.debug_out) return fail(c, HADI_ERR_INVALID, "output array missing");
     if (debug && (p->scheme != HADI_SCHEME_DOUGLAS || p->state_precision != HADI_STATE_FP64))
         return fail(c, HADI_ERR_UNSUPPORTED, "diagnostics cover fp64 Douglas steps");
     if (debug == 2 && p->variant != HADI_EU && p->variant != HADI_DIV)
@@ -1199,82 +1285,29 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
     const int n = p->n_instances, m1 = p->m1, m2 = p->m2;
     const size_t m = (size_t)(m1 + 1) * (m2 + 1);
     SweepDesc d;
-    fill_common(p, d);
-    d.n = n; d.n_src = n;
-    d.debug = debug; d.debug_step = debug_step;
-    fill_par(p, d, 1);
-    if (debug == 1 && (debug_step < 1 || debug_step > d.Nmax)) return fail(c, HADI_ERR_INVALID, "step %d outside 1..%d", debug_step, d.Nmax);
-    if ((rc = to_device(c, p->memspace, p->vec_s, (size_t)n * (m1 + 1), c->g_s, &d.d_vec_s))) return rc;
-    if ((rc = to_device(c, p->memspace, p->delta_s, (size_t)n * m1, c->g_ds, &d.d_delta_s))) return rc;
-    const bool per_inst_v0 = rebuild_v && c->t.device_vgrid;
-    if (rebuild_v && !c->t.device_vgrid && p->V_0_i)
-        return fail(c, HADI_ERR_INVALID, "V_0_i needs the device v-grid rebuild (hadi_set_tuning \"device_vgrid\", 1)");
-    if (per_inst_v0) {
-        std::vector<double> v0i(n);
-        for (int k = 0; k < n; k++) v0i[k] = p->V_0_i ? p->V_0_i[k] : V_0;
-        if ((rc = rebuild_v_device(c, n, m2, v0i))) return rc;
-        d.d_vec_v = ptr<double>(c->g_v);
-        d.d_delta_v = ptr<double>(c->g_dv);
-    } else if (rebuild_v) {
-        // host build (glibc sinh/asinh, bit-identical to the reference's host-side Grid), broadcast to every instance
-        std::vector<double> hv(m2 + 1), hdv(m2);
-        build_v(m2, V_0, 5.0, 5.0 / 500, hv.data(), hdv.data());
-        if ((rc = ensure(c, c->src_v, (m2 + 1) * 8)) || (rc = ensure(c, c->src_dv, m2 * 8))) return rc;
-        if ((rc = ensure(c, c->g_v, (size_t)n * (m2 + 1) * 8)) || (rc = ensure(c, c->g_dv, (size_t)n * m2 * 8))) return rc;
-        if ((rc = stage_to_device(c, c->src_v.p, hv.data(), (size_t)(m2 + 1) * 8)) || (rc = stage_to_device(c, c->src_dv.p, hdv.data(), (size_t)m2 * 8))) return rc;
-        hipLaunchKernelGGL(hadi_bcast_rows_kernel, dim3(grid1d((size_t)n * (m2 + 1))), dim3(256), 0, c->stream, m2 + 1, n,
-                           ptr<double>(c->src_v), (const int *)nullptr, ptr<double>(c->g_v));
-        hipLaunchKernelGGL(hadi_bcast_rows_kernel, dim3(grid1d((size_t)n * m2)), dim3(256), 0, c->stream, m2, n,
-                           ptr<double>(c->src_dv), (const int *)nullptr, ptr<double>(c->g_dv));
-        d.d_vec_v = ptr<double>(c->g_v);
-        d.d_delta_v = ptr<double>(c->g_dv);
-    } else {
-        if ((rc = to_device(c, p->memspace, p->vec_v, (size_t)n * (m2 + 1), c->g_v, &d.d_vec_v))) return rc;
-        if ((rc = to_device(c, p->memspace, p->delta_v, (size_t)n * m2, c->g_dv, &d.d_delta_v))) return rc;
-    }
-    if ((rc = to_device(c, p->memspace, p->U, n * m, c->natU, &d.d_natU))) return rc;
-    if ((rc = to_device(c, p->memspace, p->U_0, n * m, c->natU0, &d.d_natU0))) return rc;
+    fill_desc(p, d, 1);
+    if (debug == 1 && (x.debug_step < 1 || x.debug_step > d.Nmax))
+        return fail(c, HADI_ERR_INVALID, "step %d outside 1..%d", x.debug_step, d.Nmax);
+    bool per_inst_v0;
+    if ((rc = stage_problem(c, p, o, d, &per_inst_v0))) return rc;
     // the buffers the outputs pass through, grown before the sweep: growing one after it would drop the loop it just captured
     if (p->memspace != HADI_MEM_DEVICE && (rc = ensure(c, c->natOut, n * m * 8))) return rc;
-    if (pick && ((rc = ensure(c, c->prices, n * 8)) || (rc = ensure(c, c->status, n * sizeof(int))))) return rc;
-    if (ladder) {
-        d.n_snap = n_snap; d.snap_steps = snap_steps; d.S_0 = S_0; d.V_0 = V_0;
-        d.d_v0_i = per_inst_v0 ? ptr<double>(c->v0_i) : nullptr;
-        if (smp) { d.n_samp = n_samp; d.samp_rows = (*smp)->rows; d.spots = (*smp)->spots; d.scales = (*smp)->scales; }
-    }
-    if (ex && ex->n_ex > 0) { d.n_ex = ex->n_ex; d.ex_rows = ex->rows; d.ex_steps = ex->steps; }
-    if (ko && ko->n_mon > 0) {
-        d.n_mon = ko->n_mon; d.mon_rows = ko->mon_rows; d.mon_steps = ko->mon_steps;
-        d.ko_lower = ko->lower_i; d.ko_upper = ko->upper_i; d.ko_rebate = ko->rebate_i;
-    }
-
+    if (o.pick && ((rc = ensure(c, c->prices, n * 8)) || (rc = ensure(c, c->status, n * sizeof(int))))) return rc;
+    const double *const d_v0_i = per_inst_v0 ? ptr<double>(c->v0_i) : nullptr;
+    apply_extras(d, x, o, d_v0_i);
     HadiPlan pl;
     if ((rc = run_sweep(c, d, pl))) return rc;
 
-    if (ladder && n_samp > 0) {  // the samples and their flag words are all that leaves the device
-        if ((rc = from_device(c, p->memspace, prices_out, ptr<double>(c->samp_out), (size_t)n * n_snap * n_samp))) return rc;
-        std::vector<int> hf((size_t)n * n_samp);
-        HIP_TRY(c, hipMemcpyAsync(hf.data(), samp_flags(c, d), hf.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipGetLastError());
-        if ((rc = finish_timing(c, d))) return rc;
-        return samples_status(c, hf, n_samp);
-    }
-    if (ladder) {  // the snapshots and the locate step's status words are all that leaves the device
-        if ((rc = from_device(c, p->memspace, prices_out, ptr<double>(c->snap_out), (size_t)n * n_snap))) return rc;
-        std::vector<int> hs(n);
-        HIP_TRY(c, hipMemcpyAsync(hs.data(), c->status.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipGetLastError());
-        if ((rc = finish_timing(c, d))) return rc;
-        for (int k = 0; k < n; k++)
-            if (hs[k]) return fail(c, HADI_ERR_NOT_ON_GRID, "S_0 = %.17g is not a node of instance %d's s-grid", S_0, k);
-        return HADI_OK;
+    if (x.ladder) {  // the snapshots and the locate step's status words (or the samples and their flag words) are all that leaves
+        const DevBuf &src = d.n_samp > 0 ? c->samp_out : c->snap_out;
+        if ((rc = from_device(c, p->memspace, o.prices, static_cast<const double *>(src.p), (size_t)n * d.n_snap * std::max(d.n_samp, 1))))
+            return rc;
+        return finish_call(c, d, o, d.n_samp > 0 ? STATUS_SAMPLES : STATUS_NODE, n, false);
     }
 
     // solution back to the caller's U (natural layout); diagnostics: the pass's result to debug_out, U untouched
-    double *const host_dst = debug ? debug_out : p->U;
-    double *d_out;
-    if (p->memspace == HADI_MEM_DEVICE) d_out = host_dst;
-    else d_out = ptr<double>(c->natOut);
+    double *const host_dst = debug ? x.debug_out : p->U;
+    double *const d_out = p->memspace == HADI_MEM_DEVICE ? host_dst : ptr<double>(c->natOut);
     hipLaunchKernelGGL(hadi_unpack_kernel, dim3(grid1d(n * m)), dim3(256), 0, c->stream, pl.L, n,
                        debug == 1 ? ptr<double>(c->Y) : ptr<double>(c->U), d_out);
     if (p->memspace == HADI_MEM_HOST && (rc = from_device(c, p->memspace, host_dst, d_out, n * m))) return rc;
@@ -1289,51 +1322,36 @@ int solve_common(Ctx *c, const hadi_problem *p, bool rebuild_v, bool pick, doubl
         hipLaunchKernelGGL(hadi_unpack_kernel, dim3(grid1d(n * m)), dim3(256), 0, c->stream, pl.L, n, ptr<double>(c->LAM), d_l);
         if (p->memspace == HADI_MEM_HOST && (rc = from_device(c, p->memspace, p->lambda_bar, d_l, n * m))) return rc;
     }
-    std::vector<int> hstatus;
-    if (pick) {
+    if (o.pick) {
         hipLaunchKernelGGL(hadi_pick_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, pl.L, n, d.d_vec_s, d.d_vec_v,
-                           ptr<double>(c->U), S_0, per_inst_v0 ? ptr<double>(c->v0_i) : (const double *)nullptr, V_0,
-                           ptr<double>(c->prices), 1, ptr<int>(c->status));
-        if ((rc = from_device(c, p->memspace, prices_out, ptr<double>(c->prices), n))) return rc;
-        hstatus.resize(n);
-        HIP_TRY(c, hipMemcpyAsync(hstatus.data(), c->status.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+                           ptr<double>(c->U), o.S_0, d_v0_i, o.V_0, ptr<double>(c->prices), 1, ptr<int>(c->status));
+        if ((rc = from_device(c, p->memspace, o.prices, ptr<double>(c->prices), n))) return rc;
     }
-    HIP_TRY(c, hipGetLastError());
-    if ((rc = finish_timing(c, d))) return rc;
-    for (int k = 0; k < (int)hstatus.size(); k++)
-        if (hstatus[k]) return fail(c, HADI_ERR_NOT_ON_GRID, "S_0 = %.17g is not a node of instance %d's s-grid", S_0, k);
-    return HADI_OK;
+    return finish_call(c, d, o, o.pick ? STATUS_NODE : STATUS_NONE, n, false);
 }
 
 // hadi_compute_greeks: the sweep of hadi_DO_timestepping on the caller's grids, then hadi_greeks_kernel on the packed state the
 // sweep left in the handle (every execution path of run_sweep ends with an explicit U, American sweeps with an explicit
 // lambda_bar as well) and on its operator tables.  No field is unpacked or copied; p->U and p->lambda_bar are not written.
 static_assert(HADI_GK_N == HADI_N_GREEKS && HADI_GK_LAMBDA == HADI_GREEK_LAMBDA && HADI_GK_THETA == HADI_GREEK_THETA, "hadi.h / hadi_k_greeks.h columns");
-int greeks_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double *greeks, double *ladder) {
+int greeks_common(Ctx *c, const hadi_problem *p, const CallOut &o) {
     int rc = check_problem(c, p, true, true);
     if (rc) return rc;
-    if (!greeks) return fail(c, HADI_ERR_INVALID, "greeks missing");
+    if (!o.greeks) return fail(c, HADI_ERR_INVALID, "greeks missing");
     if (p->state_precision == HADI_STATE_FP32)
         return fail(c, HADI_ERR_UNSUPPORTED, "Greeks need the fp64 state: second-derivative stencils have weight sums near 1e2 on 512x256, "
                                              "which turn a state rounded to 24 bits into noise");
     DeviceGuard guard(c->device);
     pin_rewind(c);
-    const int n = p->n_instances, m1 = p->m1, m2 = p->m2;
-    const size_t m = (size_t)(m1 + 1) * (m2 + 1);
+    const int n = p->n_instances, m1 = p->m1;
     SweepDesc d;
-    fill_common(p, d);
-    d.n = n; d.n_src = n;
-    fill_par(p, d, 1);
-    if ((rc = to_device(c, p->memspace, p->vec_s, (size_t)n * (m1 + 1), c->g_s, &d.d_vec_s))) return rc;
-    if ((rc = to_device(c, p->memspace, p->delta_s, (size_t)n * m1, c->g_ds, &d.d_delta_s))) return rc;
-    if ((rc = to_device(c, p->memspace, p->vec_v, (size_t)n * (m2 + 1), c->g_v, &d.d_vec_v))) return rc;
-    if ((rc = to_device(c, p->memspace, p->delta_v, (size_t)n * m2, c->g_dv, &d.d_delta_v))) return rc;
-    if ((rc = to_device(c, p->memspace, p->U, n * m, c->natU, &d.d_natU))) return rc;
-    if ((rc = to_device(c, p->memspace, p->U_0, n * m, c->natU0, &d.d_natU0))) return rc;
+    fill_desc(p, d, 1);
+    bool per_inst_v0;
+    if ((rc = stage_problem(c, p, o, d, &per_inst_v0))) return rc;
     // the buffers the outputs pass through, grown before the sweep: growing one after it would drop the loop it just captured
     const size_t nlad = (size_t)n * (m1 + 1) * HADI_GK_N;
     if ((rc = ensure(c, c->prices, (size_t)n * HADI_GK_N * 8)) || (rc = ensure(c, c->status, n * sizeof(int)))) return rc;
-    if (ladder && (rc = ensure(c, c->natOut, nlad * 8))) return rc;
+    if (o.ladder && (rc = ensure(c, c->natOut, nlad * 8))) return rc;
 
     HadiPlan pl;
     if ((rc = run_sweep(c, d, pl))) return rc;
@@ -1348,31 +1366,24 @@ int greeks_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double 
     g.scoef = ptr<double>(c->scoef); g.b2row = ptr<double>(c->b2row); g.rowc = ptr<double>(c->rowc);
     g.ipar = ptr<HadiInstPar>(c->ipar);
     g.vec_s = d.d_vec_s; g.vec_v = d.d_vec_v; g.delta_s = d.d_delta_s; g.delta_v = d.d_delta_v;
-    g.S_0 = S_0; g.V_0 = V_0;
-    g.greeks = ptr<double>(c->prices); g.ladder = ladder ? ptr<double>(c->natOut) : nullptr; g.status = ptr<int>(c->status);
+    g.S_0 = o.S_0; g.V_0 = o.V_0;
+    g.greeks = ptr<double>(c->prices); g.ladder = o.ladder ? ptr<double>(c->natOut) : nullptr; g.status = ptr<int>(c->status);
     hipLaunchKernelGGL(hadi_greeks_kernel, dim3((unsigned)(n * g.ntiles)), dim3(HADI_GK_THREADS), hadi_greeks_smem(g.span), c->stream, g);
     HIP_TRY(c, hipGetLastError());
-    if ((rc = from_device(c, p->memspace, greeks, ptr<double>(c->prices), (size_t)n * HADI_GK_N))) return rc;
-    if (ladder && (rc = from_device(c, p->memspace, ladder, ptr<double>(c->natOut), nlad))) return rc;
-    std::vector<int> hstatus(n);
-    HIP_TRY(c, hipMemcpyAsync(hstatus.data(), c->status.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = finish_timing(c, d))) return rc;
-    for (int k = 0; k < n; k++) {
-        if (hstatus[k] == 1) return fail(c, HADI_ERR_NOT_ON_GRID, "S_0 = %.17g is not a node of instance %d's s-grid", S_0, k);
-        if (hstatus[k]) return fail(c, HADI_ERR_NOT_ON_GRID, "V_0 = %.17g is not a node of instance %d's v-grid", V_0, k);
-    }
-    return HADI_OK;
+    if ((rc = from_device(c, p->memspace, o.greeks, ptr<double>(c->prices), (size_t)n * HADI_GK_N))) return rc;
+    if (o.ladder && (rc = from_device(c, p->memspace, o.ladder, ptr<double>(c->natOut), nlad))) return rc;
+    return finish_call(c, d, o, STATUS_GREEKS, n, false);
 }
 
 // The grids of the 6 groups of a Jacobian's batch: the caller's s-rows replicated, the v-grids rebuilt for V_0 (groups 0..4) and
-// V_0 + eps (group 5); c->v0_i keeps the per-instance V_0 for the price pick.
-int jacobian_grids(Ctx *c, const hadi_problem *p, int G, double V_0, double eps, int n_snap, SweepDesc &d) {
+// V_0 + eps (group 5); c->v0_i keeps the per-instance V_0 for the price pick.  n_col: the output columns per instance.
+int jacobian_grids(Ctx *c, const hadi_problem *p, int G, const CallOut &o, int n_col, SweepDesc &d) {
     const int n0 = p->n_instances, m1 = p->m1, m2 = p->m2, n = n0 * G;
     int rc;
     const double *src_s, *src_ds;
     // (natOut stages delta_s here and takes J and the base prices after the sweep; prices / status: the pick.  All grown before
     // the sweep: growing one after it would drop the loop it just captured)
-    if ((rc = ensure(c, c->natOut, (size_t)n0 * std::max(m1, 6 * std::max(n_snap, 1)) * 8)) || (rc = ensure(c, c->prices, n * 8)) ||
+    if ((rc = ensure(c, c->natOut, (size_t)n0 * std::max(m1, 6 * std::max(n_col, 1)) * 8)) || (rc = ensure(c, c->prices, n * 8)) ||
         (rc = ensure(c, c->status, n * sizeof(int))))
         return rc;
     if ((rc = to_device(c, p->memspace, p->vec_s, (size_t)n0 * (m1 + 1), c->natU, &src_s))) return rc;
@@ -1383,36 +1394,30 @@ int jacobian_grids(Ctx *c, const hadi_problem *p, int G, double V_0, double eps,
         for (int k = 0; k < n0; k++) {
             sel_a[g * n0 + k] = k;
             sel_b[g * n0 + k] = (g == 5) ? 1 : 0;
-            const double v0k = p->V_0_i ? p->V_0_i[k] : V_0;
-            v0i[g * n0 + k] = (g == 5) ? v0k + eps : v0k;
+            const double v0k = p->V_0_i ? p->V_0_i[k] : o.V_0;
+            v0i[g * n0 + k] = (g == 5) ? v0k + o.eps : v0k;
         }
     if ((rc = ensure(c, c->sel_a, n * sizeof(int))) || (rc = ensure(c, c->sel_b, n * sizeof(int))) ||
         (rc = ensure(c, c->v0_i, n * 8)) || (rc = ensure(c, c->src_v, 2 * (m2 + 1) * 8)) ||
         (rc = ensure(c, c->src_dv, 2 * m2 * 8)) || (rc = ensure(c, c->g_s, (size_t)n * (m1 + 1) * 8)) ||
         (rc = ensure(c, c->g_ds, (size_t)n * m1 * 8)) || (rc = ensure(c, c->g_v, (size_t)n * (m2 + 1) * 8)) ||
         (rc = ensure(c, c->g_dv, (size_t)n * m2 * 8)))
-        return rc;
+        return rc;  // (all grown here, ahead of the first launch, in one order whichever way the v-grids are rebuilt)
     hipStream_t s = c->stream;
     if ((rc = stage_to_device(c, c->sel_a.p, sel_a.data(), n * sizeof(int)))) return rc;
     hipLaunchKernelGGL(hadi_bcast_rows_kernel, dim3(grid1d((size_t)n * (m1 + 1))), dim3(256), 0, s, m1 + 1, n, src_s,
                        ptr<int>(c->sel_a), ptr<double>(c->g_s));
     hipLaunchKernelGGL(hadi_bcast_rows_kernel, dim3(grid1d((size_t)n * m1)), dim3(256), 0, s, m1, n, src_ds,
                        ptr<int>(c->sel_a), ptr<double>(c->g_ds));
-    std::vector<double> hv(2 * (m2 + 1)), hdv(2 * m2);
     if (c->t.device_vgrid) {
         // every instance rebuilds its own v-grid on the device: V_0 for the groups 0..4, V_0 + eps for group 5
         // (jacobian_computation.cpp:253,339-341)
         if ((rc = rebuild_v_device(c, n, m2, v0i))) return rc;
     } else {
-        build_v(m2, V_0, 5.0, 5.0 / 500, hv.data(), hdv.data());
-        build_v(m2, V_0 + eps, 5.0, 5.0 / 500, hv.data() + m2 + 1, hdv.data() + m2);
+        const double v0[2] = {o.V_0, o.V_0 + o.eps};
         if ((rc = stage_to_device(c, c->sel_b.p, sel_b.data(), n * sizeof(int))) || (rc = stage_to_device(c, c->v0_i.p, v0i.data(), (size_t)n * 8)) ||
-            (rc = stage_to_device(c, c->src_v.p, hv.data(), (size_t)2 * (m2 + 1) * 8)) || (rc = stage_to_device(c, c->src_dv.p, hdv.data(), (size_t)2 * m2 * 8)))
+            (rc = rebuild_v_host(c, n, m2, 2, v0, ptr<int>(c->sel_b))))
             return rc;
-        hipLaunchKernelGGL(hadi_bcast_rows_kernel, dim3(grid1d((size_t)n * (m2 + 1))), dim3(256), 0, s, m2 + 1, n,
-                           ptr<double>(c->src_v), ptr<int>(c->sel_b), ptr<double>(c->g_v));
-        hipLaunchKernelGGL(hadi_bcast_rows_kernel, dim3(grid1d((size_t)n * m2)), dim3(256), 0, s, m2, n,
-                           ptr<double>(c->src_dv), ptr<int>(c->sel_b), ptr<double>(c->g_dv));
     }
     // (no synchronisation here: the host vectors above went through the pinned arena, and the device-side staging buffers natU /
     // natOut are only reused by later operations of the same stream)
@@ -1424,92 +1429,61 @@ int jacobian_grids(Ctx *c, const hadi_problem *p, int G, double V_0, double eps,
 // compute_jacobian*: the reference runs 6 solves one after the other inside each team
 // (jacobian_computation.cpp:232-363); here they are 6n independent instances of ONE batched sweep:
 // group 0 = base, 1..4 = kappa, eta, sigma, rho + eps, 5 = v-grid rebuilt for V_0 + eps.
-// Ladder (n_snap > 0; hadi_compute_jacobian_ladder): J [n][n_snap][5] and base_prices [n][n_snap] from the snapshots of the 6n solves.
-int jacobian_common(Ctx *c, const hadi_problem *p, double S_0, double V_0, double eps, double *J, double *base_prices,
-                    int n_snap = 0, const int *snap_steps = nullptr, const ExSched *ex = nullptr, const hadi_barrier *ko = nullptr,
-                    const hadi_samples *const *smp = nullptr) {
+// Ladder (x.ladder; hadi_compute_jacobian_ladder): J [n][n_snap][5] and base_prices [n][n_snap] from the snapshots of the 6n solves.
+int jacobian_common(Ctx *c, const hadi_problem *p, const CallExtras &x, const CallOut &o) {
     int rc = check_problem(c, p, false, false);
-    if (rc) return rc;
-    if (ex && (rc = check_bermudan(c, p, *ex))) return rc;
-    if (ko && (rc = check_barrier(c, p, ko))) return rc;
-    const bool ladder = n_snap > 0 || snap_steps;
-    if (ladder && (rc = check_ladder(c, p, n_snap, snap_steps, (J && base_prices) ? J : nullptr))) return rc;
-    if (smp && (rc = check_samples(c, p, *smp))) return rc;
-    const int n_samp = smp ? (*smp)->n_samp : 0;
-    const int n_col = n_snap * std::max(n_samp, 1);  // columns per instance: a sample call's [n_snap][n_samp] is the ladder's [n_snap]
+    if (rc || (rc = check_extras(c, p, x, (o.J && o.base_prices) ? o.J : nullptr))) return rc;
+    const int n_samp = x.sampled ? x.samples->n_samp : 0;
+    const int n_col = x.n_snap * std::max(n_samp, 1);  // columns per instance: a sample call's [n_snap][n_samp] is the ladder's [n_snap]
     DeviceGuard guard(c->device);
     pin_rewind(c);
     if (!p->U_0) return fail(c, HADI_ERR_INVALID, "U_0 (initial condition) is required for the Jacobian");
-    if (!J || !base_prices) return fail(c, HADI_ERR_INVALID, "J / base_prices missing");
+    if (!o.J || !o.base_prices) return fail(c, HADI_ERR_INVALID, "J / base_prices missing");
     const int n0 = p->n_instances, m1 = p->m1, m2 = p->m2, G = 6;
     if (!c->t.device_vgrid && p->V_0_i)
         return fail(c, HADI_ERR_INVALID, "V_0_i needs the device v-grid rebuild (hadi_set_tuning \"device_vgrid\", 1)");
     const int n = n0 * G;
     const size_t m = (size_t)(m1 + 1) * (m2 + 1);
+    const double eps = o.eps;
     SweepDesc d;
-    fill_common(p, d);
-    d.n = n; d.n_src = n0;
-    fill_par(p, d, G);
+    fill_desc(p, d, G);
     for (int k = 0; k < n0; k++) {
         d.par8[((size_t)1 * n0 + k) * 8 + 2] += eps;  // kappa
         d.par8[((size_t)2 * n0 + k) * 8 + 3] += eps;  // eta
         d.par8[((size_t)3 * n0 + k) * 8 + 1] += eps;  // sigma
         d.par8[((size_t)4 * n0 + k) * 8 + 0] += eps;  // rho
     }
-    if ((rc = jacobian_grids(c, p, G, V_0, eps, n_col, d))) return rc;
+    if ((rc = jacobian_grids(c, p, G, o, n_col, d))) return rc;
     hipStream_t s = c->stream;
     // every solve starts from U_0 (jacobian_computation.cpp:307-309); payoff for American = U_0 too
     if ((rc = to_device(c, p->memspace, p->U_0, n0 * m, c->natU0, &d.d_natU))) return rc;
     d.d_natU0 = d.d_natU;
-    if (ladder) {
-        d.n_snap = n_snap; d.snap_steps = snap_steps; d.S_0 = S_0; d.V_0 = V_0; d.d_v0_i = ptr<double>(c->v0_i);
-        if (smp) { d.n_samp = n_samp; d.samp_rows = (*smp)->rows; d.spots = (*smp)->spots; d.scales = (*smp)->scales; }
-    }
-    if (ex && ex->n_ex > 0) { d.n_ex = ex->n_ex; d.ex_rows = ex->rows; d.ex_steps = ex->steps; }
-    if (ko && ko->n_mon > 0) {
-        d.n_mon = ko->n_mon; d.mon_rows = ko->mon_rows; d.mon_steps = ko->mon_steps;
-        d.ko_lower = ko->lower_i; d.ko_upper = ko->upper_i; d.ko_rebate = ko->rebate_i;
-    }
+    apply_extras(d, x, o, ptr<double>(c->v0_i));
 
     HadiPlan pl;
     if ((rc = run_sweep(c, d, pl))) return rc;
-    if (!ladder)
+    if (!x.ladder)
         hipLaunchKernelGGL(hadi_pick_kernel, dim3((n + 63) / 64), dim3(64), 0, s, pl.L, n, d.d_vec_s, d.d_vec_v,
-                           ptr<double>(c->U), S_0, ptr<double>(c->v0_i), V_0, ptr<double>(c->prices), 1, ptr<int>(c->status));
+                           ptr<double>(c->U), o.S_0, ptr<double>(c->v0_i), o.V_0, ptr<double>(c->prices), 1, ptr<int>(c->status));
     // J(k, param) = (pert - base) / eps on the device (jacobian_computation.cpp:329,360): with HADI_MEM_DEVICE the rows
     // never leave HBM (hadi_lm_partials_device reduces them there); only the n status words come back
-    double *dJ = J, *db = base_prices;
+    double *dJ = o.J, *db = o.base_prices;
     if (p->memspace == HADI_MEM_HOST) {
         dJ = ptr<double>(c->natOut);
         db = dJ + (size_t)n0 * 5 * std::max(n_col, 1);
     }
     const size_t nrow = (size_t)n0 * std::max(n_col, 1);  // rows of J
-    if (ladder)  // (a sample call: the same kernel with n_snap * n_samp columns)
+    if (x.ladder)  // (a sample call: the same kernel with n_snap * n_samp columns)
         hipLaunchKernelGGL(hadi_jacobian_ladder_rows_kernel, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, s, n0, n_col,
                            n_samp > 0 ? ptr<double>(c->samp_out) : ptr<double>(c->snap_out), eps, dJ, db);
     else
         hipLaunchKernelGGL(hadi_jacobian_rows_kernel, dim3((n0 + 255) / 256), dim3(256), 0, s, n0, ptr<double>(c->prices), eps, dJ, db);
     if (p->memspace == HADI_MEM_HOST) {
-        HIP_TRY(c, hipMemcpyAsync(J, dJ, nrow * 5 * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(base_prices, db, nrow * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(o.J, dJ, nrow * 5 * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(o.base_prices, db, nrow * 8, hipMemcpyDeviceToHost, s));
     }
-    std::vector<int> hs_fallback;
-    int *hs = static_cast<int *>(pin_alloc(c, (size_t)n * sizeof(int)));  // (pinned: the copy does not block the host)
-    if (!hs) { hs_fallback.resize(n); hs = hs_fallback.data(); }
-    if (n_samp > 0) {  // the flag words of all six groups' samples (the v0 group located its own row; the s-grids are the same)
-        std::vector<int> hf((size_t)n * n_samp);
-        HIP_TRY(c, hipMemcpyAsync(hf.data(), samp_flags(c, d), hf.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipGetLastError());
-        if ((rc = finish_timing(c, d))) return rc;
-        hf.resize((size_t)n0 * n_samp);
-        return samples_status(c, hf, n_samp);
-    }
-    HIP_TRY(c, hipMemcpyAsync(hs, c->status.p, n * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipGetLastError());
-    if ((rc = finish_timing(c, d))) return rc;
-    for (int k = 0; k < n0; k++)
-        if (hs[k]) return fail(c, HADI_ERR_NOT_ON_GRID, "S_0 = %.17g is not a node of instance %d's s-grid", S_0, k);
-    return HADI_OK;
+    // (a sample call: the v0 group located its own row and the s-grids are the same, so the caller's n0 instances decide as well)
+    return finish_call(c, d, o, n_samp > 0 ? STATUS_SAMPLES : STATUS_NODE, n0, n_samp == 0);
 }
 
 int with_variant(hadi_ctx *ctx, const hadi_problem *p, int variant, hadi_problem *tmp) {
@@ -1744,31 +1718,36 @@ int hadi_find_v_index(int m2, const double *vec_v, double V_0) {
 
 // ---- hot path ------------------------------------------------------------------------------------------
 int hadi_DO_timestepping(hadi_ctx *ctx, const hadi_problem *p) {
-    return solve_common(reinterpret_cast<Ctx *>(ctx), p, false, false, 0.0, 0.0, nullptr);
+    return solve_common(reinterpret_cast<Ctx *>(ctx), p, CallExtras{}, CallOut{});
 }
 
 int hadi_parallel_DO_solve(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double *base_prices) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && !base_prices) return fail(c, HADI_ERR_INVALID, "base_prices missing");
-    return solve_common(c, p, false, true, S_0, V_0, base_prices);
+    CallOut o; o.pick = true; o.S_0 = S_0; o.V_0 = V_0; o.prices = base_prices;
+    return solve_common(c, p, CallExtras{}, o);
 }
 
 int hadi_compute_greeks(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double *greeks, double *ladder) {
-    return greeks_common(reinterpret_cast<Ctx *>(ctx), p, S_0, V_0, greeks, ladder);
+    CallOut o; o.S_0 = S_0; o.V_0 = V_0; o.greeks = greeks; o.ladder = ladder;
+    return greeks_common(reinterpret_cast<Ctx *>(ctx), p, o);
 }
 
 int hadi_compute_base_prices(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double *base_prices) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && !base_prices) return fail(c, HADI_ERR_INVALID, "base_prices missing");
-    return solve_common(c, p, true, true, S_0, V_0, base_prices);
+    CallOut o; o.rebuild_v = true; o.pick = true; o.S_0 = S_0; o.V_0 = V_0; o.prices = base_prices;
+    return solve_common(c, p, CallExtras{}, o);
 }
 
 int hadi_debug_row_pass(hadi_ctx *ctx, const hadi_problem *p, int step, double *Y1rhs) {
-    return solve_common(reinterpret_cast<Ctx *>(ctx), p, false, false, 0.0, 0.0, nullptr, 1, step, Y1rhs);
+    CallExtras x; x.debug = 1; x.debug_step = step; x.debug_out = Y1rhs;
+    return solve_common(reinterpret_cast<Ctx *>(ctx), p, x, CallOut{});
 }
 
 int hadi_debug_col_solve(hadi_ctx *ctx, const hadi_problem *p, double *X) {
-    return solve_common(reinterpret_cast<Ctx *>(ctx), p, false, false, 0.0, 0.0, nullptr, 2, 1, X);
+    CallExtras x; x.debug = 2; x.debug_out = X;
+    return solve_common(reinterpret_cast<Ctx *>(ctx), p, x, CallOut{});
 }
 
 int hadi_debug_rcp(hadi_ctx *ctx, int n, const double *x, double *out) {
@@ -1802,69 +1781,83 @@ int hadi_debug_rcp(hadi_ctx *ctx, int n, const double *x, double *out) {
 
 int hadi_compute_jacobian(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, double *J,
                           double *base_prices) {
-    return jacobian_common(reinterpret_cast<Ctx *>(ctx), p, S_0, V_0, eps, J, base_prices);
+    CallOut o; o.S_0 = S_0; o.V_0 = V_0; o.eps = eps; o.J = J; o.base_prices = base_prices;
+    return jacobian_common(reinterpret_cast<Ctx *>(ctx), p, CallExtras{}, o);
 }
 
 // ---- maturity ladder: the sweep's intermediate states at the price node --------------------------------
 int hadi_maturity_ladder(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, int n_snap, const int *snap_steps, double *prices) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
-    return solve_common(c, p, false, true, S_0, V_0, prices, 0, 1, nullptr, n_snap, snap_steps);
+    CallExtras x; x.ladder = true; x.n_snap = n_snap; x.snap_steps = snap_steps;
+    CallOut o; o.pick = true; o.S_0 = S_0; o.V_0 = V_0; o.prices = prices;
+    return solve_common(c, p, x, o);
 }
 
 int hadi_compute_base_prices_ladder(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, int n_snap, const int *snap_steps,
                                     double *prices) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
-    return solve_common(c, p, true, true, S_0, V_0, prices, 0, 1, nullptr, n_snap, snap_steps);
+    CallExtras x; x.ladder = true; x.n_snap = n_snap; x.snap_steps = snap_steps;
+    CallOut o; o.rebuild_v = true; o.pick = true; o.S_0 = S_0; o.V_0 = V_0; o.prices = prices;
+    return solve_common(c, p, x, o);
 }
 
 int hadi_compute_jacobian_ladder(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, int n_snap,
                                  const int *snap_steps, double *J, double *base_prices) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
-    return jacobian_common(c, p, S_0, V_0, eps, J, base_prices, n_snap, snap_steps);
+    CallExtras x; x.ladder = true; x.n_snap = n_snap; x.snap_steps = snap_steps;
+    CallOut o; o.S_0 = S_0; o.V_0 = V_0; o.eps = eps; o.J = J; o.base_prices = base_prices;
+    return jacobian_common(c, p, x, o);
 }
 
 // ---- Bermudan: the European sweep with U <- max(U, payoff) at the end of the listed steps --------------------
 int hadi_bermudan_timestepping(hadi_ctx *ctx, const hadi_problem *p, int n_ex, const int *ex_steps, int ex_rows) {
-    const ExSched ex{n_ex, ex_rows, ex_steps};
-    return solve_common(reinterpret_cast<Ctx *>(ctx), p, false, false, 0.0, 0.0, nullptr, 0, 1, nullptr, 0, nullptr, &ex);
+    CallExtras x; x.bermudan = true; x.ex.n_ex = n_ex; x.ex.rows = ex_rows; x.ex.steps = ex_steps;
+    return solve_common(reinterpret_cast<Ctx *>(ctx), p, x, CallOut{});
 }
 
 int hadi_compute_base_prices_bermudan(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, int n_ex, const int *ex_steps,
                                       int ex_rows, double *base_prices) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && !base_prices) return fail(c, HADI_ERR_INVALID, "base_prices missing");
-    const ExSched ex{n_ex, ex_rows, ex_steps};
-    return solve_common(c, p, true, true, S_0, V_0, base_prices, 0, 1, nullptr, 0, nullptr, &ex);
+    CallExtras x; x.bermudan = true; x.ex.n_ex = n_ex; x.ex.rows = ex_rows; x.ex.steps = ex_steps;
+    CallOut o; o.rebuild_v = true; o.pick = true; o.S_0 = S_0; o.V_0 = V_0; o.prices = base_prices;
+    return solve_common(c, p, x, o);
 }
 
 int hadi_compute_jacobian_bermudan(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, int n_ex,
                                    const int *ex_steps, int ex_rows, double *J, double *base_prices) {
-    const ExSched ex{n_ex, ex_rows, ex_steps};
-    return jacobian_common(reinterpret_cast<Ctx *>(ctx), p, S_0, V_0, eps, J, base_prices, 0, nullptr, &ex);
+    CallExtras x; x.bermudan = true; x.ex.n_ex = n_ex; x.ex.rows = ex_rows; x.ex.steps = ex_steps;
+    CallOut o; o.S_0 = S_0; o.V_0 = V_0; o.eps = eps; o.J = J; o.base_prices = base_prices;
+    return jacobian_common(reinterpret_cast<Ctx *>(ctx), p, x, o);
 }
 
 // ---- knock-out barrier: the European sweep with U <- rebate beyond the barriers at the end of the monitoring steps ----------
 int hadi_barrier_timestepping(hadi_ctx *ctx, const hadi_problem *p, const hadi_barrier *barrier) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && !barrier) return fail(c, HADI_ERR_INVALID, "barrier description missing");
-    return solve_common(c, p, false, false, 0.0, 0.0, nullptr, 0, 1, nullptr, 0, nullptr, nullptr, barrier);
+    CallExtras x; x.barrier = barrier;
+    return solve_common(c, p, x, CallOut{});
 }
 
 int hadi_compute_base_prices_barrier(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, const hadi_barrier *barrier,
                                      double *base_prices) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && (!barrier || !base_prices)) return fail(c, HADI_ERR_INVALID, "%s missing", barrier ? "base_prices" : "barrier description");
-    return solve_common(c, p, true, true, S_0, V_0, base_prices, 0, 1, nullptr, 0, nullptr, nullptr, barrier);
+    CallExtras x; x.barrier = barrier;
+    CallOut o; o.rebuild_v = true; o.pick = true; o.S_0 = S_0; o.V_0 = V_0; o.prices = base_prices;
+    return solve_common(c, p, x, o);
 }
 
 int hadi_compute_jacobian_barrier(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, const hadi_barrier *barrier,
                                   double *J, double *base_prices) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && !barrier) return fail(c, HADI_ERR_INVALID, "barrier description missing");
-    return jacobian_common(c, p, S_0, V_0, eps, J, base_prices, 0, nullptr, nullptr, barrier);
+    CallExtras x; x.barrier = barrier;
+    CallOut o; o.S_0 = S_0; o.V_0 = V_0; o.eps = eps; o.J = J; o.base_prices = base_prices;
+    return jacobian_common(c, p, x, o);
 }
 
 // ---- sampled ladder: the ladder's calls with n_samp interpolants of the row of V_0 in the single node's place --------------
@@ -1872,21 +1865,27 @@ int hadi_sample_ladder(hadi_ctx *ctx, const hadi_problem *p, double V_0, const h
                        double *out) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
-    return solve_common(c, p, false, true, 0.0, V_0, out, 0, 1, nullptr, n_snap, snap_steps, nullptr, nullptr, &samples);
+    CallExtras x; x.ladder = true; x.n_snap = n_snap; x.snap_steps = snap_steps; x.sampled = true; x.samples = samples;
+    CallOut o; o.pick = true; o.V_0 = V_0; o.prices = out;
+    return solve_common(c, p, x, o);
 }
 
 int hadi_compute_base_prices_samples(hadi_ctx *ctx, const hadi_problem *p, double V_0, const hadi_samples *samples, int n_snap,
                                      const int *snap_steps, double *out) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
-    return solve_common(c, p, true, true, 0.0, V_0, out, 0, 1, nullptr, n_snap, snap_steps, nullptr, nullptr, &samples);
+    CallExtras x; x.ladder = true; x.n_snap = n_snap; x.snap_steps = snap_steps; x.sampled = true; x.samples = samples;
+    CallOut o; o.rebuild_v = true; o.pick = true; o.V_0 = V_0; o.prices = out;
+    return solve_common(c, p, x, o);
 }
 
 int hadi_compute_jacobian_samples(hadi_ctx *ctx, const hadi_problem *p, double V_0, double eps, const hadi_samples *samples, int n_snap,
                                   const int *snap_steps, double *J, double *base) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
-    return jacobian_common(c, p, 0.0, V_0, eps, J, base, n_snap, snap_steps, nullptr, nullptr, &samples);
+    CallExtras x; x.ladder = true; x.n_snap = n_snap; x.snap_steps = snap_steps; x.sampled = true; x.samples = samples;
+    CallOut o; o.V_0 = V_0; o.eps = eps; o.J = J; o.base_prices = base;
+    return jacobian_common(c, p, x, o);
 }
 
 HADI_VARIANT_WRAPPERS(american, HADI_AM)

@@ -108,9 +108,7 @@ class HestonADI:
     def set_tuning(self, key, value):
         """Execution-path switch (hadi.h: 'small_grid', 'small_seq', 'small_sch', 'graph', 'american_p', 'strip', 'row_tile', 'col_groups',
         'small_waves', 'device_vgrid'); results agree to round-off."""
-        rc = self._lib.hadi_set_tuning(self._h, key.encode(), int(value))
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_set_tuning, key.encode(), int(value))
 
     def get_tuning(self, key):
         v = C.c_int()
@@ -126,9 +124,7 @@ class HestonADI:
         import torch
         if stream is None:
             stream = torch.cuda.current_stream(torch.device("cuda", self.device_id))
-        rc = self._lib.hadi_wait_stream(self._h, C.c_void_p(stream.cuda_stream))
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_wait_stream, C.c_void_p(stream.cuda_stream))
 
     def timing(self):
         t = nat.Timing()
@@ -224,6 +220,34 @@ class HestonADI:
             return CALL, None
         return per_instance.get("option_type", CALL), per_instance.get("strikes")
 
+    def _base_problem(self, variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, num_strikes,
+                      deviceGrids, workspace, U_0, dividends, per_instance, scheme):
+        """The problem of a compute_base_prices* launcher: workspace.U is the state, the v-grid is rebuilt by the library."""
+        option_type, strikes = self._option(per_instance)
+        if total_size != (m1 + 1) * (m2 + 1):
+            raise ValueError("total_size != (m1+1)*(m2+1)")
+        if deviceGrids.Vec_s.shape[0] != num_strikes:
+            raise ValueError("num_strikes does not match the grid batch")
+        return self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=workspace.U,
+                             U_0=U_0, dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
+                             option_type=option_type, strikes=strikes)
+
+    def _jacobian_problem(self, variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, deviceGrids,
+                          U_0, dividends, per_instance, scheme):
+        """The problem of a compute_jacobian* launcher: every solve starts from U_0, the v-grids are rebuilt by the library."""
+        if total_size != (m1 + 1) * (m2 + 1):
+            raise ValueError("total_size != (m1+1)*(m2+1)")
+        option_type, strikes = self._option(per_instance)
+        return self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=None, U_0=U_0,
+                             dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
+                             option_type=option_type, strikes=strikes)
+
+    def _call(self, fn, *args):
+        """One native call on this handle; a status other than HADI_OK raises HadiError with the library's message."""
+        rc = fn(self._h, *args)
+        if rc != nat.HADI_OK:
+            self._raise(rc)
+
     def _out(self, n, cols, like):
         if _is_device(like):
             import torch
@@ -244,9 +268,7 @@ class HestonADI:
         p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids,
                           U=U, U_0=U_0, lambda_bar=lambda_bar, dividends=dividends, per_instance=per_instance,
                           scheme=scheme, state_precision=state_precision, option_type=option_type, strikes=strikes)
-        rc = self._lib.hadi_DO_timestepping(self._h, C.byref(p))
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_DO_timestepping, C.byref(p))
         return U
 
     # ---- diagnostics: the two directional passes of one Douglas step as operators (hadi.h) -------------------------
@@ -256,27 +278,21 @@ class HestonADI:
         p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U=U, U_0=U_0,
                           option_type=option_type, strikes=strikes)
         out, optr = self._out(grids.Vec_s.shape[0], (m1 + 1) * (m2 + 1), U)
-        rc = self._lib.hadi_debug_row_pass(self._h, C.byref(p), int(step), optr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_debug_row_pass, C.byref(p), int(step), optr)
         return out
 
     def debug_col_solve(self, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, rhs):
         """(I - theta dt A2)^{-1} rhs through the product's column pass (rhs not modified)."""
         p = self._problem(EU, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U=rhs)
         out, optr = self._out(grids.Vec_s.shape[0], (m1 + 1) * (m2 + 1), rhs)
-        rc = self._lib.hadi_debug_col_solve(self._h, C.byref(p), optr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_debug_col_solve, C.byref(p), optr)
         return out
 
     def debug_rcp(self, x):
         """1/x exactly as the line solves of the sweep form it (v_rcp_f64 + one Newton step), elementwise (tests)."""
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
         out = np.empty_like(x)
-        rc = self._lib.hadi_debug_rcp(self._h, int(x.size), x.ctypes.data_as(nat._dp), out.ctypes.data_as(nat._dp))
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_debug_rcp, int(x.size), x.ctypes.data_as(nat._dp), out.ctypes.data_as(nat._dp))
         return out
 
     # ---- CS_scheme_shuffled (src/solver.hpp:781-907), batched on the device -----------------------
@@ -308,9 +324,7 @@ class HestonADI:
         p = self._problem(EU, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
                           U=workspace.U)
         out, optr = self._out(nInstances, 1, workspace.U)
-        rc = self._lib.hadi_parallel_DO_solve(self._h, C.byref(p), float(S_0), float(V_0), optr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_parallel_DO_solve, C.byref(p), float(S_0), float(V_0), optr)
         if base_prices is not None:
             base_prices[...] = out
             return base_prices
@@ -334,9 +348,7 @@ class HestonADI:
         if ladder:
             lad, lptr = self._out(n * (m1 + 1), nat.N_GREEKS, U)
             lad = lad.reshape(n, m1 + 1, nat.N_GREEKS)
-        rc = self._lib.hadi_compute_greeks(self._h, C.byref(p), float(S_0), float(V_0), optr, lptr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_compute_greeks, C.byref(p), float(S_0), float(V_0), optr, lptr)
         return (out, lad) if ladder else out
 
     # ---- maturity ladder (hadi_maturity_ladder and its launchers; no reference counterpart) ---------------
@@ -359,10 +371,8 @@ class HestonADI:
                           strikes=strikes)
         steps = self._snap(snap_steps)
         out, optr = self._out(grids.Vec_s.shape[0], steps.size, U)
-        rc = self._lib.hadi_maturity_ladder(self._h, C.byref(p), float(S_0), float(V_0), int(steps.size),
-                                            steps.ctypes.data_as(_ip), optr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_maturity_ladder, C.byref(p), float(S_0), float(V_0), int(steps.size),
+                   steps.ctypes.data_as(_ip), optr)
         return out.reshape(-1, steps.size)
 
     def compute_base_prices_ladder(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
@@ -370,20 +380,12 @@ class HestonADI:
                                    per_instance=None, scheme=0):
         """compute_base_prices* (the v-grid rebuilt for V_0 or per_instance['V_0_i']) with the ladder's output: [n][len(snap_steps)],
         entry q what the single call with N = snap_steps[q] returns.  workspace.U is the initial condition and is not modified."""
-        option_type, strikes = self._option(per_instance)
-        if total_size != (m1 + 1) * (m2 + 1):
-            raise ValueError("total_size != (m1+1)*(m2+1)")
-        if deviceGrids.Vec_s.shape[0] != num_strikes:
-            raise ValueError("num_strikes does not match the grid batch")
-        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=workspace.U,
-                          U_0=U_0, dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
-                          option_type=option_type, strikes=strikes)
+        p = self._base_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, num_strikes,
+                               deviceGrids, workspace, U_0, dividends, per_instance, scheme)
         steps = self._snap(snap_steps)
         out, optr = self._out(num_strikes, steps.size, workspace.U)
-        rc = self._lib.hadi_compute_base_prices_ladder(self._h, C.byref(p), float(S_0), float(V_0), int(steps.size),
-                                                       steps.ctypes.data_as(_ip), optr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_compute_base_prices_ladder, C.byref(p), float(S_0), float(V_0), int(steps.size),
+                   steps.ctypes.data_as(_ip), optr)
         return out.reshape(-1, steps.size)
 
     def compute_jacobian_ladder(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
@@ -391,19 +393,13 @@ class HestonADI:
                                 per_instance=None, scheme=0):
         """compute_jacobian* with the ladder's outputs: (J [n][len(snap_steps)][5], base_prices [n][len(snap_steps)]); J[:, q, :]
         and base_prices[:, q] are what compute_jacobian* with N = snap_steps[q] returns."""
-        if total_size != (m1 + 1) * (m2 + 1):
-            raise ValueError("total_size != (m1+1)*(m2+1)")
-        option_type, strikes = self._option(per_instance)
-        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=None, U_0=U_0,
-                          dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
-                          option_type=option_type, strikes=strikes)
+        p = self._jacobian_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, deviceGrids,
+                                   U_0, dividends, per_instance, scheme)
         steps = self._snap(snap_steps)
         J, jptr = self._out(num_strikes * steps.size, 5, U_0)
         base, bptr = self._out(num_strikes, steps.size, U_0)
-        rc = self._lib.hadi_compute_jacobian_ladder(self._h, C.byref(p), float(S_0), float(V_0), float(eps), int(steps.size),
-                                                    steps.ctypes.data_as(_ip), jptr, bptr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_compute_jacobian_ladder, C.byref(p), float(S_0), float(V_0), float(eps), int(steps.size),
+                   steps.ctypes.data_as(_ip), jptr, bptr)
         return J.reshape(num_strikes, steps.size, 5), base.reshape(-1, steps.size)
 
     # ---- sampled ladder (hadi_sample_ladder and its launchers; no reference counterpart) ---------------------
@@ -442,10 +438,8 @@ class HestonADI:
         steps = self._snap(snap_steps)
         st, keep, n_samp = self._samples(n, spots, scales)
         out, optr = self._out(n, steps.size * n_samp, U)
-        rc = self._lib.hadi_sample_ladder(self._h, C.byref(p), float(V_0), C.byref(st), int(steps.size), steps.ctypes.data_as(_ip),
-                                          optr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_sample_ladder, C.byref(p), float(V_0), C.byref(st), int(steps.size), steps.ctypes.data_as(_ip),
+                   optr)
         return out.reshape(n, steps.size, n_samp)
 
     def compute_base_prices_samples(self, spots, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
@@ -453,21 +447,13 @@ class HestonADI:
                                     dividends=None, per_instance=None, scheme=0):
         """compute_base_prices_ladder (the v-grid rebuilt for V_0 or per_instance['V_0_i']) with sample_ladder's output:
         [n][len(snap_steps)][n_samp].  workspace.U is the initial condition and is not modified."""
-        option_type, strikes = self._option(per_instance)
-        if total_size != (m1 + 1) * (m2 + 1):
-            raise ValueError("total_size != (m1+1)*(m2+1)")
-        if deviceGrids.Vec_s.shape[0] != num_strikes:
-            raise ValueError("num_strikes does not match the grid batch")
-        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=workspace.U,
-                          U_0=U_0, dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
-                          option_type=option_type, strikes=strikes)
+        p = self._base_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, num_strikes,
+                               deviceGrids, workspace, U_0, dividends, per_instance, scheme)
         steps = self._snap(snap_steps)
         st, keep, n_samp = self._samples(num_strikes, spots, scales)
         out, optr = self._out(num_strikes, steps.size * n_samp, workspace.U)
-        rc = self._lib.hadi_compute_base_prices_samples(self._h, C.byref(p), float(V_0), C.byref(st), int(steps.size),
-                                                        steps.ctypes.data_as(_ip), optr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_compute_base_prices_samples, C.byref(p), float(V_0), C.byref(st), int(steps.size),
+                   steps.ctypes.data_as(_ip), optr)
         return out.reshape(num_strikes, steps.size, n_samp)
 
     def compute_jacobian_samples(self, spots, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
@@ -475,20 +461,14 @@ class HestonADI:
                                  per_instance=None, scheme=0):
         """compute_jacobian_ladder with sample_ladder's outputs: (J [n][len(snap_steps)][n_samp][5], base [n][len(snap_steps)][n_samp])
         from ONE sweep of the 6n solves; the v0 column samples the row of V_0 + eps of its own rebuilt v-grid."""
-        if total_size != (m1 + 1) * (m2 + 1):
-            raise ValueError("total_size != (m1+1)*(m2+1)")
-        option_type, strikes = self._option(per_instance)
-        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=None, U_0=U_0,
-                          dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
-                          option_type=option_type, strikes=strikes)
+        p = self._jacobian_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, deviceGrids,
+                                   U_0, dividends, per_instance, scheme)
         steps = self._snap(snap_steps)
         st, keep, n_samp = self._samples(num_strikes, spots, scales)
         J, jptr = self._out(num_strikes * steps.size * n_samp, 5, U_0)
         base, bptr = self._out(num_strikes, steps.size * n_samp, U_0)
-        rc = self._lib.hadi_compute_jacobian_samples(self._h, C.byref(p), float(V_0), float(eps), C.byref(st), int(steps.size),
-                                                     steps.ctypes.data_as(_ip), jptr, bptr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_compute_jacobian_samples, C.byref(p), float(V_0), float(eps), C.byref(st), int(steps.size),
+                   steps.ctypes.data_as(_ip), jptr, bptr)
         return J.reshape(num_strikes, steps.size, n_samp, 5), base.reshape(num_strikes, steps.size, n_samp)
 
     # ---- Bermudan options (hadi_bermudan_timestepping and its launchers; no reference counterpart) --------------
@@ -517,9 +497,7 @@ class HestonADI:
         p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U=U, U_0=U_0,
                           dividends=dividends, per_instance=per_instance, scheme=scheme, option_type=option_type, strikes=strikes)
         ex, rows, n_ex = self._schedule(exercise_steps)
-        rc = self._lib.hadi_bermudan_timestepping(self._h, C.byref(p), n_ex, ex.ctypes.data_as(_ip), rows)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_bermudan_timestepping, C.byref(p), n_ex, ex.ctypes.data_as(_ip), rows)
         return U
 
     def compute_base_prices_bermudan(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
@@ -527,20 +505,12 @@ class HestonADI:
                                      per_instance=None, scheme=0):
         """compute_base_prices* (the v-grid rebuilt for V_0 or per_instance['V_0_i']) of Bermudan options: [n] prices at
         (S_0, V_0).  workspace.U is the initial condition (and the payoff where U_0 is None) and receives the field."""
-        option_type, strikes = self._option(per_instance)
-        if total_size != (m1 + 1) * (m2 + 1):
-            raise ValueError("total_size != (m1+1)*(m2+1)")
-        if deviceGrids.Vec_s.shape[0] != num_strikes:
-            raise ValueError("num_strikes does not match the grid batch")
-        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=workspace.U,
-                          U_0=U_0, dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
-                          option_type=option_type, strikes=strikes)
+        p = self._base_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, num_strikes,
+                               deviceGrids, workspace, U_0, dividends, per_instance, scheme)
         ex, rows, n_ex = self._schedule(exercise_steps)
         out, optr = self._out(num_strikes, 1, workspace.U)
-        rc = self._lib.hadi_compute_base_prices_bermudan(self._h, C.byref(p), float(S_0), float(V_0), n_ex,
-                                                         ex.ctypes.data_as(_ip), rows, optr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_compute_base_prices_bermudan, C.byref(p), float(S_0), float(V_0), n_ex,
+                   ex.ctypes.data_as(_ip), rows, optr)
         return out
 
     def compute_jacobian_bermudan(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
@@ -548,19 +518,13 @@ class HestonADI:
                                   per_instance=None, scheme=0):
         """compute_jacobian* of Bermudan options: (J [n][5], base_prices [n]); the six solves of an instance share its
         schedule, U_0 is the initial condition and the payoff."""
-        if total_size != (m1 + 1) * (m2 + 1):
-            raise ValueError("total_size != (m1+1)*(m2+1)")
-        option_type, strikes = self._option(per_instance)
-        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=None, U_0=U_0,
-                          dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
-                          option_type=option_type, strikes=strikes)
+        p = self._jacobian_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, deviceGrids,
+                                   U_0, dividends, per_instance, scheme)
         ex, rows, n_ex = self._schedule(exercise_steps)
         J, jptr = self._out(num_strikes, 5, U_0)
         base, bptr = self._out(num_strikes, 1, U_0)
-        rc = self._lib.hadi_compute_jacobian_bermudan(self._h, C.byref(p), float(S_0), float(V_0), float(eps), n_ex,
-                                                      ex.ctypes.data_as(_ip), rows, jptr, bptr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_compute_jacobian_bermudan, C.byref(p), float(S_0), float(V_0), float(eps), n_ex,
+                   ex.ctypes.data_as(_ip), rows, jptr, bptr)
         return J, base
 
     # ---- knock-out barrier options (hadi_barrier_timestepping and its launchers; no reference counterpart) ------
@@ -593,10 +557,8 @@ class HestonADI:
         p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U=U, dividends=dividends,
                           per_instance=per_instance, scheme=scheme, option_type=option_type, strikes=strikes)
         b, keep = self._barrier(p.n_instances, monitor_steps, lower, upper, rebate)
-        rc = self._lib.hadi_barrier_timestepping(self._h, C.byref(p), C.byref(b))
+        self._call(self._lib.hadi_barrier_timestepping, C.byref(p), C.byref(b))
         del keep
-        if rc != nat.HADI_OK:
-            self._raise(rc)
         return U
 
     def compute_base_prices_barrier(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
@@ -604,20 +566,12 @@ class HestonADI:
                                     variant=EU, dividends=None, per_instance=None, scheme=0):
         """compute_base_prices* (the v-grid rebuilt for V_0 or per_instance['V_0_i']) of knock-out options: [n] prices at
         (S_0, V_0).  workspace.U is the initial condition and receives the field."""
-        option_type, strikes = self._option(per_instance)
-        if total_size != (m1 + 1) * (m2 + 1):
-            raise ValueError("total_size != (m1+1)*(m2+1)")
-        if deviceGrids.Vec_s.shape[0] != num_strikes:
-            raise ValueError("num_strikes does not match the grid batch")
-        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=workspace.U,
-                          dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
-                          option_type=option_type, strikes=strikes)
+        p = self._base_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, num_strikes,
+                               deviceGrids, workspace, None, dividends, per_instance, scheme)
         b, keep = self._barrier(num_strikes, monitor_steps, lower, upper, rebate)
         out, optr = self._out(num_strikes, 1, workspace.U)
-        rc = self._lib.hadi_compute_base_prices_barrier(self._h, C.byref(p), float(S_0), float(V_0), C.byref(b), optr)
+        self._call(self._lib.hadi_compute_base_prices_barrier, C.byref(p), float(S_0), float(V_0), C.byref(b), optr)
         del keep
-        if rc != nat.HADI_OK:
-            self._raise(rc)
         return out
 
     def compute_jacobian_barrier(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
@@ -625,38 +579,23 @@ class HestonADI:
                                  variant=EU, dividends=None, per_instance=None, scheme=0):
         """compute_jacobian* of knock-out options: (J [n][5], base_prices [n]); the six solves of an instance share its
         barriers, rebate and schedule; U_0 is the initial condition."""
-        if total_size != (m1 + 1) * (m2 + 1):
-            raise ValueError("total_size != (m1+1)*(m2+1)")
-        option_type, strikes = self._option(per_instance)
-        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids, U=None, U_0=U_0,
-                          dividends=dividends, per_instance=per_instance, need_vgrid=False, scheme=scheme,
-                          option_type=option_type, strikes=strikes)
+        p = self._jacobian_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, deviceGrids,
+                                   U_0, dividends, per_instance, scheme)
         b, keep = self._barrier(num_strikes, monitor_steps, lower, upper, rebate)
         J, jptr = self._out(num_strikes, 5, U_0)
         base, bptr = self._out(num_strikes, 1, U_0)
-        rc = self._lib.hadi_compute_jacobian_barrier(self._h, C.byref(p), float(S_0), float(V_0), float(eps), C.byref(b), jptr, bptr)
+        self._call(self._lib.hadi_compute_jacobian_barrier, C.byref(p), float(S_0), float(V_0), float(eps), C.byref(b), jptr, bptr)
         del keep
-        if rc != nat.HADI_OK:
-            self._raise(rc)
         return J, base
 
     # ---- compute_base_prices* (src/jacobian_computation.cpp:368, 629, 922, 1232) ---------------
     def _base_prices(self, variant, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N,
                      theta, delta_t, num_strikes, deviceGrids, workspace, U_0=None, dividends=None,
                      per_instance=None, scheme=0):
-        option_type, strikes = self._option(per_instance)
-        if total_size != (m1 + 1) * (m2 + 1):
-            raise ValueError("total_size != (m1+1)*(m2+1)")
-        if deviceGrids.Vec_s.shape[0] != num_strikes:
-            raise ValueError("num_strikes does not match the grid batch")
-        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
-                          U=workspace.U, U_0=U_0, lambda_bar=None, dividends=dividends,
-                          per_instance=per_instance, need_vgrid=False, scheme=scheme, option_type=option_type,
-                          strikes=strikes)
+        p = self._base_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, num_strikes,
+                               deviceGrids, workspace, U_0, dividends, per_instance, scheme)
         out, optr = self._out(num_strikes, 1, workspace.U)
-        rc = self._lib.hadi_compute_base_prices(self._h, C.byref(p), float(S_0), float(V_0), optr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_compute_base_prices, C.byref(p), float(S_0), float(V_0), optr)
         return out
 
     def compute_base_prices(self, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta,
@@ -688,17 +627,11 @@ class HestonADI:
     # ---- compute_jacobian* (src/jacobian_computation.cpp:204, 457, 726, 1031) ------------------
     def _jacobian(self, variant, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta,
                   delta_t, num_strikes, deviceGrids, U_0, eps, dividends=None, per_instance=None, scheme=0):
-        if total_size != (m1 + 1) * (m2 + 1):
-            raise ValueError("total_size != (m1+1)*(m2+1)")
-        option_type, strikes = self._option(per_instance)
-        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
-                          U=None, U_0=U_0, dividends=dividends, per_instance=per_instance, need_vgrid=False,
-                          scheme=scheme, option_type=option_type, strikes=strikes)
+        p = self._jacobian_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, deviceGrids,
+                                   U_0, dividends, per_instance, scheme)
         J, jptr = self._out(num_strikes, 5, U_0)
         base, bptr = self._out(num_strikes, 1, U_0)
-        rc = self._lib.hadi_compute_jacobian(self._h, C.byref(p), float(S_0), float(V_0), float(eps), jptr, bptr)
-        if rc != nat.HADI_OK:
-            self._raise(rc)
+        self._call(self._lib.hadi_compute_jacobian, C.byref(p), float(S_0), float(V_0), float(eps), jptr, bptr)
         return J, base
 
     def compute_jacobian(self, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta,
@@ -842,10 +775,8 @@ def lm_partials_device(solver, J, model_prices, market_prices):
             raise ValueError("%s must be a CUDA tensor" % name)
     solver.wait_stream()
     out = np.empty(31)
-    rc = solver._lib.hadi_lm_partials_device(solver._h, n, C.c_void_p(J.data_ptr()), C.c_void_p(model_prices.data_ptr()),
-                                             C.c_void_p(market_prices.data_ptr()), out.ctypes.data_as(_dp))
-    if rc != nat.HADI_OK:
-        solver._raise(rc)
+    solver._call(solver._lib.hadi_lm_partials_device, n, C.c_void_p(J.data_ptr()), C.c_void_p(model_prices.data_ptr()),
+                 C.c_void_p(market_prices.data_ptr()), out.ctypes.data_as(_dp))
     return out
 
 

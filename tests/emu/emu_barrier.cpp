@@ -1,7 +1,7 @@
 // emu_barrier.cpp -- TEST-ONLY.  The wave emulator's driver of a knock-out barrier sweep: emu_small_sch.cpp (included whole, and
 // with it emu_driver.cpp: the two plain drivers the n_mon = 0 runs are compared with, emu_solve and emu_small_sch) plus one entry
 // point that builds the tables and packs the initial field as the library does (hadi_setup_kernel, hadi_pack_kernel), builds the
-// dividend and monitoring tables, the bounds and the rebates as stage_dividends / stage_barrier of hadi_api.hip do, locates the
+// dividend and monitoring tables, the bounds and the rebates as stage_dividends / stage_step_flags / stage_barrier of hadi_api.hip do, locates the
 // live index ranges (hadi_barrier_locate_kernel), and runs either a whole-loop kernel (the knock-out inside its time loop) or the
 // streaming loop of enqueue_sub_batch with hadi_knockout_kernel behind the listed steps.  Never shipped.
 #include "emu_small_sch.cpp"
@@ -13,7 +13,7 @@ extern "C" long long emu_barrier_packed_size(int n_inst, int m1, int m2) {
     return (long long)pl.L.inst_stride * n_inst;
 }
 
-// Arrays natural layout [n][...].  par8 [n][8]: rho, sigma, kappa, eta, dt, N, strike, put -- the rows fill_par builds; N and dt
+// Arrays natural layout [n][...].  par8 [n][8]: rho, sigma, kappa, eta, dt, N, strike, put -- the rows fill_desc builds; N and dt
 // may differ between instances.  kind: 0 / 1 hadi_small_kernel with 4 / 8 wavefronts, 2 hadi_small_seq_kernel, 3
 // hadi_small_seq2_kernel, 4 hadi_small_sch_kernel, 5 the streaming kernels (the plan's own choice; emu_set_tuning "strip" pins it).
 // scheme: enum hadi_scheme.  U: the initial field (not modified).  lower, upper, rebate [n] (-inf / +inf: no barrier on that side).
@@ -55,7 +55,7 @@ extern "C" int emu_barrier(int n_inst, int m1, int m2, double theta, double r_d,
         Nmax = std::max(Nmax, (int)par8[(size_t)k * 8 + 5]);
         uniform = uniform && par8[(size_t)k * 8 + 5] == par8[5] && par8[(size_t)k * 8 + 4] == par8[4];
     }
-    // the tables, as stage_dividends and stage_barrier build them
+    // the tables, as stage_dividends, stage_step_flags and stage_barrier build them
     const int flag_stride = uniform ? 0 : Nmax, mon_stride = mon_rows > 1 ? Nmax : 0;
     std::vector<int> flags((size_t)(uniform ? 1 : n_inst) * Nmax, -1), monf((size_t)(mon_stride ? n_inst : 1) * Nmax, 0);
     std::vector<char> div_step(Nmax + 1, 0), mon_step(Nmax + 1, 0);

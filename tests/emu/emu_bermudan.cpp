@@ -1,12 +1,12 @@
 // emu_bermudan.cpp -- TEST-ONLY.  The wave emulator's driver of a Bermudan sweep: emu_small_sch.cpp (included whole, and with it
 // emu_driver.cpp: the two non-Bermudan drivers the n_ex = 0 runs are compared with, emu_solve and emu_small_sch) plus one entry
 // point that builds the tables, packs the initial field and the payoff as the library does (hadi_setup_kernel, hadi_pack_kernel),
-// builds the dividend and exercise tables as stage_dividends / stage_exercise of hadi_api.hip do, and runs either a whole-loop
+// builds the dividend and exercise tables as stage_dividends / stage_step_flags of hadi_api.hip do, and runs either a whole-loop
 // kernel (the exercise inside its time loop) or the streaming loop of enqueue_sub_batch with hadi_exercise_kernel behind the
 // listed steps.  A second entry point returns the route of a Bermudan call.  Never shipped.
 #include "emu_small_sch.cpp"
 
-// Arrays natural layout [n][...].  par8 [n][8]: rho, sigma, kappa, eta, dt, N, strike, put -- the rows fill_par builds; N and dt
+// Arrays natural layout [n][...].  par8 [n][8]: rho, sigma, kappa, eta, dt, N, strike, put -- the rows fill_desc builds; N and dt
 // may differ between instances.  kind: 0 / 1 hadi_small_kernel with 4 / 8 wavefronts, 2 hadi_small_seq_kernel, 3
 // hadi_small_seq2_kernel, 4 hadi_small_sch_kernel, 5 the streaming kernels (the plan's own choice; emu_set_tuning "strip" pins it).
 // scheme: enum hadi_scheme.  U: the initial field (not modified); U0: the payoff, or NULL = the initial field.  ex_steps
@@ -55,7 +55,7 @@ static int bermudan_run(int n_inst, int m1, int m2, double theta, double r_d, do
         Nmax = std::max(Nmax, (int)par8[(size_t)k * 8 + 5]);
         uniform = uniform && par8[(size_t)k * 8 + 5] == par8[5] && par8[(size_t)k * 8 + 4] == par8[4];
     }
-    // the two tables, as stage_dividends and stage_exercise build them
+    // the two tables, as stage_dividends and stage_step_flags build them
     const int flag_stride = uniform ? 0 : Nmax, ex_stride = ex_rows > 1 ? Nmax : 0;
     std::vector<int> flags((size_t)(uniform ? 1 : n_inst) * Nmax, -1), exf((size_t)(ex_stride ? n_inst : 1) * Nmax, 0);
     std::vector<char> div_step(Nmax + 1, 0), ex_step(Nmax + 1, 0);

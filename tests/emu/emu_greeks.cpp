@@ -5,9 +5,9 @@
 #include "emu_driver.cpp"
 
 // Arrays natural layout [n][...].  par8 [n][8]: rho, sigma, kappa, eta, dt, N, strike, option type (0 call, 1 put), the rows
-// fill_par of hadi_api.hip builds.  LAM: lambda_bar at T for American variants, NULL otherwise.  greeks [n][8]; ladder
+// fill_desc of hadi_api.hip builds.  LAM: lambda_bar at T for American variants, NULL otherwise.  greeks [n][8]; ladder
 // [n][m1+1][8] or NULL; status [n] (0 ok, 1 S_0 off the s-grid, 2 V_0 off the v-grid).  The launch geometry is the library's
-// (greeks_common).  Returns 0, or 1 if the shape has no plan.
+// (greeks_common; S_0 and V_0 reach it in its CallOut).  Returns 0, or 1 if the shape has no plan.
 extern "C" int emu_greeks(int n_inst, int m1, int m2, double theta, double r_d, double r_f, const double *par8,
                           const double *vec_s, const double *vec_v, const double *delta_s, const double *delta_v,
                           const double *U, const double *LAM, double S_0, double V_0, double *greeks, double *ladder,

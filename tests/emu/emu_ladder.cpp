@@ -5,7 +5,7 @@
 // Never shipped.
 #include "emu_driver.cpp"
 
-// Arrays natural layout [n][...].  par8 [n][8]: rho, sigma, kappa, eta, dt, N, strike, put -- the rows fill_par of hadi_api.hip
+// Arrays natural layout [n][...].  par8 [n][8]: rho, sigma, kappa, eta, dt, N, strike, put -- the rows fill_desc of hadi_api.hip
 // builds (one N for the whole batch: a ladder shares the step indices).  kind: 0 / 1 hadi_small_kernel with 4 / 8 wavefronts,
 // 2 hadi_small_seq_kernel, 3 hadi_small_seq2_kernel, 4 hadi_small_sch_kernel (scheme: enum hadi_scheme 1 .. 3; else 0).
 // variant: bit 0 American (kinds 0 / 1 only), bit 1 dividends.  U: the initial field (not modified); U0: the payoff or NULL.

@@ -5,7 +5,7 @@
 
 // European Douglas sweep.  Arrays natural layout [n][...]; N_i / dt_i: per-instance step grids (NULL: N and dt for every
 // instance; the launch runs to the largest N_i and every block stops at its own).  strike / put: per-instance strikes and the
-// option type (put != 0: put boundary data K e^{-r_d t}; they fill par8[6] and par8[7] as fill_par of hadi_api.hip does).  The strip geometry is forced to ONE block
+// option type (put != 0: put boundary data K e^{-r_d t}; they fill par8[6] and par8[7] as fill_desc of hadi_api.hip does).  The strip geometry is forced to ONE block
 // per instance (tuning "strip" = 1, "strip_blocks" = 1 on top of the emulator's tuning), whatever the batch size: the
 // library's selection rules are tested on the GPU.  Returns 0, 1 (no plan), 3 (the shape is not eligible) or 4 (device error
 // word set).

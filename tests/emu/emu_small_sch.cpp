@@ -3,7 +3,7 @@
 // (hadi_setup_kernel, hadi_pack_kernel), runs the kernel's whole time loop and unpacks the result.  Never shipped.
 #include "emu_driver.cpp"
 
-// Arrays natural layout [n][...].  par8 [n][8]: rho, sigma, kappa, eta, dt, N, 0, 0 (call boundary data), the rows fill_par
+// Arrays natural layout [n][...].  par8 [n][8]: rho, sigma, kappa, eta, dt, N, 0, 0 (call boundary data), the rows fill_desc
 // of hadi_api.hip builds.  scheme: enum hadi_scheme (1 Craig-Sneyd, 2 Modified Craig-Sneyd, 3 Hundsdorfer-Verwer).  The time
 // loop runs to the largest N_i with the instances dispatched longest first, as in the library.  U: initial field in, U_T out.
 // lds_bytes (may be NULL) receives the kernel's dynamic LDS.  Returns 0, 1 (no plan), 2 (no such kernel), 3 (grid or scheme
