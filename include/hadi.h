@@ -482,6 +482,57 @@ int hadi_compute_base_prices_barrier(hadi_ctx *ctx, const hadi_problem *p, doubl
 int hadi_compute_jacobian_barrier(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps,
                                   const hadi_barrier *barrier, double *J, double *base_prices);
 
+/* Forward-start options and cliquets: strike fixings -- NOT a reference feature.  A cliquet sweep is the sweep of
+ * hadi_DO_timestepping (variant HADI_EU or HADI_DIV) with one addition: after the last pass of every listed fixing step n, every
+ * instance k that lists n takes, on every v-row j, boundary rows included,
+ *     c_j     = U(i_ref, j)                      read before anything of the event is written
+ *     U(i, j) <- a_i * c_j + w * P(i, j)         for every node i = 0 .. m1 (the term w * P only when w != 0)
+ * The Heston problem is homogeneous in (s, K): at a fixing date the value for the as-yet-unknown strike is the value at ONE
+ * reference node of each v-row, scaled along the row.
+ *   i_ref     the node of the instance's own vec_s where ref_spot_i[k] sits, by the price pick's rule: the first node within 1e-10.
+ *             None: HADI_ERR_NOT_ON_GRID.
+ *   a_i       HADI_FIX_SHARES: a_i = s_i / s_{i_ref} (a payoff in currency whose strike is proportional to the fixing spot;
+ *             a_{i_ref} is exactly 1).  HADI_FIX_RETURN: a_i = 1 (a payoff that is a function of the return S / S_fix; after the
+ *             event the row is flat).
+ *   w         the weight of that fixing date, weights[row][q], parallel to the schedule; NULL = all weights 0.
+ *   P         the payoff field of the Bermudan calls: p->U_0, or the initial p->U where U_0 is NULL.  Read only where w != 0.
+ * Step n is time to maturity n delta_t_k on the instance's own clock; n = N_k is the valuation date.  A dividend acts at the START
+ * of its step, the fixing at its END; a step may carry both.  With a predictor-corrector scheme the fixing follows the corrector's
+ * column pass.  Exactly: SHARES with w = 0 leaves node (i_ref, j) with its bits; RETURN with w = 0 leaves every node of row j with
+ * c_j's bits; n_fix == 0 is the plain European call: same route, same bits.
+ * MODELLING STATEMENT: the boundary data of the sweep stay the vanilla option's, as for barriers.
+ * A forward-start call: initial condition (s - k S_ref)^+, one fixing at step (T - t1) / delta_t, SHARES, no weights, the price
+ * read at S_0.  A cliquet with coupons paid at the fixing dates: initial condition f(s / S_ref) (the local-return payoff),
+ * fixings at the period starts, RETURN, weights 1, put boundary data (they keep the s_max edge flat); coupons paid at maturity:
+ * weights exp(-r_d n delta_t), computed by the caller.
+ *   fix_steps host array [fix_rows][n_fix], the rules of ex_steps above; weights host [fix_rows][n_fix] or NULL, entries behind a
+ *             zero step are ignored.
+ * hadi_cliquet_timestepping reads and writes p exactly as hadi_bermudan_timestepping does (per-instance parameters, (N_i,
+ * delta_t_i), put data with strike_i, dividends, scheme, memory space); the two launchers rebuild the v-grid and honour V_0_i as
+ * the Bermudan launchers do, and the six groups of a Jacobian share their instance's reference spot, mode, schedule and weights.
+ * The LDS-resident whole-loop kernels apply the event inside their time loop; the streaming kernels are followed by
+ * hadi_fixing_gather_kernel and hadi_fixing_kernel on the steps that some instance lists.  A cliquet call never takes
+ * hadi_sweep_resident or hadi_team_kernel.
+ * Not covered: a reference spot between two nodes; fixings combined with exercise, knock-out or the ladder in one call; globally
+ * capped cliquets (truly path-dependent).
+ * Errors: HADI_AM / HADI_AM_DIV or HADI_STATE_FP32: HADI_ERR_UNSUPPORTED; a schedule that breaks the rules, a NULL struct, NULL
+ * ref_spot_i with n_fix > 0, a non-finite reference spot or weight, a mode other than 0 or 1, SHARES with ref_spot <= 1e-10 (node 0
+ * is the grid's 0), a NULL output: HADI_ERR_INVALID; everything the underlying entry point refuses keeps its status. */
+enum hadi_fixing_mode { HADI_FIX_SHARES = 0, HADI_FIX_RETURN = 1 };
+typedef struct hadi_cliquet {
+    const double *ref_spot_i; /* host [n], required when n_fix > 0 */
+    const int *mode_i;        /* host [n] or NULL (= SHARES) */
+    int n_fix;
+    const int *fix_steps;
+    int fix_rows;          /* [fix_rows][n_fix], the rules of ex_steps */
+    const double *weights; /* host [fix_rows][n_fix] or NULL (= 0) */
+} hadi_cliquet;
+int hadi_cliquet_timestepping(hadi_ctx *ctx, const hadi_problem *p, const hadi_cliquet *cliquet);
+int hadi_compute_base_prices_cliquet(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, const hadi_cliquet *cliquet,
+                                     double *base_prices);
+int hadi_compute_jacobian_cliquet(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps,
+                                  const hadi_cliquet *cliquet, double *J, double *base_prices);
+
 /* v-grid rebuilt from (V_0, V = 5.0, d = 5.0/500) exactly as every call site of the reference
  * does (jacobian_computation.cpp:253); p->vec_v / p->delta_v are ignored. */
 int hadi_compute_base_prices(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0,

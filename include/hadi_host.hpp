@@ -371,6 +371,60 @@ inline void compute_jacobian_barrier(Handle &h, double S_0, double V_0, double /
     detail::check(h, hadi_compute_jacobian_barrier(h.ctx, &p, S_0, V_0, eps, &b, J.data(), base_prices.data()));
 }
 
+// Forward-start options and cliquets (hadi_cliquet_timestepping and its two launchers; NOT in the reference): the European or
+// dividend sweep with U(i, j) <- a_i U(i_ref, j) + w P(i, j) at the end of the fixing steps.  ref_spot: one value per instance (a
+// node of its s-grid); mode: one HADI_FIX_SHARES / HADI_FIX_RETURN per instance, or empty = SHARES; fix_steps:
+// [fix_rows][fix_steps.size() / fix_rows], the rules of ex_steps above; weights: the same shape, or empty = 0.  workspace.U is the
+// caller's initial condition and the payoff P (the launchers' U_0 likewise) and receives the field.
+struct Cliquet {
+    std::vector<double> ref_spot, weights;
+    std::vector<int> mode, fix_steps;
+    int fix_rows = 1;
+    hadi_cliquet view(int num_strikes) const {
+        if (fix_rows < 1 || fix_steps.size() % (size_t)fix_rows) throw std::runtime_error("fix_steps is not [fix_rows][n_fix]");
+        if (!weights.empty() && weights.size() != fix_steps.size()) throw std::runtime_error("weights is not [fix_rows][n_fix]");
+        if (ref_spot.size() != (size_t)num_strikes || (!mode.empty() && mode.size() != (size_t)num_strikes))
+            throw std::runtime_error("a cliquet array is not [num_strikes]");
+        return hadi_cliquet{ref_spot.data(), mode.empty() ? nullptr : mode.data(), (int)(fix_steps.size() / fix_rows), fix_steps.data(),
+                            fix_rows, weights.empty() ? nullptr : weights.data()};
+    }
+};
+inline void cliquet_timestepping(Handle &h, int m1, int m2, int N, double delta_t, double theta, double r_d, double r_f, double rho,
+                                 double sigma, double kappa, double eta, int num_strikes, const GridViews &deviceGrids,
+                                 DO_Workspace &workspace, const Cliquet &cliquet, int variant = HADI_EU, const Dividends *div = nullptr,
+                                 const PutStrikes *put = nullptr) {
+    const hadi_cliquet q = cliquet.view(num_strikes);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  workspace.U.data(), nullptr, div, put);
+    detail::check(h, hadi_cliquet_timestepping(h.ctx, &p, &q));
+}
+// ... with the v-grid rebuilt for V_0 and the price pick, as compute_base_prices does
+inline void compute_base_prices_cliquet(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho,
+                                        double sigma, double kappa, double eta, int m1, int m2, int /*total_size*/, int N,
+                                        double theta, double delta_t, int num_strikes, const GridViews &deviceGrids,
+                                        DO_Workspace &workspace, const Cliquet &cliquet, std::vector<double> &base_prices,
+                                        int variant = HADI_EU, const Dividends *div = nullptr, const PutStrikes *put = nullptr) {
+    const hadi_cliquet q = cliquet.view(num_strikes);
+    base_prices.resize(num_strikes);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  workspace.U.data(), nullptr, div, put);
+    detail::check(h, hadi_compute_base_prices_cliquet(h.ctx, &p, S_0, V_0, &q, base_prices.data()));
+}
+// J: [num_strikes][5], base_prices: [num_strikes]; the six solves of an instance share its reference spot, mode, schedule and weights
+inline void compute_jacobian_cliquet(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho,
+                                     double sigma, double kappa, double eta, int m1, int m2, int /*total_size*/, int N, double theta,
+                                     double delta_t, int num_strikes, const GridViews &deviceGrids, const std::vector<double> &U_0,
+                                     const Cliquet &cliquet, std::vector<double> &J, std::vector<double> &base_prices,
+                                     double eps = 1e-6, int variant = HADI_EU, const Dividends *div = nullptr,
+                                     const PutStrikes *put = nullptr) {
+    const hadi_cliquet q = cliquet.view(num_strikes);
+    J.resize((size_t)num_strikes * 5);
+    base_prices.resize(num_strikes);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  nullptr, U_0.data(), div, put);
+    detail::check(h, hadi_compute_jacobian_cliquet(h.ctx, &p, S_0, V_0, eps, &q, J.data(), base_prices.data()));
+}
+
 // jacobian_computation.cpp:204-364 and the three variants.  J: [num_strikes][5], columns kappa, eta, sigma, rho, v0.
 inline void compute_jacobian(Handle &h, double S_0, double V_0, double, double r_d, double r_f, double rho, double sigma,
                              double kappa, double eta, int m1, int m2, int, int N, double theta, double delta_t,

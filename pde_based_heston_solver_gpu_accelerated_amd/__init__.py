@@ -8,10 +8,11 @@ this package only marshals arguments.  There is no CPU fallback.
 from ._native import EU, AM, DIV, AM_DIV, CALL, PUT, HadiError, LIB_PATH, STATE_FP64, STATE_FP32  # noqa: F401
 from ._native import (G_PRICE, G_DELTA, G_GAMMA, G_DV, G_DVV, G_DSV, G_THETA, G_LAMBDA, N_GREEKS,  # noqa: F401
                       GREEK_NAMES)
+from ._native import FIX_SHARES, FIX_RETURN  # noqa: F401
 from ._native import SCHEME_DOUGLAS, SCHEME_CRAIG_SNEYD, SCHEME_MCS, SCHEME_HV  # noqa: F401
 from .grid import Grid, GridViewsBatch  # noqa: F401
 from .solver import (HestonADI, DOWorkspace, Dividends, compute_parameter_update,  # noqa: F401
-                     exercise_steps, knock_out_payoff, lm_partials, lm_partials_device, lm_solve, monitoring_steps,
+                     exercise_steps, fixing_steps, knock_out_payoff, local_return_payoff, lm_partials, lm_partials_device, lm_solve, monitoring_steps,
                      strike_samples)
 from .distributed import Communicator, shard_range  # noqa: F401
 from .calibration import (CalibrationPoint, calibrate, calibrate_american, calibrate_american_dividends,  # noqa: F401
@@ -29,5 +30,6 @@ __all__ = ["EU", "AM", "DIV", "AM_DIV", "CALL", "PUT", "lm_partials_device", "ST
            "calibrate_european_multi_maturity", "calibrate_american_dividends_multi_maturity",
            "make_calibration_points", "export_calibration_csv", "make_ladder_points", "calibrate_european_maturity_ladder",
            "calibrate_european_surface", "strike_samples", "calibrate_bermudan", "exercise_steps", "knock_out_payoff", "monitoring_steps",
+           "fixing_steps", "local_return_payoff", "FIX_SHARES", "FIX_RETURN",
            "G_PRICE", "G_DELTA", "G_GAMMA", "G_DV", "G_DVV", "G_DSV",
            "G_THETA", "G_LAMBDA", "N_GREEKS", "GREEK_NAMES"]

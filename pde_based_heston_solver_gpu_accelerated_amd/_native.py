@@ -51,9 +51,17 @@ class Problem(C.Structure):
     ]
 
 
+FIX_SHARES, FIX_RETURN = 0, 1  # enum hadi_fixing_mode
+
+
 class Barrier(C.Structure):
     """struct hadi_barrier (include/hadi.h)."""
     _fields_ = [("lower_i", _dp), ("upper_i", _dp), ("rebate_i", _dp), ("n_mon", C.c_int), ("mon_steps", _ip), ("mon_rows", C.c_int)]
+
+
+class Cliquet(C.Structure):
+    """struct hadi_cliquet (include/hadi.h)."""
+    _fields_ = [("ref_spot_i", _dp), ("mode_i", _ip), ("n_fix", C.c_int), ("fix_steps", _ip), ("fix_rows", C.c_int), ("weights", _dp)]
 
 
 class Samples(C.Structure):
@@ -82,6 +90,7 @@ EXPORTS = [
     "hadi_sample_ladder", "hadi_compute_base_prices_samples", "hadi_compute_jacobian_samples",
     "hadi_bermudan_timestepping", "hadi_compute_base_prices_bermudan", "hadi_compute_jacobian_bermudan",
     "hadi_barrier_timestepping", "hadi_compute_base_prices_barrier", "hadi_compute_jacobian_barrier",
+    "hadi_cliquet_timestepping", "hadi_compute_base_prices_cliquet", "hadi_compute_jacobian_cliquet",
     "hadi_compute_base_prices", "hadi_compute_base_prices_american",
     "hadi_compute_base_prices_dividends", "hadi_compute_base_prices_american_dividends",
     "hadi_compute_jacobian", "hadi_compute_jacobian_american",
@@ -163,6 +172,12 @@ def _load(LIB_PATH):
         L.hadi_barrier_timestepping.argtypes = [C.c_void_p, C.POINTER(Problem), _bp]
         L.hadi_compute_base_prices_barrier.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, _bp, C.c_void_p]
         L.hadi_compute_jacobian_barrier.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_double, _bp, C.c_void_p,
+                                                    C.c_void_p]
+    if hasattr(L, "hadi_cliquet_timestepping"):  # (likewise: a build from before the cliquet entry points)
+        _cp = C.POINTER(Cliquet)
+        L.hadi_cliquet_timestepping.argtypes = [C.c_void_p, C.POINTER(Problem), _cp]
+        L.hadi_compute_base_prices_cliquet.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, _cp, C.c_void_p]
+        L.hadi_compute_jacobian_cliquet.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_double, _cp, C.c_void_p,
                                                     C.c_void_p]
     if hasattr(L, "hadi_sample_ladder"):  # (likewise: a build from before the sampled ladder)
         _sp = C.POINTER(Samples)

@@ -63,6 +63,10 @@ struct Ctx {
     // knock-out barrier: the monitoring table (as ex_flag), the bounds [n][2], the live index ranges [n][2] (hadi_barrier_locate_kernel)
     // and the rebates [n]
     DevBuf ko_flag, ko_bounds, ko_iab, ko_rebate;
+    // strike fixings (cliquet calls): the fixing table (as ex_flag) and the weights' table of the same shape and stride, the reference
+    // spots [n], their nodes [n] with the status words [n] behind them (hadi_fixing_locate_kernel), the modes [n] and the gathered
+    // reference values c [n][nrows_pad] of the streaming path (hadi_fixing_gather_kernel)
+    DevBuf fix_flag, fix_w, fix_ref, fix_iref, fix_mode, fix_c;
     DevBuf snap_steps, snap_node, snap_out;  // maturity ladder: the snapshot steps, the instances' price nodes, the snapshots [n][n_snap]
     // sampled ladder: the spots [n][n_samp] and behind them the scales [n][n_samp] as staged; the tap records [n][n_samp] and behind
     // them the samples' flag words [n][n_samp] (hadi_sample_locate_kernel); the samples [n][n_snap][n_samp]
@@ -251,6 +255,12 @@ struct SweepDesc {
     // reads entry k % n_src as it reads its schedule's row.
     ExSched ex, mon;
     const double *ko_lower = nullptr, *ko_upper = nullptr, *ko_rebate = nullptr;
+    // Strike fixings (hadi_cliquet_timestepping and its launchers): fix.n_ex > 0 = the steps at whose end an instance fixes its
+    // strike; fix_ref: host [n_src] (validated); fix_mode: host [n_src] or null (= SHARES); fix_weights: host [fix.rows][fix.n_ex]
+    // or null (= 0), parallel to the schedule.  Instance k reads entry / row k % n_src.
+    ExSched fix;
+    const double *fix_ref = nullptr, *fix_weights = nullptr;
+    const int *fix_mode = nullptr;
 };
 
 // Kernels whose dynamic LDS can exceed the 64 KiB default need the limit raised once (hadi_create: every kernel of
@@ -277,6 +287,7 @@ struct Sweep {
     StepTable div;               // somebody pays a dividend at the step's start
     StepTable ex;                // somebody may be exercised at the step's end (Bermudan)
     StepTable mon;               // somebody is monitored at the step's end (knock-out barrier)
+    StepTable fix;               // somebody fixes its strike at the step's end (cliquet)
     std::vector<int> snap_q;     // step -> snapshot index of a ladder call, or -1
     bool amp = false;            // American sweeps in the P representation (hadi_row_step, AMER == 2)
     HadiSweepArgs a, av;         // whole-batch arguments; Craig-Sneyd: the predictor's column pass writes V (= Y2), the
@@ -322,6 +333,10 @@ int grow_buffers(Ctx *c, Sweep &w) {
     if (r.bermudan && (rc = ensure(c, c->ex_flag, w.ex.bytes(d)))) return rc;
     if (r.barrier && ((rc = ensure(c, c->ko_flag, w.mon.bytes(d))) || (rc = ensure(c, c->ko_bounds, 16 * n)) ||
                       (rc = ensure(c, c->ko_iab, 2 * sizeof(int) * n)) || (rc = ensure(c, c->ko_rebate, 8 * n))))
+        return rc;
+    if (r.cliquet && ((rc = ensure(c, c->fix_flag, w.fix.bytes(d))) || (rc = ensure(c, c->fix_w, 2 * w.fix.bytes(d))) ||
+                      (rc = ensure(c, c->fix_ref, 8 * n)) || (rc = ensure(c, c->fix_iref, 2 * sizeof(int) * n)) ||
+                      (rc = ensure(c, c->fix_mode, sizeof(int) * n)) || (rc = ensure(c, c->fix_c, 8 * n * pl.L.nrows_pad))))
         return rc;
     if (r.need_ut && (rc = ensure(c, c->UT, st))) return rc;
     if (r.need_f32 && ((rc = ensure(c, c->Uf, st / 2)) || (rc = ensure(c, c->Yf, st / 2)))) return rc;
@@ -411,6 +426,34 @@ int stage_barrier(Ctx *c, const Sweep &w) {
     return HADI_OK;
 }
 
+// Cliquet: behind the fixing table, the weights' table (the shape and stride of the fixing table: entry [k][n - 1] is the weight of
+// instance k's fixing at step n), the reference spots and the modes of all n instances, then the reference nodes and their status
+// words from the device s-grids (hadi_fixing_locate_kernel) -- on every call, also before a replay: they are data.
+int *fix_status(Ctx *c, const SweepDesc &d) { return ptr<int>(c->fix_iref) + d.n; }
+int stage_cliquet(Ctx *c, const Sweep &w) {
+    const SweepDesc &d = w.d;
+    const int rows = w.fix.stride ? d.n : 1;
+    std::vector<double> wt((size_t)rows * d.Nmax, 0.0), ref(d.n);
+    std::vector<int> mode(d.n);
+    for (int k = 0; k < rows; k++) {
+        const size_t row = (size_t)(w.fix.stride ? k % d.n_src : 0) * d.fix.n_ex;
+        for (int q = 0; q < d.fix.n_ex && d.fix_weights; q++)
+            if (d.fix.steps[row + q] > 0) wt[(size_t)k * d.Nmax + d.fix.steps[row + q] - 1] = d.fix_weights[row + q];
+    }
+    for (int k = 0; k < d.n; k++) {
+        ref[k] = d.fix_ref[k % d.n_src];
+        mode[k] = d.fix_mode ? d.fix_mode[k % d.n_src] : HADI_FIX_SHARES;
+    }
+    int rc;
+    if ((rc = stage_step_flags(c, d, d.fix, w.fix, c->fix_flag)) || (rc = stage_to_device(c, c->fix_w.p, wt.data(), wt.size() * 8)) ||
+        (rc = stage_to_device(c, c->fix_ref.p, ref.data(), ref.size() * 8)) ||
+        (rc = stage_to_device(c, c->fix_mode.p, mode.data(), mode.size() * sizeof(int))))
+        return rc;
+    hipLaunchKernelGGL(hadi_fixing_locate_kernel, dim3((d.n + 63) / 64), dim3(64), 0, c->stream, w.r.pl.L, d.n, d.d_vec_s,
+                       ptr<double>(c->fix_ref), ptr<int>(c->fix_iref), fix_status(c, d));
+    return HADI_OK;
+}
+
 // Sampled ladder: the lists of all n instances to the device, then the tap records and flag words from the sweep's own device
 // grids (hadi_sample_locate_kernel) -- on every call, also before a replay: the taps are data, not part of a captured loop.
 // The single price node of the ladder is not used: every instance's entry reads "none".
@@ -477,6 +520,12 @@ int stage_inputs(Ctx *c, Sweep &w) {
         if ((rc = stage_step_flags(c, d, d.ex, w.ex, c->ex_flag))) return rc;
     }
     if (r.barrier && (rc = stage_barrier(c, w))) return rc;
+    if (r.cliquet) {  // the payoff only where some fixing carries a weight (need_u0), packed as the state is
+        if (r.need_u0 && !r.bermudan)
+            hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src,
+                               d.d_natU0 ? d.d_natU0 : d.d_natU, ptr<double>(c->U0));
+        if ((rc = stage_cliquet(c, w))) return rc;
+    }
     if (r.american) {
         hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src,
                            d.d_natU0 ? d.d_natU0 : d.d_natU, ptr<double>(c->U0));
@@ -557,6 +606,10 @@ int small_args(Ctx *c, const Sweep &w, HadiSmallArgs &sm) {
     if (w.r.barrier) {
         sm.ko_flag = ptr<int>(c->ko_flag); sm.ko_stride = w.mon.stride;
         sm.ko_iab = ptr<int>(c->ko_iab); sm.ko_rebate = ptr<double>(c->ko_rebate);
+    }
+    if (w.r.cliquet) {
+        sm.fix_flag = ptr<int>(c->fix_flag); sm.fix_stride = w.fix.stride; sm.fix_w = w.in.fix_weights ? ptr<double>(c->fix_w) : nullptr;
+        sm.fix_iref = ptr<int>(c->fix_iref); sm.fix_mode = ptr<int>(c->fix_mode);
     }
     if (w.r.ladder) {
         sm.snap_steps = ptr<int>(c->snap_steps); sm.n_snap = d.n_snap;
@@ -730,6 +783,16 @@ int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
                                ptr<int>(c->ko_flag) + (size_t)o * w.mon.stride, w.mon.stride, ptr<int>(c->ko_iab) + 2 * (size_t)o,
                                ptr<double>(c->ko_rebate) + o, nstep);
         }
+        if (r.cliquet && w.fix.any[nstep]) {  // strike fixing behind the step's last column pass: the reference values out, then the event
+            const int bpi = hadi_exercise_bpi(L), c_stride = L.nrows_pad;
+            const int *const ff = ptr<int>(c->fix_flag) + (size_t)o * w.fix.stride, *const ir = ptr<int>(c->fix_iref) + o;
+            double *const cb = ptr<double>(c->fix_c) + (size_t)o * c_stride;
+            hipLaunchKernelGGL(hadi_fixing_gather_kernel, dim3((unsigned)(((size_t)nsb * L.nrows + 255) / 256)), dim3(256), 0, q, L, nsb, Ub, ff,
+                               w.fix.stride, ir, cb, c_stride, nstep);
+            hipLaunchKernelGGL(hadi_fixing_kernel, dim3((unsigned)nsb * bpi), dim3(HADI_EX_THREADS), 0, q, L, nsb, bpi, Ub, U0b, ff,
+                               w.in.fix_weights ? ptr<double>(c->fix_w) + (size_t)o * w.fix.stride : nullptr, w.fix.stride, ir,
+                               ptr<int>(c->fix_mode) + o, cb, c_stride, d.d_vec_s + (size_t)o * (L.m1 + 1), nstep);
+        }
         if (r.ladder && w.snap_q[nstep] >= 0 && d.n_samp > 0) {  // a sample call: n_samp interpolants where the ladder copies one node
             const size_t ns = (size_t)nsb * d.n_samp;
             hipLaunchKernelGGL(hadi_sample_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, q, L, nsb, Ub,
@@ -831,6 +894,11 @@ std::string graph_key(const Ctx *c, const Sweep &w) {
         put(ko, sizeof(ko));
         put_table(c->ko_flag, w.mon);
     }
+    if (w.r.cliquet) {  // the nodes are located again every call; the launches name them, the weights, the modes and c
+        const void *fx[] = {c->fix_iref.p, c->fix_mode.p, c->fix_c.p, w.in.fix_weights ? c->fix_w.p : nullptr};
+        put(fx, sizeof(fx));
+        put_table(c->fix_flag, w.fix);
+    }
     if (w.r.have_div) put_table(c->div_flag, w.div);  // (amounts / percentages: `own` above)
     return key;
 }
@@ -893,6 +961,9 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     Sweep w{d, route_in(c, d)};
     w.in.n_ex_steps = mark_steps(d, d.ex, w.ex);
     w.in.n_mon_steps = mark_steps(d, d.mon, w.mon);
+    w.in.n_fix_steps = mark_steps(d, d.fix, w.fix);
+    for (size_t e = 0; d.fix_weights && e < (size_t)d.fix.rows * d.fix.n_ex; e++)
+        if (d.fix.steps[e] > 0 && d.fix_weights[e] != 0.0) w.in.fix_weights = true;
     w.r = hadi_route(w.in);
     if (w.r.status == HADI_ROUTE_BAD_GRID)
         return fail(c, HADI_ERR_UNSUPPORTED, "grid %dx%d not supported (need m1 >= 2, m2 >= 3 and (m1 + 16)(m2 + 1) < 2^28)", d.m1, d.m2);
@@ -1105,6 +1176,31 @@ int check_barrier(Ctx *c, const hadi_problem *p, const hadi_barrier *b) {
     return rc;
 }
 
+// What the cliquet entry points ask beyond check_problem (which has passed).  The schedule follows the rules of ex_steps.
+static_assert(HADI_FIX_SHARES == HADI_FIXM_SHARES && HADI_FIX_RETURN == HADI_FIXM_RETURN, "hadi.h / hadi_k_fixing.h modes");
+int check_cliquet(Ctx *c, const hadi_problem *p, const hadi_cliquet *q) {
+    if (p->variant == HADI_AM || p->variant == HADI_AM_DIV)
+        return fail(c, HADI_ERR_UNSUPPORTED, "a cliquet sweep is the European sweep (HADI_EU or HADI_DIV) with fixing steps");
+    if (p->state_precision == HADI_STATE_FP32) return fail(c, HADI_ERR_UNSUPPORTED, "cliquet sweeps need the fp64 state");
+    const ExSched fix{q->n_fix, q->fix_rows, q->fix_steps};
+    const int rc = check_bermudan(c, p, fix);
+    if (rc == HADI_ERR_INVALID) c->err = "fix_steps (the rules of ex_steps): " + c->err;
+    if (rc) return rc;
+    const int n = p->n_instances;
+    if (q->n_fix > 0 && !q->ref_spot_i) return fail(c, HADI_ERR_INVALID, "ref_spot_i missing");
+    for (int k = 0; k < n; k++) {
+        const int mode = q->mode_i ? q->mode_i[k] : HADI_FIX_SHARES;
+        if (mode != HADI_FIX_SHARES && mode != HADI_FIX_RETURN) return fail(c, HADI_ERR_INVALID, "instance %d: fixing mode %d is neither 0 nor 1", k, mode);
+        if (!q->ref_spot_i) continue;
+        if (!std::isfinite(q->ref_spot_i[k])) return fail(c, HADI_ERR_INVALID, "instance %d: the reference spot is not finite", k);
+        if (mode == HADI_FIX_SHARES && q->ref_spot_i[k] <= 1e-10)
+            return fail(c, HADI_ERR_INVALID, "instance %d: HADI_FIX_SHARES needs a reference spot above 1e-10 (node 0 is the grid's 0)", k);
+    }
+    for (size_t e = 0; q->weights && e < (size_t)q->fix_rows * q->n_fix; e++)
+        if (q->fix_steps[e] > 0 && !std::isfinite(q->weights[e])) return fail(c, HADI_ERR_INVALID, "weights: entry %zu is not finite", e);
+    return HADI_OK;
+}
+
 // What a call may carry beyond the problem, as its entry point received it.  Every entry point fills the fields of its feature
 // by name and leaves the others as they are here.  A new per-call feature goes here, into check_extras and into apply_extras.
 struct CallExtras {
@@ -1113,6 +1209,7 @@ struct CallExtras {
     bool sampled = false; const hadi_samples *samples = nullptr;  // a sample entry point (NULL is not "absent": check_samples refuses it)
     bool bermudan = false; ExSched ex;                            // a Bermudan entry point, with its exercise schedule
     const hadi_barrier *barrier = nullptr;                        // a barrier entry point (each refuses NULL itself)
+    const hadi_cliquet *cliquet = nullptr;                        // a cliquet entry point (each refuses NULL itself)
     int debug = 0, debug_step = 1; double *debug_out = nullptr;   // diagnostics (hadi_debug_*): SweepDesc::debug, and where the pass's result goes
 };
 
@@ -1131,6 +1228,7 @@ int check_extras(Ctx *c, const hadi_problem *p, const CallExtras &x, const void 
     int rc;
     if (x.bermudan && (rc = check_bermudan(c, p, x.ex))) return rc;
     if (x.barrier && (rc = check_barrier(c, p, x.barrier))) return rc;
+    if (x.cliquet && (rc = check_cliquet(c, p, x.cliquet))) return rc;
     if (x.ladder && (rc = check_ladder(c, p, x.n_snap, x.snap_steps, ladder_out))) return rc;
     if (x.sampled && (rc = check_samples(c, p, x.samples))) return rc;
     return HADI_OK;
@@ -1147,6 +1245,10 @@ void apply_extras(SweepDesc &d, const CallExtras &x, const CallOut &o, const dou
     if (x.barrier && x.barrier->n_mon > 0) {
         d.mon = ExSched{x.barrier->n_mon, x.barrier->mon_rows, x.barrier->mon_steps};
         d.ko_lower = x.barrier->lower_i; d.ko_upper = x.barrier->upper_i; d.ko_rebate = x.barrier->rebate_i;
+    }
+    if (x.cliquet && x.cliquet->n_fix > 0) {
+        d.fix = ExSched{x.cliquet->n_fix, x.cliquet->fix_rows, x.cliquet->fix_steps};
+        d.fix_ref = x.cliquet->ref_spot_i; d.fix_mode = x.cliquet->mode_i; d.fix_weights = x.cliquet->weights;
     }
 }
 
@@ -1255,9 +1357,15 @@ int finish_call(Ctx *c, const SweepDesc &d, const CallOut &o, StatusKind kind, i
     if (words)
         HIP_TRY(c, hipMemcpyAsync(hs, kind == STATUS_SAMPLES ? samp_flags(c, d) : ptr<int>(c->status), words * sizeof(int),
                                   hipMemcpyDeviceToHost, c->stream));
+    // a cliquet call: the reference nodes' status words as well (pageable: n words, once per call)
+    std::vector<int> fixs(d.fix.n_ex > 0 && !d.debug ? (size_t)d.n : 0);
+    if (!fixs.empty()) HIP_TRY(c, hipMemcpyAsync(fixs.data(), fix_status(c, d), fixs.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipGetLastError());
     const int rc = finish_timing(c, d);
-    if (rc || kind == STATUS_NONE) return rc;
+    if (rc) return rc;
+    for (size_t k = 0; k < fixs.size(); k++)
+        if (fixs[k]) return fail(c, HADI_ERR_NOT_ON_GRID, "ref_spot = %.17g is not a node of instance %zu's s-grid", d.fix_ref[k % d.n_src], k % d.n_src);
+    if (kind == STATUS_NONE) return rc;
     if (kind == STATUS_SAMPLES) return samples_status(c, hs, n_count * per, d.n_samp);
     for (int k = 0; k < n_count; k++) {
         if (hs[k] && (hs[k] == 1 || kind == STATUS_NODE))
@@ -1502,7 +1610,8 @@ void release_handle(Ctx *c) {
                       &c->src_dv, &c->sel_a, &c->sel_b, &c->v0_i, &c->natU, &c->natU0, &c->natOut, &c->prices,
                       &c->status, &c->div_flag, &c->div_amt, &c->div_pct, &c->V, &c->R1, &c->C2, &c->pay_mis, &c->Uf, &c->Yf,
                       &c->order, &c->lm31, &c->team, &c->rs_tab, &c->snap_steps, &c->snap_node, &c->snap_out, &c->samp_in, &c->samp_tap, &c->samp_out, &c->ex_flag,
-                      &c->ko_flag, &c->ko_bounds, &c->ko_iab, &c->ko_rebate};
+                      &c->ko_flag, &c->ko_bounds, &c->ko_iab, &c->ko_rebate,
+                      &c->fix_flag, &c->fix_w, &c->fix_ref, &c->fix_iref, &c->fix_mode, &c->fix_c};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto &g : c->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
@@ -1856,6 +1965,32 @@ int hadi_compute_jacobian_barrier(hadi_ctx *ctx, const hadi_problem *p, double S
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && !barrier) return fail(c, HADI_ERR_INVALID, "barrier description missing");
     CallExtras x; x.barrier = barrier;
+    CallOut o; o.S_0 = S_0; o.V_0 = V_0; o.eps = eps; o.J = J; o.base_prices = base_prices;
+    return jacobian_common(c, p, x, o);
+}
+
+// ---- forward-start options and cliquets: the European sweep with strike fixings at the end of the fixing steps ----------------
+int hadi_cliquet_timestepping(hadi_ctx *ctx, const hadi_problem *p, const hadi_cliquet *cliquet) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && !cliquet) return fail(c, HADI_ERR_INVALID, "cliquet description missing");
+    CallExtras x; x.cliquet = cliquet;
+    return solve_common(c, p, x, CallOut{});
+}
+
+int hadi_compute_base_prices_cliquet(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, const hadi_cliquet *cliquet,
+                                     double *base_prices) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && (!cliquet || !base_prices)) return fail(c, HADI_ERR_INVALID, "%s missing", cliquet ? "base_prices" : "cliquet description");
+    CallExtras x; x.cliquet = cliquet;
+    CallOut o; o.rebuild_v = true; o.pick = true; o.S_0 = S_0; o.V_0 = V_0; o.prices = base_prices;
+    return solve_common(c, p, x, o);
+}
+
+int hadi_compute_jacobian_cliquet(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, const hadi_cliquet *cliquet,
+                                  double *J, double *base_prices) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && !cliquet) return fail(c, HADI_ERR_INVALID, "cliquet description missing");
+    CallExtras x; x.cliquet = cliquet;
     CallOut o; o.S_0 = S_0; o.V_0 = V_0; o.eps = eps; o.J = J; o.base_prices = base_prices;
     return jacobian_common(c, p, x, o);
 }

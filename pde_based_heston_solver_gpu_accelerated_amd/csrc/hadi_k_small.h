@@ -41,6 +41,14 @@ struct HadiSmallArgs {
     int ko_stride = 0;
     const int *ko_iab = nullptr;
     const double *ko_rebate = nullptr;
+    // Strike fixings (hadi_cliquet_timestepping; nullptr = none): at the END of step n where fix_flag[k*fix_stride + n-1] != 0
+    // (fix_stride 0 = one shared row) instance k takes U(i, j) <- a_i U(fix_iref[k], j) + w P(i, j) with w = fix_w[k*fix_stride + n-1]
+    // (nullptr: 0), a_i by fix_mode[k] (hadi_k_fixing.h); fix_iref is what hadi_fixing_locate_kernel wrote, P is HadiSweepArgs::U0
+    const int *fix_flag = nullptr;
+    int fix_stride = 0;
+    const double *fix_w = nullptr;
+    const int *fix_iref = nullptr;
+    const int *fix_mode = nullptr;
     // Sampled ladder (hadi_sample_ladder; n_samp 0 = none): on the snapshot steps above, instead of the one node, sample s of the
     // instance -- the tap record taps[inst * n_samp + s] that hadi_sample_locate_kernel wrote -- goes to
     // samp_out[(inst * n_snap + q) * n_samp + s]
@@ -251,6 +259,11 @@ __global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, Had
                 hadi_knock_lds<B>(Ul, rowp, false, sm.ko_iab[2 * inst], sm.ko_iab[2 * inst + 1], sm.ko_rebate[inst], nrows, m1, tid, NT);
                 __syncthreads();
             }
+            if (hadi_ex_listed(sm.fix_flag, sm.fix_stride, inst, n)) {  // strike fixing at the end of a fixing step (block-uniform)
+                hadi_fixing_lds<B>(Ul, rowp, false, a.U0 + (size_t)inst * a.L.inst_stride, sm.vec_s + (size_t)inst * (m1 + 1), sm.fix_iref[inst],
+                                   sm.fix_mode[inst], hadi_fix_weight(sm.fix_w, sm.fix_stride, inst, n), nrows, m1, rowp, tid, NT);
+                __syncthreads();
+            }
         }
         // maturity ladder: nothing writes U before the next barrier (the row pass reads it, a dividend copies it to Y first)
         if (n == snap.next) {
@@ -401,6 +414,11 @@ __global__ void __launch_bounds__(64) hadi_small_seq_kernel(HadiSweepArgs a, Had
             hadi_knock_lds<B>(Ul, PL, true, sm.ko_iab[2 * inst], sm.ko_iab[2 * inst + 1], sm.ko_rebate[inst], nrows, m1, lane, 64);
             __syncthreads();
         }
+        if (hadi_ex_listed(sm.fix_flag, sm.fix_stride, inst, n)) {  // strike fixing behind the knock-out's place (wave-uniform)
+            hadi_fixing_lds<B>(Ul, PL, true, a.U0 + (size_t)inst * a.L.inst_stride, sm.vec_s + (size_t)inst * (m1 + 1), sm.fix_iref[inst],
+                               sm.fix_mode[inst], hadi_fix_weight(sm.fix_w, sm.fix_stride, inst, n), nrows, m1, rowp, lane, 64);
+            __syncthreads();
+        }
         // maturity ladder: lane 0 reads the node before it stores anything of the next step (one wavefront: nobody else has yet)
         if (n == snap.next) {
             if (sm.n_samp > 0) {  // sampled ladder: every lane reads before the row sweep of the next step parks c' in U
@@ -536,6 +554,11 @@ __global__ void __launch_bounds__(64) hadi_small_seq2_kernel(HadiSweepArgs a, Ha
             }
             if (n <= Nh && hadi_ex_listed(sm.ko_flag, sm.ko_stride, ih, n)) {  // knock-out, per half as the exercise (wave-uniform)
                 hadi_knock_lds<B>(h ? base1 : base0, PL, true, sm.ko_iab[2 * ih], sm.ko_iab[2 * ih + 1], sm.ko_rebate[ih], nrows, m1, lane, 64);
+                __syncthreads();
+            }
+            if (n <= Nh && hadi_ex_listed(sm.fix_flag, sm.fix_stride, ih, n)) {  // strike fixing, per half as the knock-out (wave-uniform)
+                hadi_fixing_lds<B>(h ? base1 : base0, PL, true, a.U0 + (size_t)ih * a.L.inst_stride, sm.vec_s + (size_t)ih * (m1 + 1),
+                                   sm.fix_iref[ih], sm.fix_mode[ih], hadi_fix_weight(sm.fix_w, sm.fix_stride, ih, n), nrows, m1, rowp, lane, 64);
                 __syncthreads();
             }
         }

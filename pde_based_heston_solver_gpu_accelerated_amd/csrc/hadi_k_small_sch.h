@@ -287,6 +287,11 @@ __global__ void __launch_bounds__(64) hadi_small_sch_kernel(HadiSweepArgs a, Had
             hadi_knock_lds<B>(Ul, PL, true, sm.ko_iab[2 * inst], sm.ko_iab[2 * inst + 1], sm.ko_rebate[inst], nrows, m1, lane, 64);
             __syncthreads();
         }
+        if (hadi_ex_listed(sm.fix_flag, sm.fix_stride, inst, n)) {  // strike fixing behind the knock-out's place (wave-uniform)
+            hadi_fixing_lds<B>(Ul, PL, true, a.U0 + (size_t)inst * a.L.inst_stride, sm.vec_s + (size_t)inst * (m1 + 1), sm.fix_iref[inst],
+                               sm.fix_mode[inst], hadi_fix_weight(sm.fix_w, sm.fix_stride, inst, n), nrows, m1, rowp, lane, 64);
+            __syncthreads();
+        }
         // maturity ladder: lane 0 reads the node before it stores anything of the next step (one wavefront: nobody else has yet)
         if (n == snap.next) {
             if (sm.n_samp > 0) {  // sampled ladder: every lane reads before the row sweep of the next step parks c' in U

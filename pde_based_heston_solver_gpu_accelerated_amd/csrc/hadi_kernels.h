@@ -29,6 +29,7 @@
 #include "hadi_k_common.h"
 #include "hadi_k_bermudan.h"
 #include "hadi_k_barrier.h"
+#include "hadi_k_fixing.h"
 #include "hadi_k_row_ring.h"
 #include "hadi_k_row_strip.h"
 #include "hadi_k_col.h"

@@ -97,6 +97,8 @@ struct HadiRouteIn {
     bool team_failed = false;                 // a team could not form or a team barrier timed out once on this handle
     int n_ex_steps = 0;                       // Bermudan call: steps at whose end some instance may be exercised (0: not a Bermudan call)
     int n_mon_steps = 0;                      // barrier call: steps at whose end some instance is monitored (0: not a barrier call)
+    int n_fix_steps = 0;                      // cliquet call: steps at whose end some instance fixes its strike (0: not a cliquet call)
+    bool fix_weights = false;                 // ... and some fixing carries a non-zero weight: the packed payoff is read
     HadiHandleTuning t;
 };
 
@@ -232,6 +234,7 @@ struct HadiRoute {
     bool ladder = false, prof = false, have_div = false;
     bool bermudan = false;           // exercise steps: the whole-loop LDS kernels or the streaming kernels with hadi_exercise_kernel
     bool barrier = false;            // monitoring steps: the whole-loop LDS kernels or the streaming kernels with hadi_knockout_kernel
+    bool cliquet = false;            // fixing steps: the whole-loop LDS kernels or the streaming kernels with hadi_fixing_gather_kernel + hadi_fixing_kernel
     bool read_payoff_shape = false;  // the payoff-shape flags come back to the host: they decide `amp` (filled in by the caller)
     bool pair_tab = false;           // the pairs' coupling table is built
     bool need_u0 = false;            // the packed payoff without a lambda_bar array (a Bermudan call)
@@ -264,6 +267,9 @@ static inline HadiRoute hadi_route(const HadiRouteIn &in) {
     // A barrier call (knock-out at the end of its monitoring steps) is kept off both in the same way: hadi_knockout_kernel between
     // two steps of the streaming loop, or the knock-out inside the whole-loop LDS kernels.
     const bool barrier = r.barrier = in.n_mon_steps > 0 && !in.debug;
+    // A cliquet call (strike fixings at the end of its fixing steps) likewise: hadi_fixing_gather_kernel and hadi_fixing_kernel
+    // between two steps of the streaming loop, or the event inside the whole-loop LDS kernels.
+    const bool cliquet = r.cliquet = in.n_fix_steps > 0 && !in.debug;
     r.have_div = r.dividend && in.dividends && !in.debug;  // (diagnostics take p->U as the state the pass starts from)
     // (a caller who pins the streaming kernels' geometry -- hadi_set_tuning "strip", "row_tile", "col_groups", "strip_blocks" --
     // gets those kernels: no whole-loop kernel, resident sweep or team launch is chosen automatically)
@@ -301,7 +307,7 @@ static inline HadiRoute hadi_route(const HadiRouteIn &in) {
     // One small device-to-host copy per solve decides it.
     r.read_payoff_shape = american && t.use_amp && !cs && !takes_small_path && !in.debug && !seq_shape && !ladder;
     r.need_lam_u0 = american;
-    r.need_u0 = bermudan && !american;
+    r.need_u0 = (bermudan || (cliquet && in.fix_weights)) && !american;
     r.need_ut = r.dividend;
     r.need_f32 = f32;
     r.need_v_r1_c2 = cs && !small_sch;  // (hadi_small_sch_kernel keeps V, R1, C2 in LDS)
@@ -313,7 +319,7 @@ static inline HadiRoute hadi_route(const HadiRouteIn &in) {
     // streaming geometry; 1: wherever eligible; 0: never.
     const bool resident_shape = (t.resident_sweep > 0 || (t.resident_sweep < 0 && !pinned)) && in.scheme == HADI_SCHEME_DOUGLAS &&
                                 in.variant == HADI_EU && !f32 && hadi_resident_grid(pl, in.theta, in.rates_equal) && !in.debug &&
-                                !t.debug_fault && !prof && !ladder && !bermudan && !barrier;  // (test hooks: the streaming kernels they are for)
+                                !t.debug_fault && !prof && !ladder && !bermudan && !barrier && !cliquet;  // (test hooks: the streaming kernels they are for)
     for (const HadiSubBatch &sbt : r.bp.subs)
         r.resident.push_back(resident_shape && hadi_resident_plan(sbt.pl) && sbt.cnt <= cu &&
                              hadi_plan_row_idle(sbt.pl, sbt.cnt, cu) < HADI_TWO_STREAM_IDLE);
@@ -325,7 +331,7 @@ static inline HadiRoute hadi_route(const HadiRouteIn &in) {
     // Chosen automatically for batches of up to 8 instances on the full 256-CU device; any failure of the team protocol is
     // recorded by the kernel, checked by the caller, and the batch is solved again on the streaming path.
     const bool team = hadi_team_grid(pl, in.n, in.theta, in.rates_equal) && (in.variant == HADI_EU || in.variant == HADI_DIV) && !cs && !f32 &&
-                      !in.debug && !prof && cu == 256 && !ladder && !bermudan && !barrier && (t.team_launch > 0 || (t.team_launch < 0 && !in.team_failed && !pinned));
+                      !in.debug && !prof && cu == 256 && !ladder && !bermudan && !barrier && !cliquet && (t.team_launch > 0 || (t.team_launch < 0 && !in.team_failed && !pinned));
     r.kind = small_sch ? HADI_ROUTE_SMALL_SCH : takes_small_path ? (seq2 ? HADI_ROUTE_SMALL_SEQ2 : seq ? HADI_ROUTE_SMALL_SEQ : HADI_ROUTE_SMALL) :
              team ? HADI_ROUTE_TEAM : HADI_ROUTE_STREAMING;
     return r;
@@ -349,13 +355,15 @@ static inline std::string hadi_describe_route(const HadiRoute &r, const HadiRout
     const std::string ex_stream = r.bermudan ? "; Bermudan: hadi_exercise_kernel after each of " + std::to_string(in.n_ex_steps) + " exercise steps" : "";
     const std::string ko_loop = r.barrier ? "; barrier: knock-out at the end of " + std::to_string(in.n_mon_steps) + " steps inside the time loop" : "";
     const std::string ko_stream = r.barrier ? "; barrier: hadi_knockout_kernel after each of " + std::to_string(in.n_mon_steps) + " monitoring steps" : "";
+    const std::string fix_loop = r.cliquet ? "; cliquet: strike fixing at the end of " + std::to_string(in.n_fix_steps) + " steps inside the time loop" : "";
+    const std::string fix_stream = r.cliquet ? "; cliquet: hadi_fixing_kernel after each of " + std::to_string(in.n_fix_steps) + " fixing steps" : "";
     const std::string ladder_stream = !r.ladder ? "" : in.n_samp > 0 ? samp_words + ", hadi_sample_kernel after each snapshot step" :
                                       "; maturity ladder: " + std::to_string(in.n_snap) + " snapshots, hadi_snap_kernel after each snapshot step";
     if (r.kind == HADI_ROUTE_SMALL_SCH) {
         const int sch = hadi_route_sch(in.scheme);
         snprintf(buf, sizeof buf, "hadi_small_sch_kernel<%d,%s>: whole time loop in one launch, one wavefront per instance, predictor and corrector lines solved sequentially in LDS (%zu B)",
                  L.B, sch == HADI_SCH_MCS ? "MCS" : sch == HADI_SCH_HV ? "HV" : "CS", hadi_small_sch_smem(L));
-        return buf + ladder_loop + ex_loop + ko_loop;
+        return buf + ladder_loop + ex_loop + ko_loop + fix_loop;
     }
     if (r.kind == HADI_ROUTE_SMALL_SEQ2 || r.kind == HADI_ROUTE_SMALL_SEQ || r.kind == HADI_ROUTE_SMALL) {
         const HadiSel sel = hadi_route_small_sel(r, in.n);
@@ -366,7 +374,7 @@ static inline std::string hadi_describe_route(const HadiRoute &r, const HadiRout
         else
             snprintf(buf, sizeof buf, "hadi_small_kernel<%d,%d,%s>: whole time loop in one launch, instance resident in LDS (%zu B)", L.B,
                      sel.k ? sel.k->G : 0, r.american ? "AM" : "EU", sel.smem);
-        return buf + ladder_loop + ex_loop + ko_loop;
+        return buf + ladder_loop + ex_loop + ko_loop + fix_loop;
     }
     if (team == HADI_TEAM_RAN) {
         snprintf(buf, sizeof buf, "hadi_team_kernel<%d>: whole time loop in one launch, every instance resident in one XCD's L2 (teams of %d blocks)",
@@ -399,6 +407,7 @@ static inline std::string hadi_describe_route(const HadiRoute &r, const HadiRout
     s += ladder_stream;
     s += ex_stream;
     s += ko_stream;
+    s += fix_stream;
     if (team == HADI_TEAM_FELL_BACK) s += " (after a failed instance-resident launch)";
     return s;
 }

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as nat
-from ._native import EU, AM, DIV, AM_DIV, CALL, PUT, HadiError  # noqa: F401  (re-exported)
+from ._native import EU, AM, DIV, AM_DIV, CALL, PUT, HadiError, FIX_SHARES, FIX_RETURN  # noqa: F401  (re-exported)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -588,6 +588,74 @@ class HestonADI:
         del keep
         return J, base
 
+    # ---- forward-start options and cliquets (hadi_cliquet_timestepping and its launchers; no reference counterpart) ------
+    @classmethod
+    def _cliquet(cls, n, fixing_steps, ref_spot, mode, weights):
+        """(struct hadi_cliquet, the arrays it points into) -- host arrays [n] from scalars or sequences; the weights padded with
+        zeros as _schedule pads the steps."""
+        fix, rows, n_fix = cls._schedule(fixing_steps)
+        ref = np.ascontiguousarray(np.broadcast_to(np.asarray(ref_spot, dtype=np.float64), (n,)))
+        md = np.ascontiguousarray(np.broadcast_to(np.asarray(mode, dtype=np.int32), (n,)))
+        wt, wptr = None, None
+        if weights is not None:
+            wl = [float(weights)] * n_fix if np.isscalar(weights) else list(weights)
+            wt = np.zeros((rows, n_fix), dtype=np.float64)
+            if wl and all(np.ndim(r) == 1 for r in wl):
+                if len(wl) != rows:
+                    raise ValueError("weights: one list per schedule row")
+                for k, r in enumerate(wl):
+                    wt[k, :len(r)] = np.asarray(r, dtype=np.float64)
+            else:
+                if rows != 1 and len(wl) != n_fix:
+                    raise ValueError("weights: one list for the batch needs one schedule for the batch")
+                wt[:, :len(wl)] = np.asarray(wl, dtype=np.float64)
+            wptr = wt.ctypes.data_as(nat._dp)
+        q = nat.Cliquet(ref.ctypes.data_as(nat._dp), md.ctypes.data_as(_ip), n_fix, fix.ctypes.data_as(_ip), rows, wptr)
+        return q, [fix, ref, md, wt]
+
+    def cliquet_timestepping(self, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U, fixing_steps, ref_spot,
+                             mode=FIX_SHARES, weights=None, variant=EU, U_0=None, dividends=None, per_instance=None, scheme=0,
+                             option_type=CALL, strikes=None):
+        """DO_timestepping (variant EU or DIV) of forward-start options and cliquets: after the last pass of every step of
+        `fixing_steps` every v-row j of the instances that list it takes U(i, j) <- a_i U(i_ref, j) + w P(i, j), with i_ref the
+        node of `ref_spot`, a_i = s_i / s_ref (FIX_SHARES) or 1 (FIX_RETURN), w the weight of that fixing (weights: parallel to
+        fixing_steps, None = 0) and P the payoff U_0, or the initial U where U_0 is None.  fixing_steps: as exercise_steps of
+        bermudan_timestepping (one list, or one list per instance; fixing_steps maps calendar dates to steps).  ref_spot / mode:
+        a scalar or one value per instance.  U is updated in place."""
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U=U, U_0=U_0,
+                          dividends=dividends, per_instance=per_instance, scheme=scheme, option_type=option_type, strikes=strikes)
+        q, keep = self._cliquet(p.n_instances, fixing_steps, ref_spot, mode, weights)
+        self._call(self._lib.hadi_cliquet_timestepping, C.byref(p), C.byref(q))
+        del keep
+        return U
+
+    def compute_base_prices_cliquet(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                    num_strikes, deviceGrids, workspace, fixing_steps, ref_spot, mode=FIX_SHARES, weights=None,
+                                    variant=EU, U_0=None, dividends=None, per_instance=None, scheme=0):
+        """compute_base_prices* (the v-grid rebuilt for V_0 or per_instance['V_0_i']) of forward-start options and cliquets: [n]
+        prices at (S_0, V_0).  workspace.U is the initial condition (and the payoff where U_0 is None) and receives the field."""
+        p = self._base_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, num_strikes,
+                               deviceGrids, workspace, U_0, dividends, per_instance, scheme)
+        q, keep = self._cliquet(num_strikes, fixing_steps, ref_spot, mode, weights)
+        out, optr = self._out(num_strikes, 1, workspace.U)
+        self._call(self._lib.hadi_compute_base_prices_cliquet, C.byref(p), float(S_0), float(V_0), C.byref(q), optr)
+        del keep
+        return out
+
+    def compute_jacobian_cliquet(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                 num_strikes, deviceGrids, U_0, fixing_steps, ref_spot, mode=FIX_SHARES, weights=None, eps=1e-6,
+                                 variant=EU, dividends=None, per_instance=None, scheme=0):
+        """compute_jacobian* of forward-start options and cliquets: (J [n][5], base_prices [n]); the six solves of an instance
+        share its reference spot, mode, schedule and weights; U_0 is the initial condition and the payoff."""
+        p = self._jacobian_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, deviceGrids,
+                                   U_0, dividends, per_instance, scheme)
+        q, keep = self._cliquet(num_strikes, fixing_steps, ref_spot, mode, weights)
+        J, jptr = self._out(num_strikes, 5, U_0)
+        base, bptr = self._out(num_strikes, 1, U_0)
+        self._call(self._lib.hadi_compute_jacobian_cliquet, C.byref(p), float(S_0), float(V_0), float(eps), C.byref(q), jptr, bptr)
+        del keep
+        return J, base
+
     # ---- compute_base_prices* (src/jacobian_computation.cpp:368, 629, 922, 1232) ---------------
     def _base_prices(self, variant, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N,
                      theta, delta_t, num_strikes, deviceGrids, workspace, U_0=None, dividends=None,
@@ -740,6 +808,26 @@ def monitoring_steps(T, delta_t, dates):
     """Step indices of calendar monitoring dates of a barrier option: exercise_steps for dates in [0, T).  (A fixing at T itself
     is monitoring at maturity: knock_out_payoff.)"""
     return exercise_steps(T, delta_t, dates)
+
+
+def fixing_steps(T, delta_t, dates):
+    """Step indices of calendar fixing dates of a forward-start option or cliquet: exercise_steps for dates in [0, T)."""
+    return exercise_steps(T, delta_t, dates)
+
+
+def local_return_payoff(grids, ref_spot, strike=1.0, floor=None, cap=None):
+    """The local-return payoff of a cliquet period on the host: clamp(s / ref_spot - strike, floor, cap) on every v-row,
+    [n][(m1+1)(m2+1)].  ref_spot / strike / floor / cap: a scalar or one value per instance; None = no clamp on that side."""
+    vs = np.asarray(grids.Vec_s, dtype=np.float64)
+    n, m1p = vs.shape
+    col = lambda x: np.broadcast_to(np.asarray(x, dtype=np.float64), (n,))[:, None]
+    f = vs / col(ref_spot) - col(strike)
+    if floor is not None:
+        f = np.maximum(f, col(floor))
+    if cap is not None:
+        f = np.minimum(f, col(cap))
+    nrows = int(np.asarray(grids.Vec_v).shape[1])
+    return np.ascontiguousarray(np.broadcast_to(f[:, None, :], (n, nrows, m1p))).reshape(n, -1)
 
 
 def knock_out_payoff(grids, U, lower, upper, rebate=None):
