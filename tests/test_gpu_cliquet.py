@@ -21,6 +21,7 @@ from pde_based_heston_solver_gpu_accelerated_amd import _native as nat
 import bermudan_ref as BR
 import cliquet_ref as QR
 import common as Cm
+from fixing_cases import mixed_weights
 from test_gpu_bermudan import LAYOUTS
 
 pytestmark = pytest.mark.gpu
@@ -66,14 +67,6 @@ def batch(m1, m2, n, put=False):
     U0 = Cm.put_payoff(grids.Vec_s, strikes, m2) if put else grids.call_payoff(strikes)
     U0.setflags(write=False)
     return strikes, grids, U0
-
-
-def mixed_weights(fix):
-    """Zero and non-zero weights mixed, parallel to a schedule (one list or one list per instance)."""
-    cyc = (0.0, 1.0, 0.5, 0.0, 0.25)
-    if fix and np.ndim(fix[0]) == 1:
-        return [[cyc[(k + q) % 5] for q in range(len(r))] for k, r in enumerate(fix)]
-    return [cyc[(q + 1) % 5] for q in range(len(fix))]
 
 
 class Case:
