@@ -473,7 +473,7 @@ HADI_DEV HADI_FORCEINLINE void hadi_row_step(const HadiRowCtxT<T> &c, bool activ
             }
         } else {
             hadi_set_prio(3);
-            const double rinv0 = hadi_rcp(rb);
+            const double rinv0 = hadi_rcp_acc<(G > 1)>(rb);  // (G = 2: see hadi_rcp_acc)
             ra *= rinv0;
             rcc *= rinv0;
             rf *= rinv0;
@@ -492,7 +492,7 @@ HADI_DEV HADI_FORCEINLINE void hadi_row_step(const HadiRowCtxT<T> &c, bool activ
                     aR = hadi_lane_get(ra, dn_lane); cR = hadi_lane_get(rcc, dn_lane); fR = hadi_lane_get(rf, dn_lane);
                 }
                 const double bn = fma(-rcc, aR, fma(-ra, cL, 1.0));
-                const double rn = hadi_rcp(bn);
+                const double rn = hadi_rcp_acc<(G > 1)>(bn);
                 rf = fma(-rcc, fR, fma(-ra, fL, rf)) * rn;
                 if constexpr (G > 1) {
                     const double sL = (s == 1) ? hadi_lane_prev(rs) : hadi_lane_get(rs, up_lane);

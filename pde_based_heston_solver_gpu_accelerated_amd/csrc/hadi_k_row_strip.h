@@ -441,7 +441,7 @@ HADI_DEV HADI_FORCEINLINE void hadi_strip_step(const HadiStripCtxT<T> &c, int j,
     // ---- parallel cyclic reduction over the 64 interface unknowns (normalised rows, see hadi_row_step) ----
     {
         hadi_set_prio(3);
-        const double rinv0 = hadi_rcp(rb);
+        const double rinv0 = hadi_rcp_acc<(G > 1)>(rb);  // (G = 2: see hadi_rcp_acc)
         ra *= rinv0;
         rcc *= rinv0;
         rf *= rinv0;
@@ -460,7 +460,7 @@ HADI_DEV HADI_FORCEINLINE void hadi_strip_step(const HadiStripCtxT<T> &c, int j,
                 aR = hadi_lane_get(ra, dn_lane); cR = hadi_lane_get(rcc, dn_lane); fR = hadi_lane_get(rf, dn_lane);
             }
             const double bn = fma(-rcc, aR, fma(-ra, cL, 1.0));
-            const double rn = hadi_rcp(bn);
+            const double rn = hadi_rcp_acc<(G > 1)>(bn);
             rf = fma(-rcc, fR, fma(-ra, fL, rf)) * rn;
             if constexpr (G > 1 && !RSTAB) {  // the second right-hand side (coupling to the partner's boundary node)
                 const double sL = (s == 1) ? hadi_lane_prev(rs) : hadi_lane_get(rs, up_lane);

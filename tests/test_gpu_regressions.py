@@ -157,6 +157,37 @@ def test_gpu_sweep_seed1052_case1_tall_grid_american_lambda_bar(solver):
     assert np.abs(U - Uo).max() <= 1e-10 * np.abs(Uo).max()
 
 
+@pytest.mark.parametrize("what", ["put", "am_p", "call_R1e4"])
+@pytest.mark.parametrize("strip", [0, 1], ids=["ring", "paired_strips"])
+def test_two_wavefront_rows_with_a_tiny_interval_astride(solver, strip, what):
+    """Found by tests/test_gpu_ill_grids.py (the tiny interval PLACED between node 512, the last of wavefront 0, and node 513, the
+    first of wavefront 1, of a 600-interval row): put data, R = 1e6: libhadi 1.45e-7 of max|U| from binary128 where the fp64 oracle
+    is 3.4e-9 (43x); the American sweep at R = 1e5: 2.15e-8 against 6.3e-10 (34x); a call at R = 1e4: 2.4e-9 against 1.1e-10 (11x) --
+    on the shared ring and on paired strips alike, on the last v-rows (v = 5, where the row operator's couplings are largest),
+    smooth along s; the wave emulator, whose reciprocals are IEEE divisions, stood at 0.06 .. 1.3x.  Cause: hadi_rcp's one Newton
+    step leaves every reciprocal LOW by e^2 <= 2^-49; the cyclic reduction of a two-wavefront row hands Bc and Dd to the pair's
+    2x2 system, whose determinant 1 - Bc Dd is ~1 / R for such a pair of nodes, and the six levels' common bias is amplified by R
+    (reproduced on the CPU by giving the emulator the device's reciprocal, tests/test_emu_ill_grids.py).  Fixed by the third-order
+    step on the reduction's reciprocals of G = 2 rows (hadi_rcp_acc).  Same batches as the finding, judged by the frozen rule and
+    pinned as the adjudicated relation: the flagged instance within 10x of the yardstick."""
+    import ill_grids as I
+    import test_gpu_ill_grids as T
+    from oracle import oracle as O
+    kw = {"put": dict(put=True), "am_p": dict(variant=O.AM), "call_R1e4": {}}[what]
+    tuning = dict(T._st(strip=strip), american_p=1)
+    c = I.cfg(3, r_f=T.R_F, **kw)
+    insts, _ = T._batch(solver, tuning, 600, 40, "s", 1 if what == "call_R1e4" else 0, c)
+    U, lam, d, _ = T._sweep(solver, tuning, insts, c)
+    assert ("hadi_pass_a_strip<8," in d and "paired strips" in d) if strip else "hadi_pass_a<8,2," in d, d
+    verdicts = T._judge("600x40 %s %s" % ("paired strips" if strip else "ring", what), c, insts, U, lam)
+    k = next(i for i, x in enumerate(insts) if x.sname == "astride two wavefronts")
+    Ux, lx = I.exact(c, insts[k])
+    e_h = I.distances(U[k], None, Ux, None)[0]
+    y = I.yard(c, insts[k])[0]
+    print("astride two wavefronts: e_h %.2e, yard %.2e, ratio %.2f" % (e_h, y, e_h / y))
+    assert e_h < max(10 * y, 1e-11), (e_h, y)
+
+
 @pytest.mark.parametrize("strip", [1, 0])
 def test_rendezvous_timeout_fails_the_call(solver, strip):
     """The pair rendezvous of the two-wavefront rows (paired strips / shared ring, m1 > 512) polls a bounded number of
