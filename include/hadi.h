@@ -32,6 +32,8 @@
  *                                      on chosen steps (U <- max(U, payoff) at their end)
  *   hadi_barrier_timestepping, hadi_compute_{base_prices,jacobian}_barrier <- no counterpart: the European sweep with a knock-out
  *                                      on chosen monitoring steps (U <- rebate at or beyond a barrier, at their end)
+ *   hadi_bates_timestepping, hadi_compute_{base_prices,jacobian}_bates <- no counterpart: the European sweep under the Bates model
+ *                                      (lognormal jumps as a dense sub-step U <- U + lambda dt G U at the end of every step)
  *   hadi_make_grid / hadi_rebuild_variance <- Grid::Grid (src/grid.cpp:16-61),
  *                                      GridViews::rebuild_variance_views (src/grid_pod.hpp:25-73)
  *
@@ -532,6 +534,46 @@ int hadi_compute_base_prices_cliquet(hadi_ctx *ctx, const hadi_problem *p, doubl
                                      double *base_prices);
 int hadi_compute_jacobian_cliquet(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps,
                                   const hadi_cliquet *cliquet, double *J, double *base_prices);
+
+/* The Bates model: Heston plus compound-Poisson lognormal jumps in the spot -- NOT a reference feature.  In time to maturity
+ *     u_t = L_Heston u + lambda (E[u(s Y)] - u - kbar s u_s),   ln Y ~ N(mu, sigma^2),   kbar = exp(mu + sigma^2 / 2) - 1.
+ * A jump sweep is the sweep of hadi_DO_timestepping (variant HADI_EU or HADI_DIV, any scheme, calls and puts) with one addition:
+ * after the last pass of EVERY step n <= N_k, every v-row of instance k takes  U_row <- U_row + a_k (G U_row),  a_k = lambda_k
+ * delta_t_k.  G = J - I - kbar diag(s) D is the generator of the jump term on the instance's own s-grid, row 0 (s = 0) all zero:
+ * J[i][l] = E[phi_l(s_i Y)] for the hat functions phi_l of the piecewise-linear interpolant (the last interval's two linear
+ * pieces continued beyond s_max), D the three-point central first-derivative stencil on the non-uniform grid (the two-point
+ * backward difference at i = m1).  G annihilates constants and the function s.  The splitting is first order in time.
+ * MODELLING STATEMENT: the boundary data of the sweep stay the vanilla option's.  A dividend acts at the START of its step, the
+ * jump sub-step at its END.
+ *   lambda, mu, sigma     the jump law of every instance, unless the matching array is given
+ *   lambda_i, mu_i, sigma_i   host arrays [n] or NULL
+ *   shared_grid           the caller's promise that every instance has instance 0's s-grid: with (mu, sigma) shared too, ONE matrix
+ *                         is built and staged for the whole batch.  The promise is checked on the device (bit-equal rows of vec_s);
+ *                         a broken promise is HADI_ERR_INVALID.  0: one matrix per instance.
+ * The matrices are built on the device on every call from the sweep's own s-grids (hadi_jump_matrix_kernel); the six solves of a
+ * Jacobian row share their instance's matrix; the Jacobian keeps its five columns (kappa, eta, sigma, rho, V_0): the jump
+ * parameters are inputs.  If every a_k is 0 the call is the plain call bit for bit, on whatever route that takes; an instance
+ * with a_k = 0 inside a jump call equals its plain solve bit for bit.  A jump call runs the streaming kernels followed by
+ * hadi_jump_kernel on the fp64 matrix core: never a whole-loop LDS kernel, hadi_sweep_resident or hadi_team_kernel.
+ * hadi_bates_timestepping reads and writes p exactly as hadi_DO_timestepping does; the two launchers rebuild the v-grid and
+ * honour V_0_i as hadi_compute_base_prices / hadi_compute_jacobian do.
+ * Errors: HADI_AM / HADI_AM_DIV, HADI_STATE_FP32, a grid that takes the sequential passes (m1 > 1024 or m2 > 527):
+ * HADI_ERR_UNSUPPORTED; a NULL struct, a non-finite field, lambda < 0, sigma <= 0, lambda_k delta_t_k > 1 (the weight of the
+ * identity would turn negative), a broken shared_grid promise, a NULL output: HADI_ERR_INVALID; everything the underlying entry
+ * point refuses keeps its status. */
+typedef struct hadi_jumps {
+    double lambda, mu, sigma;                /* shared */
+    const double *lambda_i, *mu_i, *sigma_i; /* host [n] or NULL */
+    int shared_grid;                         /* caller's promise: every instance has instance 0's s-grid */
+} hadi_jumps;
+int hadi_bates_timestepping(hadi_ctx *ctx, const hadi_problem *p, const hadi_jumps *jumps);
+int hadi_compute_base_prices_bates(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, const hadi_jumps *jumps,
+                                   double *prices);
+int hadi_compute_jacobian_bates(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, const hadi_jumps *jumps,
+                                double *J, double *base_prices);
+/* diagnostics (tests): the natural-order generator G [m1 + 1][m1 + 1] of one grid, built by the kernel the sweep uses.
+ * vec_s [m1 + 1] and G_out are HOST arrays. */
+int hadi_debug_jump_matrix(hadi_ctx *ctx, int m1, const double *vec_s, double mu, double sigma, double *G_out);
 
 /* v-grid rebuilt from (V_0, V = 5.0, d = 5.0/500) exactly as every call site of the reference
  * does (jacobian_computation.cpp:253); p->vec_v / p->delta_v are ignored. */

@@ -425,6 +425,58 @@ inline void compute_jacobian_cliquet(Handle &h, double S_0, double V_0, double /
     detail::check(h, hadi_compute_jacobian_cliquet(h.ctx, &p, S_0, V_0, eps, &q, J.data(), base_prices.data()));
 }
 
+// The Bates model (hadi_bates_timestepping and its two launchers; NOT in the reference): the European or dividend sweep with the
+// lognormal-jump sub-step U <- U + lambda dt (G U) at the end of every step.  lambda / mu / sigma: the shared jump law; lambda_i /
+// mu_i / sigma_i: one value per instance, or empty = the shared value.  shared_grid: the caller's promise that every instance has
+// instance 0's s-grid (checked by the library): with a shared (mu, sigma) one matrix serves the batch.  workspace.U is the caller's
+// initial condition and receives the field.  The Jacobian keeps its five columns: the jump parameters are inputs.
+struct Jumps {
+    double lambda = 0.0, mu = 0.0, sigma = 0.1;
+    std::vector<double> lambda_i, mu_i, sigma_i;
+    bool shared_grid = false;
+    hadi_jumps view(int num_strikes) const {
+        for (const std::vector<double> *a : {&lambda_i, &mu_i, &sigma_i})
+            if (!a->empty() && a->size() != (size_t)num_strikes) throw std::runtime_error("a jump array is not [num_strikes]");
+        return hadi_jumps{lambda, mu, sigma, lambda_i.empty() ? nullptr : lambda_i.data(), mu_i.empty() ? nullptr : mu_i.data(),
+                          sigma_i.empty() ? nullptr : sigma_i.data(), shared_grid ? 1 : 0};
+    }
+};
+inline void bates_timestepping(Handle &h, int m1, int m2, int N, double delta_t, double theta, double r_d, double r_f, double rho,
+                               double sigma, double kappa, double eta, int num_strikes, const GridViews &deviceGrids,
+                               DO_Workspace &workspace, const Jumps &jumps, int variant = HADI_EU, const Dividends *div = nullptr,
+                               const PutStrikes *put = nullptr) {
+    const hadi_jumps j = jumps.view(num_strikes);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  workspace.U.data(), nullptr, div, put);
+    detail::check(h, hadi_bates_timestepping(h.ctx, &p, &j));
+}
+// ... with the v-grid rebuilt for V_0 and the price pick, as compute_base_prices does
+inline void compute_base_prices_bates(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho,
+                                      double sigma, double kappa, double eta, int m1, int m2, int /*total_size*/, int N,
+                                      double theta, double delta_t, int num_strikes, const GridViews &deviceGrids,
+                                      DO_Workspace &workspace, const Jumps &jumps, std::vector<double> &base_prices,
+                                      int variant = HADI_EU, const Dividends *div = nullptr, const PutStrikes *put = nullptr) {
+    const hadi_jumps j = jumps.view(num_strikes);
+    base_prices.resize(num_strikes);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  workspace.U.data(), nullptr, div, put);
+    detail::check(h, hadi_compute_base_prices_bates(h.ctx, &p, S_0, V_0, &j, base_prices.data()));
+}
+// J: [num_strikes][5], base_prices: [num_strikes]; the six solves of an instance share its jump law and its matrix
+inline void compute_jacobian_bates(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho,
+                                   double sigma, double kappa, double eta, int m1, int m2, int /*total_size*/, int N, double theta,
+                                   double delta_t, int num_strikes, const GridViews &deviceGrids, const std::vector<double> &U_0,
+                                   const Jumps &jumps, std::vector<double> &J, std::vector<double> &base_prices,
+                                   double eps = 1e-6, int variant = HADI_EU, const Dividends *div = nullptr,
+                                   const PutStrikes *put = nullptr) {
+    const hadi_jumps j = jumps.view(num_strikes);
+    J.resize((size_t)num_strikes * 5);
+    base_prices.resize(num_strikes);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  nullptr, U_0.data(), div, put);
+    detail::check(h, hadi_compute_jacobian_bates(h.ctx, &p, S_0, V_0, eps, &j, J.data(), base_prices.data()));
+}
+
 // jacobian_computation.cpp:204-364 and the three variants.  J: [num_strikes][5], columns kappa, eta, sigma, rho, v0.
 inline void compute_jacobian(Handle &h, double S_0, double V_0, double, double r_d, double r_f, double rho, double sigma,
                              double kappa, double eta, int m1, int m2, int, int N, double theta, double delta_t,

@@ -64,6 +64,12 @@ class Cliquet(C.Structure):
     _fields_ = [("ref_spot_i", _dp), ("mode_i", _ip), ("n_fix", C.c_int), ("fix_steps", _ip), ("fix_rows", C.c_int), ("weights", _dp)]
 
 
+class Jumps(C.Structure):
+    """struct hadi_jumps (include/hadi.h)."""
+    _fields_ = [("lam", C.c_double), ("mu", C.c_double), ("sigma", C.c_double), ("lambda_i", _dp), ("mu_i", _dp), ("sigma_i", _dp),
+                ("shared_grid", C.c_int)]
+
+
 class Samples(C.Structure):
     """struct hadi_samples (include/hadi.h)."""
     _fields_ = [("n_samp", C.c_int), ("spots", _dp), ("scales", _dp), ("rows", C.c_int)]
@@ -91,6 +97,7 @@ EXPORTS = [
     "hadi_bermudan_timestepping", "hadi_compute_base_prices_bermudan", "hadi_compute_jacobian_bermudan",
     "hadi_barrier_timestepping", "hadi_compute_base_prices_barrier", "hadi_compute_jacobian_barrier",
     "hadi_cliquet_timestepping", "hadi_compute_base_prices_cliquet", "hadi_compute_jacobian_cliquet",
+    "hadi_bates_timestepping", "hadi_compute_base_prices_bates", "hadi_compute_jacobian_bates", "hadi_debug_jump_matrix",
     "hadi_compute_base_prices", "hadi_compute_base_prices_american",
     "hadi_compute_base_prices_dividends", "hadi_compute_base_prices_american_dividends",
     "hadi_compute_jacobian", "hadi_compute_jacobian_american",
@@ -179,6 +186,13 @@ def _load(LIB_PATH):
         L.hadi_compute_base_prices_cliquet.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, _cp, C.c_void_p]
         L.hadi_compute_jacobian_cliquet.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_double, _cp, C.c_void_p,
                                                     C.c_void_p]
+    if hasattr(L, "hadi_bates_timestepping"):  # (likewise: a build from before the Bates entry points)
+        _jp = C.POINTER(Jumps)
+        L.hadi_bates_timestepping.argtypes = [C.c_void_p, C.POINTER(Problem), _jp]
+        L.hadi_compute_base_prices_bates.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, _jp, C.c_void_p]
+        L.hadi_compute_jacobian_bates.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_double, _jp, C.c_void_p,
+                                                  C.c_void_p]
+        L.hadi_debug_jump_matrix.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, C.c_double, _dp]
     if hasattr(L, "hadi_sample_ladder"):  # (likewise: a build from before the sampled ladder)
         _sp = C.POINTER(Samples)
         for name in ("hadi_sample_ladder", "hadi_compute_base_prices_samples"):

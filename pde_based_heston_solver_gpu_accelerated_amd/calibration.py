@@ -410,6 +410,43 @@ def calibrate_bermudan(solver, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1
                      dividends=dividends, max_iter=max_iter, tol=tol, scheme=scheme, launchers=launch, **kw)
 
 
+def _bates_launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, jumps, grids, U_0, dividends, scheme=0):
+    """The closures of calibrate() over the Bates launchers: one instance per strike, the jump parameters held fixed."""
+    n_loc = grids.Vec_s.shape[0]
+    total_size = (m1 + 1) * (m2 + 1)
+    delta_t = T / N
+    kw = {"variant": variant, "dividends": dividends}
+    if scheme:
+        kw["scheme"] = scheme
+
+    def jac(k, e, s, r, v, eps):
+        return solver.compute_jacobian_bates(S_0, v, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t, n_loc, grids,
+                                             U_0, *jumps, eps=eps, **kw)
+
+    def base(k, e, s, r, v):
+        ws = _WS()
+        ws.U = _clone(U_0)
+        return solver.compute_base_prices_bates(S_0, v, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t, n_loc,
+                                                grids, ws, *jumps, **kw)
+
+    return jac, base
+
+
+def calibrate_bates(solver, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0, market_prices,
+                    jump_intensity, jump_mean, jump_vol, shared_grid=False, dividends=None, max_iter=15, tol=0.1, scheme=0, **kw):
+    """calibrate_european / calibrate_dividends under the Bates model: every Jacobian and trial-price solve is the European sweep
+    (with `dividends`: the dividend sweep) with the lognormal-jump sub-step at the end of every step.  The five Heston parameters
+    are fitted; the jump parameters (a scalar or one value per strike each) are inputs and stay fixed.  shared_grid: see
+    HestonADI.bates_timestepping.  scheme / theta: see calibrate (without dividends only)."""
+    variant = DIV if dividends is not None and len(dividends) else EU
+    if scheme and variant != EU:
+        raise ValueError("scheme %r: the predictor-corrector schemes price European sweeps only" % (scheme,))
+    launch = _bates_launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, (jump_intensity, jump_mean, jump_vol, shared_grid),
+                              grids, U_0, dividends if variant == DIV else None, scheme=scheme)
+    return calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0, market_prices,
+                     dividends=dividends, max_iter=max_iter, tol=tol, scheme=scheme, launchers=launch, **kw)
+
+
 def calibrate_american_dividends_multi_maturity(solver, S_0, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, theta,
                                                 calibration_points, grids, U_0, market_prices, dividends, max_iter=20,
                                                 tol=0.1, **kw):

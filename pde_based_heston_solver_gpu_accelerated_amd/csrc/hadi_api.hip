@@ -67,6 +67,9 @@ struct Ctx {
     // spots [n], their nodes [n] with the status words [n] behind them (hadi_fixing_locate_kernel), the modes [n] and the gathered
     // reference values c [n][nrows_pad] of the streaming path (hadi_fixing_gather_kernel)
     DevBuf fix_flag, fix_w, fix_ref, fix_iref, fix_mode, fix_c;
+    // lognormal jumps (Bates calls): the generators in operand order [n_mat][hadi_jump_matrix_doubles] (hadi_jump_matrix_kernel), the
+    // weights a_k = lambda_k dt_k [n], the (mu, sigma) pairs of the matrices [n_mat][2], the status word of the shared-grid promise
+    DevBuf jmp_G, jmp_a, jmp_par, jmp_stat;
     DevBuf snap_steps, snap_node, snap_out;  // maturity ladder: the snapshot steps, the instances' price nodes, the snapshots [n][n_snap]
     // sampled ladder: the spots [n][n_samp] and behind them the scales [n][n_samp] as staged; the tap records [n][n_samp] and behind
     // them the samples' flag words [n][n_samp] (hadi_sample_locate_kernel); the samples [n][n_snap][n_samp]
@@ -261,6 +264,13 @@ struct SweepDesc {
     ExSched fix;
     const double *fix_ref = nullptr, *fix_weights = nullptr;
     const int *fix_mode = nullptr;
+    // Lognormal jumps (hadi_bates_timestepping and its launchers): jmp_a non-empty = [n] weights a_k = lambda_k dt_k of the sub-step
+    // at the end of every step, some of them non-zero (a call whose weights are all zero carries none: it is the plain call);
+    // jmp_musig: [jmp_nmat][2], the (mu, sigma) of the matrices -- one per source instance (instance k uses matrix k % n_src), or
+    // ONE for the batch with jmp_shared (the caller's promise of a shared s-grid, checked on the device).
+    std::vector<double> jmp_a, jmp_musig;
+    int jmp_nmat = 0;
+    bool jmp_shared = false;
 };
 
 // Kernels whose dynamic LDS can exceed the 64 KiB default need the limit raised once (hadi_create: every kernel of
@@ -301,6 +311,7 @@ HadiRouteIn route_in(const Ctx *c, const SweepDesc &d) {
     in.theta = d.theta; in.rates_equal = d.r_d == d.r_f;
     in.debug = d.debug; in.profiling = c->profiling != 0; in.n_snap = d.n_snap; in.n_samp = d.n_samp; in.dividends = d.num_div > 0;
     in.uniform_steps = d.uniform_steps; in.team_failed = c->team_failed != 0; in.t = c->t;
+    in.jumps = !d.jmp_a.empty();
     return in;
 }
 
@@ -337,6 +348,9 @@ int grow_buffers(Ctx *c, Sweep &w) {
     if (r.cliquet && ((rc = ensure(c, c->fix_flag, w.fix.bytes(d))) || (rc = ensure(c, c->fix_w, 2 * w.fix.bytes(d))) ||
                       (rc = ensure(c, c->fix_ref, 8 * n)) || (rc = ensure(c, c->fix_iref, 2 * sizeof(int) * n)) ||
                       (rc = ensure(c, c->fix_mode, sizeof(int) * n)) || (rc = ensure(c, c->fix_c, 8 * n * pl.L.nrows_pad))))
+        return rc;
+    if (r.jumps && ((rc = ensure(c, c->jmp_G, 8 * (size_t)d.jmp_nmat * hadi_jump_matrix_doubles(pl.L))) || (rc = ensure(c, c->jmp_a, 8 * n)) ||
+                    (rc = ensure(c, c->jmp_par, 16 * (size_t)d.jmp_nmat)) || (rc = ensure(c, c->jmp_stat, sizeof(int)))))
         return rc;
     if (r.need_ut && (rc = ensure(c, c->UT, st))) return rc;
     if (r.need_f32 && ((rc = ensure(c, c->Uf, st / 2)) || (rc = ensure(c, c->Yf, st / 2)))) return rc;
@@ -454,6 +468,28 @@ int stage_cliquet(Ctx *c, const Sweep &w) {
     return HADI_OK;
 }
 
+// Bates: the weights a_k and the matrices' (mu, sigma) to the device, then the generators from the sweep's own device s-grids
+// (hadi_jump_matrix_kernel into the zeroed buffer) and, for a shared matrix, the check of the caller's promise -- on every call,
+// also before a replay: the matrices are data, not part of a captured loop.
+int stage_jumps(Ctx *c, const Sweep &w) {
+    const SweepDesc &d = w.d;
+    const HadiLayout &L = w.r.pl.L;
+    hipStream_t s = c->stream;
+    int rc;
+    if ((rc = stage_to_device(c, c->jmp_a.p, d.jmp_a.data(), d.jmp_a.size() * 8)) ||
+        (rc = stage_to_device(c, c->jmp_par.p, d.jmp_musig.data(), d.jmp_musig.size() * 8)))
+        return rc;
+    const size_t gd = (size_t)d.jmp_nmat * hadi_jump_matrix_doubles(L), ne = (size_t)d.jmp_nmat * (L.m1 + 1) * (L.m1 + 1);
+    HIP_TRY(c, hipMemsetAsync(c->jmp_G.p, 0, gd * 8, s));
+    HIP_TRY(c, hipMemsetAsync(c->jmp_stat.p, 0, sizeof(int), s));
+    hipLaunchKernelGGL(hadi_jump_matrix_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, L, d.jmp_nmat, d.d_vec_s,
+                       ptr<double>(c->jmp_par), ptr<double>(c->jmp_G));
+    if (d.jmp_shared)
+        hipLaunchKernelGGL(hadi_jump_grid_check_kernel, dim3((unsigned)(((size_t)d.n * (L.m1 + 1) + 255) / 256)), dim3(256), 0, s, L.m1 + 1,
+                           d.n, d.d_vec_s, ptr<int>(c->jmp_stat));
+    return HADI_OK;
+}
+
 // Sampled ladder: the lists of all n instances to the device, then the tap records and flag words from the sweep's own device
 // grids (hadi_sample_locate_kernel) -- on every call, also before a replay: the taps are data, not part of a captured loop.
 // The single price node of the ladder is not used: every instance's entry reads "none".
@@ -526,6 +562,7 @@ int stage_inputs(Ctx *c, Sweep &w) {
                                d.d_natU0 ? d.d_natU0 : d.d_natU, ptr<double>(c->U0));
         if ((rc = stage_cliquet(c, w))) return rc;
     }
+    if (r.jumps && (rc = stage_jumps(c, w))) return rc;
     if (r.american) {
         hipLaunchKernelGGL(hadi_pack_kernel, dim3(grid1d(tot)), dim3(256), 0, s, L, d.n, d.n_src,
                            d.d_natU0 ? d.d_natU0 : d.d_natU, ptr<double>(c->U0));
@@ -711,6 +748,13 @@ HadiSweepArgs sub_args(const Sweep &w, HadiSweepArgs x, int o, int cnt, const Ha
     return x;
 }
 
+// Instances that ride on one staged strip of a SHARED jump matrix: as many as still leave two blocks per CU, at most 8.  With
+// per-instance matrices every block has one instance.  (Which instances share a block never changes an instance's result.)
+int jump_ipg(const Ctx *c, const SweepDesc &d, const HadiLayout &L, int nsb) {
+    if (!d.jmp_shared) return 1;
+    return (int)std::max(1ll, std::min(8ll, (long long)nsb * hadi_jump_nib(L) / (2ll * c->cu_count)));
+}
+
 // Sub-batch `sb` through its whole time loop on stream q.
 int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
     const SweepDesc &d = w.d;
@@ -725,7 +769,7 @@ int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
     const HadiSweepArgs a = sub_args(w, w.a, o, nsb, sp), av = sub_args(w, w.av, o, nsb, sp);
     const size_t tot = (size_t)L.inst_stride * nsb, st = tot * sizeof(double);  // the sub-batch's packed state
     double *const Ub = ptr<double>(c->U) + so, *const LAMb = r.american ? ptr<double>(c->LAM) + so : nullptr;
-    double *const U0b = (r.american || r.need_u0) ? ptr<double>(c->U0) + so : nullptr, *const UTb = r.dividend ? ptr<double>(c->UT) + so : nullptr;
+    double *const U0b = (r.american || r.need_u0) ? ptr<double>(c->U0) + so : nullptr, *const UTb = r.need_ut ? ptr<double>(c->UT) + so : nullptr;
     const int ev0 = 4 * sb * d.Nmax;  // profiling events of this sub-batch
     int rc;
     if (r.pair_tab && sp.use_strip) {  // paired strips: the pairs' coupling column, once per solve (hadi_strip_step, RSTAB)
@@ -771,6 +815,13 @@ int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
         if (kev) HIP_TRY(c, hipEventRecord(kev[3], q));
         if (cs) {  // corrector (profiling events cover the predictor's two passes only)
             if ((rc = launch_pass(c, hadi_select_row_pass(pc, 2), q, av, nstep)) || (rc = launch_pass(c, col, q, a, nstep))) return rc;
+        }
+        if (r.jumps) {  // Bates: U_temp <- U, U <- U_temp + a G U_temp behind the step's last column pass, in front of the step's events
+            HIP_TRY(c, hipMemcpyAsync(UTb, Ub, st, hipMemcpyDeviceToDevice, q));
+            const int ipg = jump_ipg(c, d, L, nsb);
+            hipLaunchKernelGGL(hadi_jump_kernel, dim3(hadi_jump_grid(L, nsb, ipg)), dim3(HADI_JUMP_THREADS), hadi_jump_smem(L), q, L, nsb, ipg,
+                               o, d.n_src, UTb, Ub, ptr<double>(c->jmp_G), d.jmp_shared ? 0ll : (long long)hadi_jump_matrix_doubles(L),
+                               ptr<double>(c->jmp_a) + o, a.ipar, nstep);
         }
         if (r.bermudan && w.ex.any[nstep]) {  // Bermudan exercise behind the step's last column pass (European sweeps: U is explicit)
             const int bpi = hadi_exercise_bpi(L);
@@ -899,6 +950,13 @@ std::string graph_key(const Ctx *c, const Sweep &w) {
         put(fx, sizeof(fx));
         put_table(c->fix_flag, w.fix);
     }
+    if (w.r.jumps) {  // the matrices and the weights are built again every call; the launches name their addresses (U_temp: `own`
+                      // above), the matrix stride (0: shared), the source count and the instances per block
+        const void *jm[] = {c->jmp_G.p, c->jmp_a.p};
+        const int ji[] = {(int)d.jmp_shared, d.n_src, c->cu_count};
+        put(jm, sizeof(jm));
+        put(ji, sizeof(ji));
+    }
     if (w.r.have_div) put_table(c->div_flag, w.div);  // (amounts / percentages: `own` above)
     return key;
 }
@@ -970,6 +1028,8 @@ int run_sweep(Ctx *c, const SweepDesc &d, HadiPlan &pl) {
     if (w.r.status == HADI_ROUTE_SEQ_UNSUPPORTED)
         return fail(c, HADI_ERR_UNSUPPORTED, "grids with m1 > 1024 or m2 > %d run Douglas sweeps with the fp64 state only", HADI_MAX_P * HADI_LC - 1);
     if (w.r.status) return fail(c, HADI_ERR_UNSUPPORTED, "plan failed");
+    if (w.r.jumps && w.r.seq_shape)
+        return fail(c, HADI_ERR_UNSUPPORTED, "jump sweeps run the streaming kernels: grids with m1 > 1024 or m2 > %d take the sequential passes", HADI_MAX_P * HADI_LC - 1);
     pl = w.r.pl;
     w.tot = (size_t)pl.L.inst_stride * d.n;
     w.st = w.tot * sizeof(double);
@@ -1201,6 +1261,23 @@ int check_cliquet(Ctx *c, const hadi_problem *p, const hadi_cliquet *q) {
     return HADI_OK;
 }
 
+// What the Bates entry points ask beyond check_problem (which has passed).
+int check_jumps(Ctx *c, const hadi_problem *p, const hadi_jumps *j) {
+    if (p->variant == HADI_AM || p->variant == HADI_AM_DIV)
+        return fail(c, HADI_ERR_UNSUPPORTED, "a jump sweep is the European sweep (HADI_EU or HADI_DIV) with a jump sub-step");
+    if (p->state_precision == HADI_STATE_FP32) return fail(c, HADI_ERR_UNSUPPORTED, "jump sweeps need the fp64 state");
+    for (int k = 0; k < p->n_instances; k++) {
+        const double lam = j->lambda_i ? j->lambda_i[k] : j->lambda, mu = j->mu_i ? j->mu_i[k] : j->mu, sg = j->sigma_i ? j->sigma_i[k] : j->sigma;
+        const double dt = p->delta_t_i ? p->delta_t_i[k] : p->delta_t;
+        if (!std::isfinite(lam) || !std::isfinite(mu) || !std::isfinite(sg)) return fail(c, HADI_ERR_INVALID, "instance %d: a jump parameter is not finite", k);
+        if (lam < 0.0) return fail(c, HADI_ERR_INVALID, "instance %d: jump intensity %g is negative", k, lam);
+        if (!(sg > 0.0)) return fail(c, HADI_ERR_INVALID, "instance %d: jump volatility %g is not positive", k, sg);
+        if (lam * dt > 1.0)
+            return fail(c, HADI_ERR_INVALID, "instance %d: lambda delta_t = %g exceeds 1 (the weight of the identity in the jump sub-step would turn negative)", k, lam * dt);
+    }
+    return HADI_OK;
+}
+
 // What a call may carry beyond the problem, as its entry point received it.  Every entry point fills the fields of its feature
 // by name and leaves the others as they are here.  A new per-call feature goes here, into check_extras and into apply_extras.
 struct CallExtras {
@@ -1210,6 +1287,7 @@ struct CallExtras {
     bool bermudan = false; ExSched ex;                            // a Bermudan entry point, with its exercise schedule
     const hadi_barrier *barrier = nullptr;                        // a barrier entry point (each refuses NULL itself)
     const hadi_cliquet *cliquet = nullptr;                        // a cliquet entry point (each refuses NULL itself)
+    const hadi_jumps *jumps = nullptr;                            // a Bates entry point (each refuses NULL itself)
     int debug = 0, debug_step = 1; double *debug_out = nullptr;   // diagnostics (hadi_debug_*): SweepDesc::debug, and where the pass's result goes
 };
 
@@ -1229,6 +1307,7 @@ int check_extras(Ctx *c, const hadi_problem *p, const CallExtras &x, const void 
     if (x.bermudan && (rc = check_bermudan(c, p, x.ex))) return rc;
     if (x.barrier && (rc = check_barrier(c, p, x.barrier))) return rc;
     if (x.cliquet && (rc = check_cliquet(c, p, x.cliquet))) return rc;
+    if (x.jumps && (rc = check_jumps(c, p, x.jumps))) return rc;
     if (x.ladder && (rc = check_ladder(c, p, x.n_snap, x.snap_steps, ladder_out))) return rc;
     if (x.sampled && (rc = check_samples(c, p, x.samples))) return rc;
     return HADI_OK;
@@ -1249,6 +1328,24 @@ void apply_extras(SweepDesc &d, const CallExtras &x, const CallOut &o, const dou
     if (x.cliquet && x.cliquet->n_fix > 0) {
         d.fix = ExSched{x.cliquet->n_fix, x.cliquet->fix_rows, x.cliquet->fix_steps};
         d.fix_ref = x.cliquet->ref_spot_i; d.fix_mode = x.cliquet->mode_i; d.fix_weights = x.cliquet->weights;
+    }
+    if (x.jumps) {  // (fill_desc has run: the rows of par8 hold every instance's delta_t)
+        const hadi_jumps &j = *x.jumps;
+        std::vector<double> a(d.n);
+        bool any = false;
+        for (int k = 0; k < d.n; k++) {
+            a[k] = (j.lambda_i ? j.lambda_i[k % d.n_src] : j.lambda) * d.par8[(size_t)k * 8 + 4];
+            any = any || a[k] != 0.0;
+        }
+        if (any) {  // (all weights zero: the plain call, bit for bit, on whatever route it takes)
+            d.jmp_a = a;
+            d.jmp_shared = j.shared_grid && !j.mu_i && !j.sigma_i;
+            d.jmp_nmat = d.jmp_shared ? 1 : d.n_src;
+            for (int q = 0; q < d.jmp_nmat; q++) {
+                d.jmp_musig.push_back(j.mu_i ? j.mu_i[q] : j.mu);
+                d.jmp_musig.push_back(j.sigma_i ? j.sigma_i[q] : j.sigma);
+            }
+        }
     }
 }
 
@@ -1360,9 +1457,13 @@ int finish_call(Ctx *c, const SweepDesc &d, const CallOut &o, StatusKind kind, i
     // a cliquet call: the reference nodes' status words as well (pageable: n words, once per call)
     std::vector<int> fixs(d.fix.n_ex > 0 && !d.debug ? (size_t)d.n : 0);
     if (!fixs.empty()) HIP_TRY(c, hipMemcpyAsync(fixs.data(), fix_status(c, d), fixs.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    // a Bates call with a shared matrix: the word of the caller's promise (pageable: one word, once per call)
+    int jstat = 0;
+    if (d.jmp_shared && !d.debug) HIP_TRY(c, hipMemcpyAsync(&jstat, c->jmp_stat.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipGetLastError());
     const int rc = finish_timing(c, d);
     if (rc) return rc;
+    if (jstat) return fail(c, HADI_ERR_INVALID, "shared_grid is set, but not every instance has instance 0's s-grid");
     for (size_t k = 0; k < fixs.size(); k++)
         if (fixs[k]) return fail(c, HADI_ERR_NOT_ON_GRID, "ref_spot = %.17g is not a node of instance %zu's s-grid", d.fix_ref[k % d.n_src], k % d.n_src);
     if (kind == STATUS_NONE) return rc;
@@ -1610,7 +1711,7 @@ void release_handle(Ctx *c) {
                       &c->src_dv, &c->sel_a, &c->sel_b, &c->v0_i, &c->natU, &c->natU0, &c->natOut, &c->prices,
                       &c->status, &c->div_flag, &c->div_amt, &c->div_pct, &c->V, &c->R1, &c->C2, &c->pay_mis, &c->Uf, &c->Yf,
                       &c->order, &c->lm31, &c->team, &c->rs_tab, &c->snap_steps, &c->snap_node, &c->snap_out, &c->samp_in, &c->samp_tap, &c->samp_out, &c->ex_flag,
-                      &c->ko_flag, &c->ko_bounds, &c->ko_iab, &c->ko_rebate,
+                      &c->ko_flag, &c->ko_bounds, &c->ko_iab, &c->ko_rebate, &c->jmp_G, &c->jmp_a, &c->jmp_par, &c->jmp_stat,
                       &c->fix_flag, &c->fix_w, &c->fix_ref, &c->fix_iref, &c->fix_mode, &c->fix_c};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
@@ -1690,6 +1791,7 @@ int hadi_create(hadi_ctx **out, int device_id) {
     ok = ok && hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->join_ev, hipEventDisableTiming) == hipSuccess;
     hadi_for_each_kernel([&](auto kernel) { ok = ok && raise_lds_limit(kernel) == hipSuccess; });
+    ok = ok && raise_lds_limit(hadi_jump_kernel) == hipSuccess;  // (its strip of G: 66 KiB at m1 = 512, 132 KiB at m1 = 1024)
     for (auto &e : c->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->wait_ev, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipHostMalloc(reinterpret_cast<void **>(&c->err_host), 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
@@ -1941,6 +2043,63 @@ int hadi_compute_jacobian_bermudan(hadi_ctx *ctx, const hadi_problem *p, double 
     CallExtras x; x.bermudan = true; x.ex.n_ex = n_ex; x.ex.rows = ex_rows; x.ex.steps = ex_steps;
     CallOut o; o.S_0 = S_0; o.V_0 = V_0; o.eps = eps; o.J = J; o.base_prices = base_prices;
     return jacobian_common(reinterpret_cast<Ctx *>(ctx), p, x, o);
+}
+
+// ---- Bates: the European sweep with the jump sub-step U <- U + lambda dt G U at the end of every step ------------------------
+int hadi_bates_timestepping(hadi_ctx *ctx, const hadi_problem *p, const hadi_jumps *jumps) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && !jumps) return fail(c, HADI_ERR_INVALID, "jump description missing");
+    CallExtras x; x.jumps = jumps;
+    return solve_common(c, p, x, CallOut{});
+}
+
+int hadi_compute_base_prices_bates(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, const hadi_jumps *jumps, double *prices) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && (!jumps || !prices)) return fail(c, HADI_ERR_INVALID, "%s missing", jumps ? "prices" : "jump description");
+    CallExtras x; x.jumps = jumps;
+    CallOut o; o.rebuild_v = true; o.pick = true; o.S_0 = S_0; o.V_0 = V_0; o.prices = prices;
+    return solve_common(c, p, x, o);
+}
+
+int hadi_compute_jacobian_bates(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, const hadi_jumps *jumps,
+                                double *J, double *base_prices) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && !jumps) return fail(c, HADI_ERR_INVALID, "jump description missing");
+    CallExtras x; x.jumps = jumps;
+    CallOut o; o.S_0 = S_0; o.V_0 = V_0; o.eps = eps; o.J = J; o.base_prices = base_prices;
+    return jacobian_common(c, p, x, o);
+}
+
+// The generator of one grid in natural order, through the kernels the sweep uses (host arrays in and out).
+int hadi_debug_jump_matrix(hadi_ctx *ctx, int m1, const double *vec_s, double mu, double sigma, double *G_out) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c) return HADI_ERR_INVALID;
+    if (!vec_s || !G_out) return fail(c, HADI_ERR_INVALID, "%s missing", vec_s ? "G_out" : "vec_s");
+    if (!std::isfinite(mu) || !std::isfinite(sigma) || !(sigma > 0.0)) return fail(c, HADI_ERR_INVALID, "jump law (%g, %g) is not admissible", mu, sigma);
+    HadiPlan pl;
+    if (hadi_make_plan(m1, 8, 1, 8 * c->cu_count, &pl, c->t.tune, 8) || pl.row_seq)
+        return fail(c, HADI_ERR_UNSUPPORTED, "no streaming layout for m1 = %d", m1);
+    DeviceGuard guard(c->device);
+    pin_rewind(c);
+    const HadiLayout &L = pl.L;
+    const size_t m1p = (size_t)m1 + 1, gd = hadi_jump_matrix_doubles(L);
+    const double ms[2] = {mu, sigma};
+    int rc;
+    if ((rc = ensure(c, c->g_s, m1p * 8)) || (rc = ensure(c, c->jmp_G, gd * 8)) || (rc = ensure(c, c->jmp_par, 16)) ||
+        (rc = ensure(c, c->natOut, m1p * m1p * 8)))
+        return rc;
+    if ((rc = stage_to_device(c, c->g_s.p, vec_s, m1p * 8)) || (rc = stage_to_device(c, c->jmp_par.p, ms, 16))) return rc;
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemsetAsync(c->jmp_G.p, 0, gd * 8, s));
+    hipLaunchKernelGGL(hadi_jump_matrix_kernel, dim3((unsigned)((m1p * m1p + 255) / 256)), dim3(256), 0, s, L, 1, ptr<double>(c->g_s),
+                       ptr<double>(c->jmp_par), ptr<double>(c->jmp_G));
+    hipLaunchKernelGGL(hadi_jump_matrix_unpack_kernel, dim3((unsigned)((m1p * m1p + 255) / 256)), dim3(256), 0, s, L, ptr<double>(c->jmp_G),
+                       ptr<double>(c->natOut));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(G_out, c->natOut.p, m1p * m1p * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    c->pin_dirty = 0;
+    return HADI_OK;
 }
 
 // ---- knock-out barrier: the European sweep with U <- rebate beyond the barriers at the end of the monitoring steps ----------

@@ -85,12 +85,19 @@ HADI_DEV HADI_FORCEINLINE void hadi_pb_load(const HadiPassBCtx &c, int ctile, do
 // tools/mfma_probe.hip: lane 16 k + i holds A[i][k], lane 16 k + j holds B[k][j]; register r of lane 16 q + j holds D[4 r + q][j].
 HADI_DEV HADI_FORCEINLINE void hadi_mfma_f64_16x16x4(double a, double b, double (&acc)[4]) {
 #if defined(HADI_EMU)
+    // (the lanes of a wavefront are fibers of one thread: both operands are published once and read between two rendezvous,
+    // where twenty shuffles cost forty -- the dense product of hadi_jump_kernel issues hundreds of these per tile)
+    static thread_local double img[2][64];
     const int q = emu::t_lane >> 4, j = emu::t_lane & 15;
+    img[0][emu::t_lane] = a;
+    img[1][emu::t_lane] = b;
+    emu::wave_barrier();
     double av[4][4], bv[4];
     for (int k = 0; k < 4; k++) {
-        bv[k] = __shfl(b, 16 * k + j);
-        for (int r = 0; r < 4; r++) av[r][k] = __shfl(a, 16 * k + 4 * r + q);
+        bv[k] = img[1][16 * k + j];
+        for (int r = 0; r < 4; r++) av[r][k] = img[0][16 * k + 4 * r + q];
     }
+    emu::wave_barrier();
     for (int r = 0; r < 4; r++)
         for (int k = 0; k < 4; k++) acc[r] = fma(av[r][k], bv[k], acc[r]);
 #else

@@ -33,6 +33,7 @@
 #include "hadi_k_row_ring.h"
 #include "hadi_k_row_strip.h"
 #include "hadi_k_col.h"
+#include "hadi_k_jumps.h"
 #include "hadi_k_team.h"
 #include "hadi_k_resident.h"
 #include "hadi_k_lds_seq.h"

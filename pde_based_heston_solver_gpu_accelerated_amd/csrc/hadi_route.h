@@ -99,6 +99,7 @@ struct HadiRouteIn {
     int n_mon_steps = 0;                      // barrier call: steps at whose end some instance is monitored (0: not a barrier call)
     int n_fix_steps = 0;                      // cliquet call: steps at whose end some instance fixes its strike (0: not a cliquet call)
     bool fix_weights = false;                 // ... and some fixing carries a non-zero weight: the packed payoff is read
+    bool jumps = false;                       // Bates call with some a_k = lambda_k dt_k != 0: hadi_jump_kernel at the end of every step
     HadiHandleTuning t;
 };
 
@@ -235,6 +236,7 @@ struct HadiRoute {
     bool bermudan = false;           // exercise steps: the whole-loop LDS kernels or the streaming kernels with hadi_exercise_kernel
     bool barrier = false;            // monitoring steps: the whole-loop LDS kernels or the streaming kernels with hadi_knockout_kernel
     bool cliquet = false;            // fixing steps: the whole-loop LDS kernels or the streaming kernels with hadi_fixing_gather_kernel + hadi_fixing_kernel
+    bool jumps = false;              // lognormal jumps: the streaming kernels with hadi_jump_kernel behind every step's last column pass
     bool read_payoff_shape = false;  // the payoff-shape flags come back to the host: they decide `amp` (filled in by the caller)
     bool pair_tab = false;           // the pairs' coupling table is built
     bool need_u0 = false;            // the packed payoff without a lambda_bar array (a Bermudan call)
@@ -270,6 +272,9 @@ static inline HadiRoute hadi_route(const HadiRouteIn &in) {
     // A cliquet call (strike fixings at the end of its fixing steps) likewise: hadi_fixing_gather_kernel and hadi_fixing_kernel
     // between two steps of the streaming loop, or the event inside the whole-loop LDS kernels.
     const bool cliquet = r.cliquet = in.n_fix_steps > 0 && !in.debug;
+    // A jump call (Bates) takes the streaming path only: the dense sub-step sits between two steps of the streaming loop
+    // (hadi_jump_kernel); it is not built into the whole-loop LDS kernels, the resident sweep or the team launch.
+    const bool jumps = r.jumps = in.jumps && !in.debug;
     r.have_div = r.dividend && in.dividends && !in.debug;  // (diagnostics take p->U as the state the pass starts from)
     // (a caller who pins the streaming kernels' geometry -- hadi_set_tuning "strip", "row_tile", "col_groups", "strip_blocks" --
     // gets those kernels: no whole-loop kernel, resident sweep or team launch is chosen automatically)
@@ -281,11 +286,11 @@ static inline HadiRoute hadi_route(const HadiRouteIn &in) {
     // streaming -> this kernel): 50x25 (three per CU) x257 0.040 -> 0.020, x500 0.057 -> 0.021, x1024 0.082 -> 0.041, x3000
     // 0.210 -> 0.100; 100x30 (one per CU: one wavefront on each CU) x500 0.064 -> 0.081, so such grids stay streaming.
     const bool small_sch = cs && t.use_small && !in.profiling && !in.debug && !t.debug_fault && !f32 && in.variant == HADI_EU &&
-                           !seq_shape && hadi_small_sch_admits(L) &&
+                           !seq_shape && hadi_small_sch_admits(L) && !jumps &&
                            (t.small_sch > 0 || (t.small_sch < 0 && in.n > cu && 3 * hadi_small_sch_smem(L) <= (size_t)160 * 1024 &&
                                                 !pinned && t.cs_strips != 0));
     // ---- small grids: the whole instance fits in LDS -> one launch runs the entire time loop ----------
-    const bool takes_small_path = t.use_small && !in.profiling && !cs && !f32 && !in.debug && (american ? pl.smem_small_am : pl.smem_small_eu) > 0;
+    const bool takes_small_path = t.use_small && !in.profiling && !cs && !f32 && !in.debug && !jumps && (american ? pl.smem_small_am : pl.smem_small_eu) > 0;
     // European / dividend sweeps: one wavefront per instance with sequential line solves (hadi_small_seq_kernel) issues about
     // half the instructions per instance and step but runs them on ONE wavefront -- ahead once there are more instances than
     // CUs (50x25, 40 steps, ms block kernel / this one: 256 instances 0.49 / 0.55, 320: 0.67 / 0.60, 512: 0.71 / 0.63, 768: 0.95 /
@@ -308,7 +313,7 @@ static inline HadiRoute hadi_route(const HadiRouteIn &in) {
     r.read_payoff_shape = american && t.use_amp && !cs && !takes_small_path && !in.debug && !seq_shape && !ladder;
     r.need_lam_u0 = american;
     r.need_u0 = (bermudan || (cliquet && in.fix_weights)) && !american;
-    r.need_ut = r.dividend;
+    r.need_ut = r.dividend || jumps;  // (the sub-step works out of place: it reads the copy of U it finds there)
     r.need_f32 = f32;
     r.need_v_r1_c2 = cs && !small_sch;  // (hadi_small_sch_kernel keeps V, R1, C2 in LDS)
     r.need_r1 = pl.row_seq != 0;        // (hadi_pass_a_seq parks the Thomas multipliers there)
@@ -319,7 +324,7 @@ static inline HadiRoute hadi_route(const HadiRouteIn &in) {
     // streaming geometry; 1: wherever eligible; 0: never.
     const bool resident_shape = (t.resident_sweep > 0 || (t.resident_sweep < 0 && !pinned)) && in.scheme == HADI_SCHEME_DOUGLAS &&
                                 in.variant == HADI_EU && !f32 && hadi_resident_grid(pl, in.theta, in.rates_equal) && !in.debug &&
-                                !t.debug_fault && !prof && !ladder && !bermudan && !barrier && !cliquet;  // (test hooks: the streaming kernels they are for)
+                                !t.debug_fault && !prof && !ladder && !bermudan && !barrier && !cliquet && !jumps;  // (test hooks: the streaming kernels they are for)
     for (const HadiSubBatch &sbt : r.bp.subs)
         r.resident.push_back(resident_shape && hadi_resident_plan(sbt.pl) && sbt.cnt <= cu &&
                              hadi_plan_row_idle(sbt.pl, sbt.cnt, cu) < HADI_TWO_STREAM_IDLE);
@@ -331,7 +336,7 @@ static inline HadiRoute hadi_route(const HadiRouteIn &in) {
     // Chosen automatically for batches of up to 8 instances on the full 256-CU device; any failure of the team protocol is
     // recorded by the kernel, checked by the caller, and the batch is solved again on the streaming path.
     const bool team = hadi_team_grid(pl, in.n, in.theta, in.rates_equal) && (in.variant == HADI_EU || in.variant == HADI_DIV) && !cs && !f32 &&
-                      !in.debug && !prof && cu == 256 && !ladder && !bermudan && !barrier && !cliquet && (t.team_launch > 0 || (t.team_launch < 0 && !in.team_failed && !pinned));
+                      !in.debug && !prof && cu == 256 && !ladder && !bermudan && !barrier && !cliquet && !jumps && (t.team_launch > 0 || (t.team_launch < 0 && !in.team_failed && !pinned));
     r.kind = small_sch ? HADI_ROUTE_SMALL_SCH : takes_small_path ? (seq2 ? HADI_ROUTE_SMALL_SEQ2 : seq ? HADI_ROUTE_SMALL_SEQ : HADI_ROUTE_SMALL) :
              team ? HADI_ROUTE_TEAM : HADI_ROUTE_STREAMING;
     return r;
@@ -408,6 +413,7 @@ static inline std::string hadi_describe_route(const HadiRoute &r, const HadiRout
     s += ex_stream;
     s += ko_stream;
     s += fix_stream;
+    if (r.jumps) s += "; Bates: hadi_jump_kernel (fp64 matrix core) behind the last column pass of every step";
     if (team == HADI_TEAM_FELL_BACK) s += " (after a failed instance-resident launch)";
     return s;
 }

@@ -656,6 +656,76 @@ class HestonADI:
         del keep
         return J, base
 
+    # ---- the Bates model: lognormal jumps (hadi_bates_timestepping and its launchers; no reference counterpart) ------
+    @staticmethod
+    def _jumps(n, jump_intensity, jump_mean, jump_vol, shared_grid):
+        """(struct hadi_jumps, the arrays it points into) -- a scalar fills the shared field, a sequence becomes a host array [n]."""
+        keep = []
+
+        def field(x, name):
+            if np.ndim(x) == 0:
+                return float(x), None
+            a = np.ascontiguousarray(x, dtype=np.float64)
+            if a.shape != (n,):
+                raise ValueError("%s: a scalar or one value per instance" % name)
+            keep.append(a)
+            return 0.0, a.ctypes.data_as(nat._dp)
+
+        (lam, lam_i), (mu, mu_i), (sg, sg_i) = (field(jump_intensity, "jump_intensity"), field(jump_mean, "jump_mean"),
+                                                field(jump_vol, "jump_vol"))
+        return nat.Jumps(lam, mu, sg, lam_i, mu_i, sg_i, int(bool(shared_grid))), keep
+
+    def bates_timestepping(self, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U, jump_intensity, jump_mean,
+                           jump_vol, shared_grid=False, variant=EU, dividends=None, per_instance=None, scheme=0, option_type=CALL,
+                           strikes=None):
+        """DO_timestepping (variant EU or DIV) under the Bates model: Heston plus compound-Poisson jumps in the spot of intensity
+        `jump_intensity` with ln Y ~ N(jump_mean, jump_vol^2).  After the last pass of EVERY step each v-row takes
+        U <- U + lambda dt (G U), G the generator of the jump term on the instance's own s-grid (include/hadi.h).  The three jump
+        arguments: a scalar or one value per instance.  shared_grid: the caller's promise that every instance has instance 0's
+        s-grid -- with a shared (jump_mean, jump_vol) one matrix then serves the whole batch; the promise is checked.  First order
+        in time; European and dividend sweeps on the streaming path only.  U is updated in place."""
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U=U, dividends=dividends,
+                          per_instance=per_instance, scheme=scheme, option_type=option_type, strikes=strikes)
+        j, keep = self._jumps(p.n_instances, jump_intensity, jump_mean, jump_vol, shared_grid)
+        self._call(self._lib.hadi_bates_timestepping, C.byref(p), C.byref(j))
+        del keep
+        return U
+
+    def compute_base_prices_bates(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                  num_strikes, deviceGrids, workspace, jump_intensity, jump_mean, jump_vol, shared_grid=False,
+                                  variant=EU, dividends=None, per_instance=None, scheme=0):
+        """compute_base_prices* (the v-grid rebuilt for V_0 or per_instance['V_0_i']) under the Bates model: [n] prices at
+        (S_0, V_0).  workspace.U is the initial condition and receives the field."""
+        p = self._base_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, num_strikes,
+                               deviceGrids, workspace, None, dividends, per_instance, scheme)
+        j, keep = self._jumps(num_strikes, jump_intensity, jump_mean, jump_vol, shared_grid)
+        out, optr = self._out(num_strikes, 1, workspace.U)
+        self._call(self._lib.hadi_compute_base_prices_bates, C.byref(p), float(S_0), float(V_0), C.byref(j), optr)
+        del keep
+        return out
+
+    def compute_jacobian_bates(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                               num_strikes, deviceGrids, U_0, jump_intensity, jump_mean, jump_vol, shared_grid=False, eps=1e-6,
+                               variant=EU, dividends=None, per_instance=None, scheme=0):
+        """compute_jacobian* under the Bates model: (J [n][5], base_prices [n]), columns kappa, eta, sigma, rho, V_0 -- the jump
+        parameters are inputs, held fixed; the six solves of an instance share its matrix.  U_0 is the initial condition."""
+        p = self._jacobian_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, deviceGrids,
+                                   U_0, dividends, per_instance, scheme)
+        j, keep = self._jumps(num_strikes, jump_intensity, jump_mean, jump_vol, shared_grid)
+        J, jptr = self._out(num_strikes, 5, U_0)
+        base, bptr = self._out(num_strikes, 1, U_0)
+        self._call(self._lib.hadi_compute_jacobian_bates, C.byref(p), float(S_0), float(V_0), float(eps), C.byref(j), jptr, bptr)
+        del keep
+        return J, base
+
+    def debug_jump_matrix(self, vec_s, jump_mean, jump_vol):
+        """The generator G [m1+1][m1+1] of the jump term on the grid vec_s, natural order, as the sweep's kernel builds it."""
+        vs = np.ascontiguousarray(vec_s, dtype=np.float64)
+        G = np.empty((vs.size, vs.size))
+        self._call(self._lib.hadi_debug_jump_matrix, vs.size - 1, vs.ctypes.data_as(nat._dp), float(jump_mean), float(jump_vol),
+                   G.ctypes.data_as(nat._dp))
+        return G
+
     # ---- compute_base_prices* (src/jacobian_computation.cpp:368, 629, 922, 1232) ---------------
     def _base_prices(self, variant, S_0, V_0, T, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N,
                      theta, delta_t, num_strikes, deviceGrids, workspace, U_0=None, dividends=None,
