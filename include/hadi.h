@@ -32,7 +32,8 @@
  *                                      on chosen steps (U <- max(U, payoff) at their end)
  *   hadi_barrier_timestepping, hadi_compute_{base_prices,jacobian}_barrier <- no counterpart: the European sweep with a knock-out
  *                                      on chosen monitoring steps (U <- rebate at or beyond a barrier, at their end)
- *   hadi_bates_timestepping, hadi_compute_{base_prices,jacobian}_bates <- no counterpart: the European sweep under the Bates model
+ *   hadi_bates_timestepping, hadi_compute_{base_prices,jacobian}_bates, hadi_compute_jacobian_bates_jumps
+ *                                   <- no counterpart: the European sweep under the Bates model
  *                                      (lognormal jumps as a dense sub-step U <- U + lambda dt G U at the end of every step)
  *   hadi_make_grid / hadi_rebuild_variance <- Grid::Grid (src/grid.cpp:16-61),
  *                                      GridViews::rebuild_variance_views (src/grid_pod.hpp:25-73)
@@ -268,6 +269,8 @@ int hadi_get_timing(const hadi_ctx *ctx, hadi_timing *out);
  *                 the plan picks strips (0: on the shared ring, the path of rounds 2 - 3; same fields to round-off)
  *   "graph_max_melems" hipGraph replay of the time loop for batches of up to this many Mi state elements (default 8; larger
  *                 batches are not launch-bound: measured equal)
+ *   "jump_share"  1 (default) / 0: hadi_compute_jacobian_bates_jumps with per-instance matrices -- the groups 0 .. 6 of an instance
+ *                 share one staged strip of its matrix (0: every block stages the strip for one instance); same bits
  *   "device_vgrid" v-grids of compute_base_prices / compute_jacobian rebuilt per instance on the device (default 1;
  *                 0 = built once on the host with glibc sinh/asinh and broadcast -- bit-identical to the reference's
  *                 host-side Grid, needs one shared V_0)
@@ -551,8 +554,9 @@ int hadi_compute_jacobian_cliquet(hadi_ctx *ctx, const hadi_problem *p, double S
  *                         is built and staged for the whole batch.  The promise is checked on the device (bit-equal rows of vec_s);
  *                         a broken promise is HADI_ERR_INVALID.  0: one matrix per instance.
  * The matrices are built on the device on every call from the sweep's own s-grids (hadi_jump_matrix_kernel); the six solves of a
- * Jacobian row share their instance's matrix; the Jacobian keeps its five columns (kappa, eta, sigma, rho, V_0): the jump
- * parameters are inputs.  If every a_k is 0 the call is the plain call bit for bit, on whatever route that takes; an instance
+ * Jacobian row share their instance's matrix; hadi_compute_jacobian_bates keeps the five columns (kappa, eta, sigma, rho, V_0): the
+ * jump parameters are inputs (hadi_compute_jacobian_bates_jumps below has them as columns).
+ * If every a_k is 0 the call is the plain call bit for bit, on whatever route that takes; an instance
  * with a_k = 0 inside a jump call equals its plain solve bit for bit.  A jump call runs the streaming kernels followed by
  * hadi_jump_kernel on the fp64 matrix core: never a whole-loop LDS kernel, hadi_sweep_resident or hadi_team_kernel.
  * hadi_bates_timestepping reads and writes p exactly as hadi_DO_timestepping does; the two launchers rebuild the v-grid and
@@ -571,6 +575,20 @@ int hadi_compute_base_prices_bates(hadi_ctx *ctx, const hadi_problem *p, double 
                                    double *prices);
 int hadi_compute_jacobian_bates(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, const hadi_jumps *jumps,
                                 double *J, double *base_prices);
+/* The Jacobian with the jump law among its columns: J [n][8], columns kappa, eta, sigma, rho, V_0, lambda, mu_J, sigma_J, all forward
+ * differences with the one step eps; base_prices [n].  Nine groups of ONE batched sweep: the groups 0 .. 5 exactly as in
+ * hadi_compute_jacobian_bates, group 6 with a_k = (lambda_k + eps) delta_t_k on the base matrix, group 7 on the matrix of (mu_k + eps,
+ * sigma_k), group 8 on the matrix of (mu_k, sigma_k + eps) -- three matrix sets, each one matrix per instance, or one for the batch
+ * with shared_grid and a shared (mu, sigma); per-instance lambda_i / mu_i / sigma_i are bumped per instance.  The sub-step is
+ * hadi_jump_sel_kernel: hadi_jump_kernel's arithmetic, the matrix picked by group and source instance.  With per-instance matrices
+ * the groups 0 .. 6 of an instance that fall into one sub-batch share a staged strip of G (hadi_set_tuning "jump_share", default 1;
+ * 0: one instance per block): which instances share a block changes no result bit.
+ * Variants, schemes, calls and puts, per-instance (N, delta_t) and V_0_i, memory spaces and refusals as hadi_compute_jacobian_bates,
+ * plus: (lambda_k + eps) delta_t_k > 1 is HADI_ERR_INVALID.  The call always takes the jump route (group 6 jumps even where every
+ * lambda_k is 0).  An instance with lambda_k = 0 has J[k][6] == J[k][7] == 0.0 exactly: its groups 7 and 8 are skipped as its
+ * group 0 is. */
+int hadi_compute_jacobian_bates_jumps(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, const hadi_jumps *jumps,
+                                      double *J, double *base_prices);
 /* diagnostics (tests): the natural-order generator G [m1 + 1][m1 + 1] of one grid, built by the kernel the sweep uses.
  * vec_s [m1 + 1] and G_out are HOST arrays. */
 int hadi_debug_jump_matrix(hadi_ctx *ctx, int m1, const double *vec_s, double mu, double sigma, double *G_out);
@@ -609,6 +627,14 @@ int hadi_lm_partials_device(hadi_ctx *ctx, int n, const double *J, const double 
                             const double *market_prices, double *partial31);
 /* delta = (J^T J with diagonal *(1+lambda))^-1 J^T r by 5x5 partial-pivot elimination. */
 int hadi_lm_solve(const double *partial31, double lambda, double *delta5);
+/* The three functions above for n_par = 1 .. HADI_LM_MAX_PAR parameters (8: hadi_compute_jacobian_bates_jumps): J [n][n_par];
+ * partials = [J^T J row-major n_par^2][J^T r n_par][sum r^2], n_par^2 + n_par + 1 doubles (73 at n_par = 8); delta [n_par].
+ * At n_par = 5 they are the functions above, bit for bit.  n_par outside 1 .. HADI_LM_MAX_PAR: HADI_ERR_INVALID. */
+#define HADI_LM_MAX_PAR 8
+int hadi_lm_partials_n(int n, int n_par, const double *J, const double *residuals, double *partials);
+int hadi_lm_partials_device_n(hadi_ctx *ctx, int n, int n_par, const double *J, const double *model_prices,
+                              const double *market_prices, double *partials);
+int hadi_lm_solve_n(int n_par, const double *partials, double lambda, double *delta);
 /* Both steps on one rank: compute_parameter_update_on_device. */
 int hadi_compute_parameter_update(int n, const double *J, const double *residuals, double lambda,
                                   double *delta5);

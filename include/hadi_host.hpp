@@ -429,7 +429,8 @@ inline void compute_jacobian_cliquet(Handle &h, double S_0, double V_0, double /
 // lognormal-jump sub-step U <- U + lambda dt (G U) at the end of every step.  lambda / mu / sigma: the shared jump law; lambda_i /
 // mu_i / sigma_i: one value per instance, or empty = the shared value.  shared_grid: the caller's promise that every instance has
 // instance 0's s-grid (checked by the library): with a shared (mu, sigma) one matrix serves the batch.  workspace.U is the caller's
-// initial condition and receives the field.  The Jacobian keeps its five columns: the jump parameters are inputs.
+// initial condition and receives the field.  compute_jacobian_bates keeps the five columns (the jump parameters are inputs);
+// compute_jacobian_bates_jumps has eight.
 struct Jumps {
     double lambda = 0.0, mu = 0.0, sigma = 0.1;
     std::vector<double> lambda_i, mu_i, sigma_i;
@@ -475,6 +476,21 @@ inline void compute_jacobian_bates(Handle &h, double S_0, double V_0, double /*T
     hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
                                   nullptr, U_0.data(), div, put);
     detail::check(h, hadi_compute_jacobian_bates(h.ctx, &p, S_0, V_0, eps, &j, J.data(), base_prices.data()));
+}
+// J: [num_strikes][8], columns kappa, eta, sigma, rho, V_0, lambda, mu_J, sigma_J -- the jump law among the parameters: nine solves
+// per instance over three sets of matrices (hadi_compute_jacobian_bates_jumps); (lambda + eps) delta_t must not exceed 1
+inline void compute_jacobian_bates_jumps(Handle &h, double S_0, double V_0, double /*T*/, double r_d, double r_f, double rho,
+                                         double sigma, double kappa, double eta, int m1, int m2, int /*total_size*/, int N, double theta,
+                                         double delta_t, int num_strikes, const GridViews &deviceGrids, const std::vector<double> &U_0,
+                                         const Jumps &jumps, std::vector<double> &J, std::vector<double> &base_prices,
+                                         double eps = 1e-6, int variant = HADI_EU, const Dividends *div = nullptr,
+                                         const PutStrikes *put = nullptr) {
+    const hadi_jumps j = jumps.view(num_strikes);
+    J.resize((size_t)num_strikes * 8);
+    base_prices.resize(num_strikes);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  nullptr, U_0.data(), div, put);
+    detail::check(h, hadi_compute_jacobian_bates_jumps(h.ctx, &p, S_0, V_0, eps, &j, J.data(), base_prices.data()));
 }
 
 // jacobian_computation.cpp:204-364 and the three variants.  J: [num_strikes][5], columns kappa, eta, sigma, rho, v0.
@@ -526,6 +542,20 @@ inline void compute_parameter_update_on_device(const std::vector<double> &J, con
     delta.resize(5);
     if (hadi_compute_parameter_update((int)residuals.size(), J.data(), residuals.data(), lambda, delta.data()))
         throw std::runtime_error("hadi_compute_parameter_update failed");
+}
+
+// The LM normal equations for n_par = 1 .. HADI_LM_MAX_PAR parameters (hadi_lm_partials_n, hadi_lm_solve_n): J [n][n_par];
+// partials = [J^T J row-major][J^T r][sum r^2], n_par^2 + n_par + 1 doubles -- what is all-reduced across ranks; delta [n_par].
+inline void lm_partials_n(int n_par, const std::vector<double> &J, const std::vector<double> &residuals, std::vector<double> &partials) {
+    if (n_par < 1 || J.size() != residuals.size() * (size_t)n_par) throw std::runtime_error("lm_partials_n: J is not [n][n_par]");
+    partials.resize((size_t)n_par * n_par + n_par + 1);
+    if (hadi_lm_partials_n((int)residuals.size(), n_par, J.data(), residuals.data(), partials.data()))
+        throw std::runtime_error("hadi_lm_partials_n failed");
+}
+inline void lm_solve_n(int n_par, const std::vector<double> &partials, double lambda, std::vector<double> &delta) {
+    if (n_par < 1 || partials.size() != (size_t)n_par * n_par + n_par + 1) throw std::runtime_error("lm_solve_n: partials are not of n_par parameters");
+    delta.resize(n_par);
+    if (hadi_lm_solve_n(n_par, partials.data(), lambda, delta.data())) throw std::runtime_error("hadi_lm_solve_n failed");
 }
 
 }  // namespace hadi_host

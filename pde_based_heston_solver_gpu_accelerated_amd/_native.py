@@ -98,6 +98,7 @@ EXPORTS = [
     "hadi_barrier_timestepping", "hadi_compute_base_prices_barrier", "hadi_compute_jacobian_barrier",
     "hadi_cliquet_timestepping", "hadi_compute_base_prices_cliquet", "hadi_compute_jacobian_cliquet",
     "hadi_bates_timestepping", "hadi_compute_base_prices_bates", "hadi_compute_jacobian_bates", "hadi_debug_jump_matrix",
+    "hadi_compute_jacobian_bates_jumps", "hadi_lm_partials_n", "hadi_lm_partials_device_n", "hadi_lm_solve_n",
     "hadi_compute_base_prices", "hadi_compute_base_prices_american",
     "hadi_compute_base_prices_dividends", "hadi_compute_base_prices_american_dividends",
     "hadi_compute_jacobian", "hadi_compute_jacobian_american",
@@ -193,6 +194,12 @@ def _load(LIB_PATH):
         L.hadi_compute_jacobian_bates.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_double, _jp, C.c_void_p,
                                                   C.c_void_p]
         L.hadi_debug_jump_matrix.argtypes = [C.c_void_p, C.c_int, _dp, C.c_double, C.c_double, _dp]
+    if hasattr(L, "hadi_compute_jacobian_bates_jumps"):  # (likewise: a build from before the eight-column Jacobian)
+        L.hadi_compute_jacobian_bates_jumps.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_double,
+                                                        C.POINTER(Jumps), C.c_void_p, C.c_void_p]
+        L.hadi_lm_partials_n.argtypes = [C.c_int, C.c_int, _dp, _dp, _dp]
+        L.hadi_lm_partials_device_n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _dp]
+        L.hadi_lm_solve_n.argtypes = [C.c_int, _dp, C.c_double, _dp]
     if hasattr(L, "hadi_sample_ladder"):  # (likewise: a build from before the sampled ladder)
         _sp = C.POINTER(Samples)
         for name in ("hadi_sample_ladder", "hadi_compute_base_prices_samples"):

@@ -11,6 +11,7 @@ normal equations are all-reduced (31 doubles per iteration, 1 double for the tri
     calibrate_american_dividends_multi_maturity test_calibration_american_divident_multi_maturity  :3245-3820
     calibrate_bermudan                          no counterpart: European / dividend sweeps with exercise on chosen steps
     calibrate_european_maturity_ladder          no counterpart: all maturities of a strike from ONE sweep on a shared delta_t
+    calibrate_bates, calibrate_bates_jumps      no counterpart: the Bates model, the jump law held fixed / fitted (8 parameters)
 
 `solver` is anything with the mirrored launchers of solver.HestonADI (`compute_jacobian*`, `compute_base_prices*`).
 """
@@ -26,6 +27,12 @@ from .distributed import Communicator
 RHO_MIN, RHO_MAX = -1.0, 1.0           # heston_calibration.cpp:194
 KAPPA_FLOOR, OTHER_FLOOR = 1e-3, 1e-2  # heston_calibration.cpp:286-290
 LAMBDA_MIN, LAMBDA_MAX = 1e-7, 1e7     # heston_calibration.cpp:398-408
+# The jump law of calibrate_bates_jumps (no counterpart).  The floor of the intensity keeps the mu_J and sigma_J columns of the
+# Jacobian from vanishing (they scale with it: zero pivots); its ceiling is JUMP_INTENSITY_CEIL / delta_t, so that (intensity + eps)
+# delta_t stays admissible.
+JUMP_INTENSITY_FLOOR, JUMP_INTENSITY_CEIL = 1e-3, 0.99
+JUMP_MEAN_MIN, JUMP_MEAN_MAX = -1.0, 1.0
+JUMP_VOL_FLOOR, JUMP_VOL_MAX = OTHER_FLOOR, 1.0
 
 EU, AM, DIV, AM_DIV = _solver.EU, _solver.AM, _solver.DIV, _solver.AM_DIV
 
@@ -70,6 +77,12 @@ def make_ladder_points(strikes, maturities, delta_t):
 def clamp_parameters(kappa, eta, sigma, rho, v0):
     return (max(KAPPA_FLOOR, kappa), max(OTHER_FLOOR, eta), max(OTHER_FLOOR, sigma),
             min(RHO_MAX, max(RHO_MIN, rho)), max(OTHER_FLOOR, v0))
+
+
+def clamp_jump_parameters(jump_intensity, jump_mean, jump_vol, delta_t):
+    """The clamps of the three jump parameters of calibrate_bates_jumps, beside clamp_parameters' five."""
+    return (min(JUMP_INTENSITY_CEIL / delta_t, max(JUMP_INTENSITY_FLOOR, jump_intensity)),
+            min(JUMP_MEAN_MAX, max(JUMP_MEAN_MIN, jump_mean)), min(JUMP_VOL_MAX, max(JUMP_VOL_FLOOR, jump_vol)))
 
 
 class _WS:  # minimal DO_Workspace: the launchers read the initial condition from .U
@@ -139,7 +152,8 @@ def _launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, grids, U_0, 
 
 def calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0,
               market_prices, dividends=None, calibration_points=None, max_iter=20, tol=0.1, delta_tol=None, eps=1e-6,
-              lam=0.01, comm=None, lm_partials=_solver.lm_partials, lm_solve=_solver.lm_solve, scheme=0, launchers=None):
+              lam=0.01, comm=None, lm_partials=_solver.lm_partials, lm_solve=_solver.lm_solve, scheme=0, launchers=None,
+              extra=(), clamp_extra=None, solves_per_iteration=7):
     """The LM loop shared by all drivers (heston_calibration.cpp:204-417).  `grids`, `U_0`, `market_prices` (and
     `calibration_points` for the multi-maturity drivers, which then ignore T and N) are this rank's shard.
     `scheme`: the time stepper of every Jacobian and trial-price solve of the loop (0 Douglas, 1 Craig-Sneyd, 2 Modified
@@ -147,6 +161,10 @@ def calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1
     the usual pairs are 1/3 for MCS and 1/2 + sqrt(3)/6 for HV, which are second order in time where Douglas is first.
     `launchers`: the pair of closures _launchers would build, for drivers whose instruments are not one instance each (the
     maturity ladder); market_prices then follow the closures' order.
+    `extra`: further parameters behind the five (calibrate_bates_jumps: the jump law) -- the closures then take 5 + len(extra)
+    parameters, the Jacobian has as many columns, and `clamp_extra` (a function of the extra entries that returns them clamped;
+    None: none) stands beside clamp_parameters.  The result then carries "extra".  `solves_per_iteration`: sweeps per instance and
+    iteration, for `pde_solves` (columns + 1 for the Jacobian, 1 for the trial).
     Stops when ||delta||_2 < delta_tol (default: tol) or sum r^2 < tol.  Returns a dict with the calibrated
     parameters, final error, iteration count, PDE-solve count, the last computed model prices and the trajectory."""
     comm = comm or Communicator()
@@ -155,7 +173,8 @@ def calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1
     market = np.asarray(market_prices, dtype=np.float64)
     jac, base_fn = launchers or _launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, grids, U_0, dividends,
                                            calibration_points, scheme=scheme)
-    cur = (kappa, eta, sigma, rho, V_0)
+    extra = tuple(float(e) for e in extra)
+    cur = (kappa, eta, sigma, rho, V_0) + extra
     final_error, iteration_count, converged = 100.0, 0, False
     history = []
     model = None
@@ -181,9 +200,12 @@ def calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1
             part_loc = lm_partials(J, resid)
         part = comm.allreduce_sum(part_loc)                              # the only collective of the step
         delta = lm_solve(part, lam)
-        new = clamp_parameters(*(c + d for c, d in zip(cur, delta)))
+        moved = tuple(c + d for c, d in zip(cur, delta))
+        new = clamp_parameters(*moved[:5])
+        if extra:
+            new = new + tuple(clamp_extra(*moved[5:]) if clamp_extra else moved[5:])
         delta_norm = float(np.sqrt(np.sum(delta * delta)))
-        current_error = float(part[30])
+        current_error = float(part[-1])                                  # sum r^2: the last slot, whatever the width
         history.append({"iter": it + 1, "params": cur, "error": current_error, "lambda": lam,
                         "delta": delta.copy(), "trial": new})
         if delta_norm < delta_tol or current_error < tol:                # heston_calibration.cpp:322-338
@@ -212,11 +234,14 @@ def calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1
         final_error = min(new_error, current_error)
         iteration_count = it + 1
     n_glob = int(round(comm.allreduce_sum(np.array([float(n_loc)]))[0]))
-    return {"kappa": cur[0], "eta": cur[1], "sigma": cur[2], "rho": cur[3], "v0": cur[4],
-            "final_error": final_error, "iterations": iteration_count, "converged": converged,
-            "pde_solves": n_glob * 7 * iteration_count - n_glob,          # heston_calibration.cpp:428
-            "initial": (kappa, eta, sigma, rho, V_0), "model_prices": None if model is None else _to_numpy(model),
-            "history": history}
+    out = {"kappa": cur[0], "eta": cur[1], "sigma": cur[2], "rho": cur[3], "v0": cur[4],
+           "final_error": final_error, "iterations": iteration_count, "converged": converged,
+           "pde_solves": n_glob * solves_per_iteration * iteration_count - n_glob,  # heston_calibration.cpp:428
+           "initial": (kappa, eta, sigma, rho, V_0), "model_prices": None if model is None else _to_numpy(model),
+           "history": history}
+    if extra:
+        out["extra"] = cur[5:]
+    return out
 
 
 def calibrate_european(solver, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0,
@@ -445,6 +470,52 @@ def calibrate_bates(solver, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m
                               grids, U_0, dividends if variant == DIV else None, scheme=scheme)
     return calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0, market_prices,
                      dividends=dividends, max_iter=max_iter, tol=tol, scheme=scheme, launchers=launch, **kw)
+
+
+def _bates_jumps_launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, shared_grid, grids, U_0, dividends, scheme=0):
+    """The closures of calibrate() over the eight-column Bates launchers: one instance per strike, eight parameters."""
+    n_loc = grids.Vec_s.shape[0]
+    total_size = (m1 + 1) * (m2 + 1)
+    delta_t = T / N
+    kw = {"variant": variant, "dividends": dividends}
+    if scheme:
+        kw["scheme"] = scheme
+
+    def jac(k, e, s, r, v, lj, mj, sj, eps):
+        return solver.compute_jacobian_bates_jumps(S_0, v, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t, n_loc, grids,
+                                                   U_0, lj, mj, sj, shared_grid, eps=eps, **kw)
+
+    def base(k, e, s, r, v, lj, mj, sj):
+        ws = _WS()
+        ws.U = _clone(U_0)
+        return solver.compute_base_prices_bates(S_0, v, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t, n_loc,
+                                                grids, ws, lj, mj, sj, shared_grid, **kw)
+
+    return jac, base
+
+
+def calibrate_bates_jumps(solver, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0, market_prices,
+                          jump_intensity, jump_mean, jump_vol, shared_grid=False, dividends=None, max_iter=15, tol=0.1, scheme=0, **kw):
+    """calibrate_bates with the jump law fitted too: eight parameters -- the five of calibrate_bates and the scalars jump_intensity,
+    jump_mean, jump_vol, which are the start values.  Every iteration is one eight-column Jacobian (compute_jacobian_bates_jumps:
+    nine sweeps per strike) and one trial (compute_base_prices_bates); 73 doubles are all-reduced.  Clamps beside clamp_parameters:
+    clamp_jump_parameters.  The result carries jump_intensity, jump_mean and jump_vol beside calibrate's keys; `pde_solves` counts
+    ten sweeps per strike and iteration.  shared_grid, dividends, scheme / theta: as calibrate_bates."""
+    for x, name in ((jump_intensity, "jump_intensity"), (jump_mean, "jump_mean"), (jump_vol, "jump_vol")):
+        if np.ndim(x) != 0:
+            raise ValueError("%s: calibrate_bates_jumps fits one jump law, so a scalar start value" % name)
+    variant = DIV if dividends is not None and len(dividends) else EU
+    if scheme and variant != EU:
+        raise ValueError("scheme %r: the predictor-corrector schemes price European sweeps only" % (scheme,))
+    delta_t = T / N
+    launch = _bates_jumps_launchers(solver, variant, S_0, T, r_d, r_f, m1, m2, N, theta, shared_grid, grids, U_0,
+                                    dividends if variant == DIV else None, scheme=scheme)
+    res = calibrate(solver, variant, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, N, theta, grids, U_0, market_prices,
+                    dividends=dividends, max_iter=max_iter, tol=tol, scheme=scheme, launchers=launch,
+                    extra=(jump_intensity, jump_mean, jump_vol), clamp_extra=lambda lj, mj, sj: clamp_jump_parameters(lj, mj, sj, delta_t),
+                    solves_per_iteration=10, **kw)
+    res["jump_intensity"], res["jump_mean"], res["jump_vol"] = res.pop("extra")
+    return res
 
 
 def calibrate_american_dividends_multi_maturity(solver, S_0, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, theta,

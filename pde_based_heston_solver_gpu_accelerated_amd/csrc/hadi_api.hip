@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "hadi_route.h"
@@ -268,8 +269,10 @@ struct SweepDesc {
     // at the end of every step, some of them non-zero (a call whose weights are all zero carries none: it is the plain call);
     // jmp_musig: [jmp_nmat][2], the (mu, sigma) of the matrices -- one per source instance (instance k uses matrix k % n_src), or
     // ONE for the batch with jmp_shared (the caller's promise of a shared s-grid, checked on the device).
+    // jmp_sets = 3 (hadi_compute_jacobian_bates_jumps): the batch is 9 groups, and jmp_musig holds three sets of jmp_nmat / 3
+    // matrices -- (mu, sigma), (mu + eps, sigma), (mu, sigma + eps) -- that hadi_jump_sel_kernel picks from by group.
     std::vector<double> jmp_a, jmp_musig;
-    int jmp_nmat = 0;
+    int jmp_nmat = 0, jmp_sets = 1;
     bool jmp_shared = false;
 };
 
@@ -312,6 +315,7 @@ HadiRouteIn route_in(const Ctx *c, const SweepDesc &d) {
     in.debug = d.debug; in.profiling = c->profiling != 0; in.n_snap = d.n_snap; in.n_samp = d.n_samp; in.dividends = d.num_div > 0;
     in.uniform_steps = d.uniform_steps; in.team_failed = c->team_failed != 0; in.t = c->t;
     in.jumps = !d.jmp_a.empty();
+    in.jump_sets = d.jmp_sets;
     return in;
 }
 
@@ -470,7 +474,9 @@ int stage_cliquet(Ctx *c, const Sweep &w) {
 
 // Bates: the weights a_k and the matrices' (mu, sigma) to the device, then the generators from the sweep's own device s-grids
 // (hadi_jump_matrix_kernel into the zeroed buffer) and, for a shared matrix, the check of the caller's promise -- on every call,
-// also before a replay: the matrices are data, not part of a captured loop.
+// also before a replay: the matrices are data, not part of a captured loop.  Matrix q is built on row q of the sweep's s-grids:
+// the groups of a Jacobian's batch repeat the caller's rows, so the three sets of an eight-column call (jmp_nmat = 3 n_src, or 3
+// of a batch of at least 9 bit-equal rows when the matrices are shared) find their source instance's grid there as well.
 int stage_jumps(Ctx *c, const Sweep &w) {
     const SweepDesc &d = w.d;
     const HadiLayout &L = w.r.pl.L;
@@ -755,6 +761,18 @@ int jump_ipg(const Ctx *c, const SweepDesc &d, const HadiLayout &L, int nsb) {
     return (int)std::max(1ll, std::min(8ll, (long long)nsb * hadi_jump_nib(L) / (2ll * c->cu_count)));
 }
 
+// The lists of hadi_jump_sel_kernel for the sub-batch [o, o + nsb) of an eight-column Jacobian's batch.  Shared matrices: runs of
+// consecutive instances, as jump_ipg has them (the groups 0 .. 6 are one matrix).  Per-instance matrices: with "jump_share" the set-0
+// instances of one source instance ride on one staged strip, up to 7 and by jump_ipg's rule of two blocks per CU; else one
+// instance per block.
+HadiJumpSel jump_sel(const Ctx *c, const SweepDesc &d, const HadiLayout &L, int o, int nsb) {
+    HadiJumpSel q;
+    q.inst0 = o; q.n_src = d.n_src; q.per = d.jmp_nmat / d.jmp_sets;
+    q.share = (!d.jmp_shared && c->t.jump_share) ? 1 : 0;
+    q.cap = q.share ? (int)std::max(1ll, std::min(7ll, (long long)nsb * hadi_jump_nib(L) / (2ll * c->cu_count))) : jump_ipg(c, d, L, nsb);
+    return q;
+}
+
 // Sub-batch `sb` through its whole time loop on stream q.
 int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
     const SweepDesc &d = w.d;
@@ -818,10 +836,17 @@ int enqueue_sub_batch(Ctx *c, const Sweep &w, int sb, hipStream_t q) {
         }
         if (r.jumps) {  // Bates: U_temp <- U, U <- U_temp + a G U_temp behind the step's last column pass, in front of the step's events
             HIP_TRY(c, hipMemcpyAsync(UTb, Ub, st, hipMemcpyDeviceToDevice, q));
-            const int ipg = jump_ipg(c, d, L, nsb);
-            hipLaunchKernelGGL(hadi_jump_kernel, dim3(hadi_jump_grid(L, nsb, ipg)), dim3(HADI_JUMP_THREADS), hadi_jump_smem(L), q, L, nsb, ipg,
-                               o, d.n_src, UTb, Ub, ptr<double>(c->jmp_G), d.jmp_shared ? 0ll : (long long)hadi_jump_matrix_doubles(L),
-                               ptr<double>(c->jmp_a) + o, a.ipar, nstep);
+            if (d.jmp_sets > 1) {  // the nine groups of an eight-column Jacobian: three matrix sets, picked by group
+                const HadiJumpSel js = jump_sel(c, d, L, o, nsb);
+                hipLaunchKernelGGL(hadi_jump_sel_kernel, dim3(hadi_jump_sel_grid(L, js, nsb)), dim3(HADI_JUMP_THREADS), hadi_jump_smem(L), q, L,
+                                   nsb, js, UTb, Ub, ptr<double>(c->jmp_G), (long long)hadi_jump_matrix_doubles(L), ptr<double>(c->jmp_a) + o,
+                                   a.ipar, nstep);
+            } else {
+                const int ipg = jump_ipg(c, d, L, nsb);
+                hipLaunchKernelGGL(hadi_jump_kernel, dim3(hadi_jump_grid(L, nsb, ipg)), dim3(HADI_JUMP_THREADS), hadi_jump_smem(L), q, L, nsb,
+                                   ipg, o, d.n_src, UTb, Ub, ptr<double>(c->jmp_G), d.jmp_shared ? 0ll : (long long)hadi_jump_matrix_doubles(L),
+                                   ptr<double>(c->jmp_a) + o, a.ipar, nstep);
+            }
         }
         if (r.bermudan && w.ex.any[nstep]) {  // Bermudan exercise behind the step's last column pass (European sweeps: U is explicit)
             const int bpi = hadi_exercise_bpi(L);
@@ -953,7 +978,7 @@ std::string graph_key(const Ctx *c, const Sweep &w) {
     if (w.r.jumps) {  // the matrices and the weights are built again every call; the launches name their addresses (U_temp: `own`
                       // above), the matrix stride (0: shared), the source count and the instances per block
         const void *jm[] = {c->jmp_G.p, c->jmp_a.p};
-        const int ji[] = {(int)d.jmp_shared, d.n_src, c->cu_count};
+        const int ji[] = {(int)d.jmp_shared, d.n_src, c->cu_count, d.jmp_sets, c->t.jump_share};
         put(jm, sizeof(jm));
         put(ji, sizeof(ji));
     }
@@ -1262,7 +1287,8 @@ int check_cliquet(Ctx *c, const hadi_problem *p, const hadi_cliquet *q) {
 }
 
 // What the Bates entry points ask beyond check_problem (which has passed).
-int check_jumps(Ctx *c, const hadi_problem *p, const hadi_jumps *j) {
+// bump: what the lambda group of an eight-column Jacobian adds to every intensity (0: no such group).
+int check_jumps(Ctx *c, const hadi_problem *p, const hadi_jumps *j, double bump) {
     if (p->variant == HADI_AM || p->variant == HADI_AM_DIV)
         return fail(c, HADI_ERR_UNSUPPORTED, "a jump sweep is the European sweep (HADI_EU or HADI_DIV) with a jump sub-step");
     if (p->state_precision == HADI_STATE_FP32) return fail(c, HADI_ERR_UNSUPPORTED, "jump sweeps need the fp64 state");
@@ -1274,6 +1300,8 @@ int check_jumps(Ctx *c, const hadi_problem *p, const hadi_jumps *j) {
         if (!(sg > 0.0)) return fail(c, HADI_ERR_INVALID, "instance %d: jump volatility %g is not positive", k, sg);
         if (lam * dt > 1.0)
             return fail(c, HADI_ERR_INVALID, "instance %d: lambda delta_t = %g exceeds 1 (the weight of the identity in the jump sub-step would turn negative)", k, lam * dt);
+        if (bump != 0.0 && !((lam + bump) * dt <= 1.0))
+            return fail(c, HADI_ERR_INVALID, "instance %d: (lambda + eps) delta_t = %g exceeds 1 in the Jacobian's lambda group", k, (lam + bump) * dt);
     }
     return HADI_OK;
 }
@@ -1288,6 +1316,7 @@ struct CallExtras {
     const hadi_barrier *barrier = nullptr;                        // a barrier entry point (each refuses NULL itself)
     const hadi_cliquet *cliquet = nullptr;                        // a cliquet entry point (each refuses NULL itself)
     const hadi_jumps *jumps = nullptr;                            // a Bates entry point (each refuses NULL itself)
+    bool jump_cols = false; double jump_eps = 0;                  // ... whose Jacobian has the columns lambda, mu_J, sigma_J: 9 groups, step eps
     int debug = 0, debug_step = 1; double *debug_out = nullptr;   // diagnostics (hadi_debug_*): SweepDesc::debug, and where the pass's result goes
 };
 
@@ -1307,7 +1336,7 @@ int check_extras(Ctx *c, const hadi_problem *p, const CallExtras &x, const void 
     if (x.bermudan && (rc = check_bermudan(c, p, x.ex))) return rc;
     if (x.barrier && (rc = check_barrier(c, p, x.barrier))) return rc;
     if (x.cliquet && (rc = check_cliquet(c, p, x.cliquet))) return rc;
-    if (x.jumps && (rc = check_jumps(c, p, x.jumps))) return rc;
+    if (x.jumps && (rc = check_jumps(c, p, x.jumps, x.jump_cols ? x.jump_eps : 0.0))) return rc;
     if (x.ladder && (rc = check_ladder(c, p, x.n_snap, x.snap_steps, ladder_out))) return rc;
     if (x.sampled && (rc = check_samples(c, p, x.samples))) return rc;
     return HADI_OK;
@@ -1332,18 +1361,23 @@ void apply_extras(SweepDesc &d, const CallExtras &x, const CallOut &o, const dou
     if (x.jumps) {  // (fill_desc has run: the rows of par8 hold every instance's delta_t)
         const hadi_jumps &j = *x.jumps;
         std::vector<double> a(d.n);
-        bool any = false;
+        bool any = x.jump_cols;  // (the lambda group of an eight-column Jacobian always jumps)
         for (int k = 0; k < d.n; k++) {
-            a[k] = (j.lambda_i ? j.lambda_i[k % d.n_src] : j.lambda) * d.par8[(size_t)k * 8 + 4];
+            const double lam = j.lambda_i ? j.lambda_i[k % d.n_src] : j.lambda;
+            // group 6 of the eight-column Jacobian: lambda + eps.  An instance with lambda = 0 keeps a = 0 in the groups 7 and 8.
+            a[k] = ((x.jump_cols && k / d.n_src == 6) ? lam + x.jump_eps : lam) * d.par8[(size_t)k * 8 + 4];
             any = any || a[k] != 0.0;
         }
         if (any) {  // (all weights zero: the plain call, bit for bit, on whatever route it takes)
             d.jmp_a = a;
             d.jmp_shared = j.shared_grid && !j.mu_i && !j.sigma_i;
-            d.jmp_nmat = d.jmp_shared ? 1 : d.n_src;
-            for (int q = 0; q < d.jmp_nmat; q++) {
-                d.jmp_musig.push_back(j.mu_i ? j.mu_i[q] : j.mu);
-                d.jmp_musig.push_back(j.sigma_i ? j.sigma_i[q] : j.sigma);
+            d.jmp_sets = x.jump_cols ? HADI_JUMP_SETS : 1;
+            const int per = d.jmp_shared ? 1 : d.n_src;
+            d.jmp_nmat = d.jmp_sets * per;
+            for (int q = 0; q < d.jmp_nmat; q++) {  // set 1: mu + eps, set 2: sigma + eps
+                const int set = q / per, k = q % per;
+                d.jmp_musig.push_back((j.mu_i ? j.mu_i[k] : j.mu) + (set == 1 ? x.jump_eps : 0.0));
+                d.jmp_musig.push_back((j.sigma_i ? j.sigma_i[k] : j.sigma) + (set == 2 ? x.jump_eps : 0.0));
             }
         }
     }
@@ -1584,15 +1618,16 @@ int greeks_common(Ctx *c, const hadi_problem *p, const CallOut &o) {
     return finish_call(c, d, o, STATUS_GREEKS, n, false);
 }
 
-// The grids of the 6 groups of a Jacobian's batch: the caller's s-rows replicated, the v-grids rebuilt for V_0 (groups 0..4) and
-// V_0 + eps (group 5); c->v0_i keeps the per-instance V_0 for the price pick.  n_col: the output columns per instance.
+// The grids of the G groups of a Jacobian's batch (6, or 9 with the jump columns): the caller's s-rows replicated, the v-grids
+// rebuilt for V_0 + eps (group 5) and V_0 (every other group); c->v0_i keeps the per-instance V_0 for the price pick.  n_col: the
+// output columns per instance.
 int jacobian_grids(Ctx *c, const hadi_problem *p, int G, const CallOut &o, int n_col, SweepDesc &d) {
     const int n0 = p->n_instances, m1 = p->m1, m2 = p->m2, n = n0 * G;
     int rc;
     const double *src_s, *src_ds;
     // (natOut stages delta_s here and takes J and the base prices after the sweep; prices / status: the pick.  All grown before
     // the sweep: growing one after it would drop the loop it just captured)
-    if ((rc = ensure(c, c->natOut, (size_t)n0 * std::max(m1, 6 * std::max(n_col, 1)) * 8)) || (rc = ensure(c, c->prices, n * 8)) ||
+    if ((rc = ensure(c, c->natOut, (size_t)n0 * std::max(m1, G * std::max(n_col, 1)) * 8)) || (rc = ensure(c, c->prices, n * 8)) ||
         (rc = ensure(c, c->status, n * sizeof(int))))
         return rc;
     if ((rc = to_device(c, p->memspace, p->vec_s, (size_t)n0 * (m1 + 1), c->natU, &src_s))) return rc;
@@ -1619,7 +1654,7 @@ int jacobian_grids(Ctx *c, const hadi_problem *p, int G, const CallOut &o, int n
     hipLaunchKernelGGL(hadi_bcast_rows_kernel, dim3(grid1d((size_t)n * m1)), dim3(256), 0, s, m1, n, src_ds,
                        ptr<int>(c->sel_a), ptr<double>(c->g_ds));
     if (c->t.device_vgrid) {
-        // every instance rebuilds its own v-grid on the device: V_0 for the groups 0..4, V_0 + eps for group 5
+        // every instance rebuilds its own v-grid on the device: V_0 + eps for group 5, V_0 for the others
         // (jacobian_computation.cpp:253,339-341)
         if ((rc = rebuild_v_device(c, n, m2, v0i))) return rc;
     } else {
@@ -1648,7 +1683,8 @@ int jacobian_common(Ctx *c, const hadi_problem *p, const CallExtras &x, const Ca
     pin_rewind(c);
     if (!p->U_0) return fail(c, HADI_ERR_INVALID, "U_0 (initial condition) is required for the Jacobian");
     if (!o.J || !o.base_prices) return fail(c, HADI_ERR_INVALID, "J / base_prices missing");
-    const int n0 = p->n_instances, m1 = p->m1, m2 = p->m2, G = 6;
+    // G groups, NC = G - 1 columns: the five Heston parameters, and with x.jump_cols lambda (6), mu_J (7), sigma_J (8)
+    const int n0 = p->n_instances, m1 = p->m1, m2 = p->m2, G = x.jump_cols ? HADI_JUMP_GROUPS : 6, NC = G - 1;
     if (!c->t.device_vgrid && p->V_0_i)
         return fail(c, HADI_ERR_INVALID, "V_0_i needs the device v-grid rebuild (hadi_set_tuning \"device_vgrid\", 1)");
     const int n = n0 * G;
@@ -1679,16 +1715,18 @@ int jacobian_common(Ctx *c, const hadi_problem *p, const CallExtras &x, const Ca
     double *dJ = o.J, *db = o.base_prices;
     if (p->memspace == HADI_MEM_HOST) {
         dJ = ptr<double>(c->natOut);
-        db = dJ + (size_t)n0 * 5 * std::max(n_col, 1);
+        db = dJ + (size_t)n0 * NC * std::max(n_col, 1);
     }
     const size_t nrow = (size_t)n0 * std::max(n_col, 1);  // rows of J
     if (x.ladder)  // (a sample call: the same kernel with n_snap * n_samp columns)
         hipLaunchKernelGGL(hadi_jacobian_ladder_rows_kernel, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, s, n0, n_col,
                            n_samp > 0 ? ptr<double>(c->samp_out) : ptr<double>(c->snap_out), eps, dJ, db);
+    else if (x.jump_cols)
+        hipLaunchKernelGGL(hadi_jacobian_rows8_kernel, dim3((n0 + 255) / 256), dim3(256), 0, s, n0, ptr<double>(c->prices), eps, dJ, db);
     else
         hipLaunchKernelGGL(hadi_jacobian_rows_kernel, dim3((n0 + 255) / 256), dim3(256), 0, s, n0, ptr<double>(c->prices), eps, dJ, db);
     if (p->memspace == HADI_MEM_HOST) {
-        HIP_TRY(c, hipMemcpyAsync(o.J, dJ, nrow * 5 * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(o.J, dJ, nrow * NC * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(o.base_prices, db, nrow * 8, hipMemcpyDeviceToHost, s));
     }
     // (a sample call: the v0 group located its own row and the s-grids are the same, so the caller's n0 instances decide as well)
@@ -1792,6 +1830,8 @@ int hadi_create(hadi_ctx **out, int device_id) {
     ok = ok && hipEventCreateWithFlags(&c->join_ev, hipEventDisableTiming) == hipSuccess;
     hadi_for_each_kernel([&](auto kernel) { ok = ok && raise_lds_limit(kernel) == hipSuccess; });
     ok = ok && raise_lds_limit(hadi_jump_kernel) == hipSuccess;  // (its strip of G: 66 KiB at m1 = 512, 132 KiB at m1 = 1024)
+    ok = ok && raise_lds_limit(hadi_jump_sel_kernel) == hipSuccess;       // (the same strip)
+    ok = ok && raise_lds_limit(hadi_lm_partials_n_kernel) == hipSuccess;  // (45 rows of 256 doubles at n_par = 8: 90 KiB)
     for (auto &e : c->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->wait_ev, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipHostMalloc(reinterpret_cast<void **>(&c->err_host), 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
@@ -2070,6 +2110,16 @@ int hadi_compute_jacobian_bates(hadi_ctx *ctx, const hadi_problem *p, double S_0
     return jacobian_common(c, p, x, o);
 }
 
+// The eight-column Jacobian: kappa, eta, sigma, rho, V_0, lambda, mu_J, sigma_J -- nine groups of one batched sweep.
+int hadi_compute_jacobian_bates_jumps(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, const hadi_jumps *jumps,
+                                      double *J, double *base_prices) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && !jumps) return fail(c, HADI_ERR_INVALID, "jump description missing");
+    CallExtras x; x.jumps = jumps; x.jump_cols = true; x.jump_eps = eps;
+    CallOut o; o.S_0 = S_0; o.V_0 = V_0; o.eps = eps; o.J = J; o.base_prices = base_prices;
+    return jacobian_common(c, p, x, o);
+}
+
 // The generator of one grid in natural order, through the kernels the sweep uses (host arrays in and out).
 int hadi_debug_jump_matrix(hadi_ctx *ctx, int m1, const double *vec_s, double mu, double sigma, double *G_out) {
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
@@ -2187,50 +2237,37 @@ HADI_VARIANT_WRAPPERS(dividends, HADI_DIV)
 HADI_VARIANT_WRAPPERS(american_dividends, HADI_AM_DIV)
 
 // ---- Levenberg-Marquardt normal equations (jacobian_computation.cpp:20-195) ---------------------------
-int hadi_lm_partials(int n, const double *J, const double *r, double *out) {
-    if (n < 0 || !out || (n > 0 && (!J || !r))) return HADI_ERR_INVALID;
-    for (int k = 0; k < 31; k++) out[k] = 0.0;
-    for (int i = 0; i < 5; i++)
-        for (int j = 0; j < 5; j++) {
+}  // extern "C"
+
+namespace {
+// [J^T J row-major NP^2][J^T r NP][sum r^2] of n rows of NP columns.
+template <int NP>
+void lm_partials_host(int n, const double *J, const double *r, double *out) {
+    for (int k = 0; k < hadi_lm_doubles(NP); k++) out[k] = 0.0;
+    for (int i = 0; i < NP; i++)
+        for (int j = 0; j < NP; j++) {
             double s = 0.0;
-            for (int k = 0; k < n; k++) s += J[(size_t)k * 5 + i] * J[(size_t)k * 5 + j];
-            out[i * 5 + j] = s;
+            for (int k = 0; k < n; k++) s += J[(size_t)k * NP + i] * J[(size_t)k * NP + j];
+            out[i * NP + j] = s;
         }
-    for (int i = 0; i < 5; i++) {
+    for (int i = 0; i < NP; i++) {
         double s = 0.0;
-        for (int k = 0; k < n; k++) s += J[(size_t)k * 5 + i] * r[k];
-        out[25 + i] = s;
+        for (int k = 0; k < n; k++) s += J[(size_t)k * NP + i] * r[k];
+        out[NP * NP + i] = s;
     }
     double s2 = 0.0;
     for (int k = 0; k < n; k++) s2 += r[k] * r[k];
-    out[30] = s2;
-    return HADI_OK;
+    out[NP * NP + NP] = s2;
 }
 
-int hadi_lm_partials_device(hadi_ctx *ctx, int n, const double *J, const double *model_prices, const double *market_prices,
-                            double *partial31) {
-    Ctx *c = reinterpret_cast<Ctx *>(ctx);
-    if (!c) return HADI_ERR_INVALID;
-    if (n < 0 || !partial31 || (n > 0 && (!J || !model_prices || !market_prices))) return fail(c, HADI_ERR_INVALID, "bad arguments");
-    DeviceGuard guard(c->device);
-    int rc = ensure(c, c->lm31, 31 * sizeof(double));
-    if (rc) return rc;
-    hipLaunchKernelGGL(hadi_lm_partials_kernel, dim3(1), dim3(256), (size_t)21 * 256 * sizeof(double), c->stream, n, J, model_prices,
-                       market_prices, ptr<double>(c->lm31));
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(partial31, c->lm31.p, 31 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return HADI_OK;
-}
-
-int hadi_lm_solve(const double *partial31, double lambda, double *delta5) {
-    if (!partial31 || !delta5) return HADI_ERR_INVALID;
-    constexpr int NP = 5;
+// delta = (J^T J with diagonal * (1 + lambda))^-1 J^T r by NP x NP partial-pivot elimination.
+template <int NP>
+void lm_solve_host(const double *part, double lambda, double *delta) {
     double A[NP * NP], b[NP];
-    for (int i = 0; i < NP * NP; i++) A[i] = partial31[i];
+    for (int i = 0; i < NP * NP; i++) A[i] = part[i];
     for (int i = 0; i < NP; i++) {
         A[i * NP + i] *= (1.0 + lambda);  // jacobian_computation.cpp:136-138
-        b[i] = partial31[25 + i];
+        b[i] = part[NP * NP + i];
     }
     for (int k = 0; k < NP; k++) {  // partial-pivot elimination, jacobian_computation.cpp:44-83
         int piv = k;
@@ -2257,9 +2294,69 @@ int hadi_lm_solve(const double *partial31, double lambda, double *delta5) {
         for (int col = k + 1; col < NP; col++) v -= A[k * NP + col] * b[col];
         b[k] = v;
     }
-    for (int i = 0; i < NP; i++) delta5[i] = b[i];
+    for (int i = 0; i < NP; i++) delta[i] = b[i];
+}
+
+// f.template operator()<NP>() for the width n_par = 1 .. 8 (the caller has checked it).
+template <class F>
+void for_width(int n_par, F f) {
+    switch (n_par) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 3: f(std::integral_constant<int, 3>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+        case 5: f(std::integral_constant<int, 5>()); break;
+        case 6: f(std::integral_constant<int, 6>()); break;
+        case 7: f(std::integral_constant<int, 7>()); break;
+        default: f(std::integral_constant<int, 8>()); break;
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int hadi_lm_partials_n(int n, int n_par, const double *J, const double *r, double *out) {
+    if (n_par < 1 || n_par > HADI_LM_MAX_PAR || n < 0 || !out || (n > 0 && (!J || !r))) return HADI_ERR_INVALID;
+    for_width(n_par, [&](auto w) { lm_partials_host<decltype(w)::value>(n, J, r, out); });
     return HADI_OK;
 }
+
+int hadi_lm_partials(int n, const double *J, const double *r, double *out) { return hadi_lm_partials_n(n, 5, J, r, out); }
+
+int hadi_lm_partials_device_n(hadi_ctx *ctx, int n, int n_par, const double *J, const double *model_prices, const double *market_prices,
+                              double *partials) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (!c) return HADI_ERR_INVALID;
+    if (n_par < 1 || n_par > HADI_LM_MAX_PAR) return fail(c, HADI_ERR_INVALID, "n_par = %d outside 1..%d", n_par, HADI_LM_MAX_PAR);
+    if (n < 0 || !partials || (n > 0 && (!J || !model_prices || !market_prices))) return fail(c, HADI_ERR_INVALID, "bad arguments");
+    DeviceGuard guard(c->device);
+    const size_t nd = (size_t)hadi_lm_doubles(n_par);
+    int rc = ensure(c, c->lm31, (size_t)hadi_lm_doubles(HADI_LM_MAX_PAR) * sizeof(double));
+    if (rc) return rc;
+    if (n_par == 5)  // (the kernel of hadi_lm_partials_device, under its own name)
+        hipLaunchKernelGGL(hadi_lm_partials_kernel, dim3(1), dim3(256), (size_t)21 * 256 * sizeof(double), c->stream, n, J, model_prices,
+                           market_prices, ptr<double>(c->lm31));
+    else
+        hipLaunchKernelGGL(hadi_lm_partials_n_kernel, dim3(1), dim3(256), (size_t)hadi_lm_sums(n_par) * 256 * sizeof(double), c->stream, n_par,
+                           n, J, model_prices, market_prices, ptr<double>(c->lm31));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(partials, c->lm31.p, nd * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return HADI_OK;
+}
+
+int hadi_lm_partials_device(hadi_ctx *ctx, int n, const double *J, const double *model_prices, const double *market_prices,
+                            double *partial31) {
+    return hadi_lm_partials_device_n(ctx, n, 5, J, model_prices, market_prices, partial31);
+}
+
+int hadi_lm_solve_n(int n_par, const double *partials, double lambda, double *delta) {
+    if (n_par < 1 || n_par > HADI_LM_MAX_PAR || !partials || !delta) return HADI_ERR_INVALID;
+    for_width(n_par, [&](auto w) { lm_solve_host<decltype(w)::value>(partials, lambda, delta); });
+    return HADI_OK;
+}
+
+int hadi_lm_solve(const double *partial31, double lambda, double *delta5) { return hadi_lm_solve_n(5, partial31, lambda, delta5); }
 
 int hadi_compute_parameter_update(int n, const double *J, const double *r, double lambda, double *delta5) {
     double part[31];

@@ -208,47 +208,76 @@ __global__ void __launch_bounds__(256) hadi_rebuild_variance_kernel(int m2, int 
 // gemv("T") and the residual kernel, jacobian_computation.cpp:117,154, heston_calibration.cpp:271-275):
 //   out[0..24] = J^T J (row-major), out[25..29] = J^T r, out[30] = sum r^2,  r = market - model.
 // One block, fixed-shape tree reduction: the result does not depend on scheduling (n is a few thousand at most).
-__global__ void __launch_bounds__(256) hadi_lm_partials_kernel(int n, const double *__restrict__ J,
-                                                               const double *__restrict__ model,
-                                                               const double *__restrict__ market, double *__restrict__ out) {
-    HADI_DYN_SMEM(double, redm);  // 21 x 256 doubles
+// The sums of NP parameters: NP (NP + 1) / 2 of the upper triangle, NP of J^T r, one of r^2 -- each a row of 256 doubles of LDS.
+HADI_HD constexpr int hadi_lm_sums(int NP) { return NP * (NP + 1) / 2 + NP + 1; }
+HADI_HD constexpr int hadi_lm_doubles(int NP) { return NP * NP + NP + 1; }  // what leaves: [J^T J row-major][J^T r][sum r^2]
+template <int NP>
+HADI_DEV HADI_FORCEINLINE void hadi_lm_partials_body(double *redm, int n, const double *__restrict__ J, const double *__restrict__ model,
+                                                     const double *__restrict__ market, double *__restrict__ out) {
+    constexpr int NT = NP * (NP + 1) / 2, NS = hadi_lm_sums(NP);
     double (*red)[256] = reinterpret_cast<double (*)[256]>(redm);
-    double acc[21];
+    double acc[NS];
 #pragma unroll
-    for (int q = 0; q < 21; q++) acc[q] = 0.0;
+    for (int q = 0; q < NS; q++) acc[q] = 0.0;
     for (int k = threadIdx.x; k < n; k += 256) {
-        double jr[5];
+        double jr[NP];
 #pragma unroll
-        for (int a = 0; a < 5; a++) jr[a] = J[(size_t)k * 5 + a];
+        for (int a = 0; a < NP; a++) jr[a] = J[(size_t)k * NP + a];
         const double r = market[k] - model[k];
         int q = 0;
 #pragma unroll
-        for (int a = 0; a < 5; a++)
+        for (int a = 0; a < NP; a++)
 #pragma unroll
-            for (int b = a; b < 5; b++) { acc[q] = fma(jr[a], jr[b], acc[q]); q++; }
+            for (int b = a; b < NP; b++) { acc[q] = fma(jr[a], jr[b], acc[q]); q++; }
 #pragma unroll
-        for (int a = 0; a < 5; a++) acc[15 + a] = fma(jr[a], r, acc[15 + a]);
-        acc[20] = fma(r, r, acc[20]);
+        for (int a = 0; a < NP; a++) acc[NT + a] = fma(jr[a], r, acc[NT + a]);
+        acc[NT + NP] = fma(r, r, acc[NT + NP]);
     }
 #pragma unroll
-    for (int q = 0; q < 21; q++) red[q][threadIdx.x] = acc[q];
+    for (int q = 0; q < NS; q++) red[q][threadIdx.x] = acc[q];
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s)
 #pragma unroll
-            for (int q = 0; q < 21; q++) red[q][threadIdx.x] += red[q][threadIdx.x + s];
+            for (int q = 0; q < NS; q++) red[q][threadIdx.x] += red[q][threadIdx.x + s];
         __syncthreads();
     }
     if (threadIdx.x == 0) {
         int q = 0;
-        for (int a = 0; a < 5; a++)
-            for (int b = a; b < 5; b++) {
-                out[a * 5 + b] = red[q][0];
-                out[b * 5 + a] = red[q][0];
+        for (int a = 0; a < NP; a++)
+            for (int b = a; b < NP; b++) {
+                out[a * NP + b] = red[q][0];
+                out[b * NP + a] = red[q][0];
                 q++;
             }
-        for (int a = 0; a < 5; a++) out[25 + a] = red[15 + a][0];
-        out[30] = red[20][0];
+        for (int a = 0; a < NP; a++) out[NP * NP + a] = red[NT + a][0];
+        out[NP * NP + NP] = red[NT + NP][0];
+    }
+}
+
+__global__ void __launch_bounds__(256) hadi_lm_partials_kernel(int n, const double *__restrict__ J,
+                                                               const double *__restrict__ model,
+                                                               const double *__restrict__ market, double *__restrict__ out) {
+    HADI_DYN_SMEM(double, redm);  // 21 x 256 doubles
+    hadi_lm_partials_body<5>(redm, n, J, model, market, out);
+}
+
+// The same for n_par = 1 .. 8 columns (hadi_lm_partials_device_n): out[0 .. n_par^2) = J^T J, then n_par of J^T r, then sum r^2.
+// hadi_lm_sums(n_par) x 256 doubles of LDS: 45 rows, 90 KiB, at n_par = 8 -- above the 64 KiB default (raise_lds_limit).
+__global__ void __launch_bounds__(256) hadi_lm_partials_n_kernel(int n_par, int n, const double *__restrict__ J,
+                                                                 const double *__restrict__ model,
+                                                                 const double *__restrict__ market, double *__restrict__ out) {
+    HADI_DYN_SMEM(double, redm);
+    switch (n_par) {  // (block-uniform)
+        case 1: hadi_lm_partials_body<1>(redm, n, J, model, market, out); break;
+        case 2: hadi_lm_partials_body<2>(redm, n, J, model, market, out); break;
+        case 3: hadi_lm_partials_body<3>(redm, n, J, model, market, out); break;
+        case 4: hadi_lm_partials_body<4>(redm, n, J, model, market, out); break;
+        case 5: hadi_lm_partials_body<5>(redm, n, J, model, market, out); break;
+        case 6: hadi_lm_partials_body<6>(redm, n, J, model, market, out); break;
+        case 7: hadi_lm_partials_body<7>(redm, n, J, model, market, out); break;
+        case 8: hadi_lm_partials_body<8>(redm, n, J, model, market, out); break;
+        default: break;
     }
 }
 
@@ -331,6 +360,17 @@ __global__ void __launch_bounds__(256) hadi_jacobian_rows_kernel(int n0, const d
     const double b = prices[k];
     base[k] = b;
     for (int g = 1; g <= 5; g++) J[(size_t)k * 5 + (g - 1)] = (prices[(size_t)g * n0 + k] - b) / eps;
+}
+
+// The same for the eight columns of hadi_compute_jacobian_bates_jumps: 9 n0 prices (groups: base, kappa, eta, sigma, rho, v0,
+// lambda, mu_J, sigma_J) -> J [n0][8], base [n0].
+__global__ void __launch_bounds__(256) hadi_jacobian_rows8_kernel(int n0, const double *__restrict__ prices, double eps,
+                                                                  double *__restrict__ J, double *__restrict__ base) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n0) return;
+    const double b = prices[k];
+    base[k] = b;
+    for (int g = 1; g <= 8; g++) J[(size_t)k * 8 + (g - 1)] = (prices[(size_t)g * n0 + k] - b) / eps;
 }
 
 // Diagnostics (hadi_debug_rcp): the reciprocal every line solve of the sweep uses, elementwise.

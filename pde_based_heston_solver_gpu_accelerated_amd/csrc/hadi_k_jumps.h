@@ -10,6 +10,8 @@
 //
 // hadi_jump_matrix_kernel builds G once per call in the operand order of the product kernel; hadi_jump_kernel is the product,
 // on the matrix core (hadi_mfma_f64_16x16x4), out of place: it reads the copy of U that the caller put into UT and writes U.
+// hadi_jump_sel_kernel is the same product (hadi_jump_step) for the nine groups of an eight-column Jacobian, which use three sets
+// of matrices.
 // Part of libhadi's device code: include through hadi_kernels.h (behind hadi_k_col.h).
 #pragma once
 
@@ -120,34 +122,38 @@ static inline unsigned hadi_jump_grid(const HadiLayout &L, int n_inst, int ipg) 
 // stores 16 consecutive slots per row.
 // Never written: pad slots, slots beyond m1, the identity rows past nrows.  Skipped, U bit-untouched: instances that have
 // finished (n > N_k) and instances with a_k = 0.  The summation order over the input slots is the slot order, whatever the batch.
-__global__ void __launch_bounds__(HADI_JUMP_THREADS) hadi_jump_kernel(HadiLayout L, int n_inst, int ipg, int inst0, int n_src,
-                                                                      const double *__restrict__ UT, double *__restrict__ U,
-                                                                      const double *__restrict__ G, long long g_stride,
-                                                                      const double *__restrict__ avec,
-                                                                      const HadiInstPar *__restrict__ ipar, int n) {
-    HADI_DYN_SMEM(double, smem);
+// The body is hadi_jump_step, for ngrp lists of instances: list_of(grp) names the instances of a block's list (start, stride,
+// count; instances of the launch), mat_of(inst) the matrix of an instance as its offset into G, in doubles.  Which instances
+// share a list never changes an instance's result.
+struct HadiJumpList { int start, stride, count; };
+template <class ListOf, class MatOf>
+HADI_DEV HADI_FORCEINLINE void hadi_jump_step(double *smem, const HadiLayout &L, int ngrp, const double *__restrict__ UT,
+                                              double *__restrict__ U, const double *__restrict__ G, const double *__restrict__ avec,
+                                              const HadiInstPar *__restrict__ ipar, int n, ListOf list_of, MatOf mat_of) {
     const int kg = hadi_jump_kg(L), nib = hadi_jump_nib(L), rowp = L.rowp, nrows = L.nrows;
     double *const Gs = smem, *const Us = smem + (size_t)kg * 64;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // The 16-slot blocks of an instance all read the instance's old field: consecutive logical ids go to ONE XCD, whose L2 then
     // holds that field (1.1 MB at 512x256) and the instance's matrix beside it.
     const int bid = hadi_xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    if (bid >= (n_inst + ipg - 1) / ipg * nib) return;  // (block-uniform: the padding of the grid)
+    if (bid >= ngrp * nib) return;  // (block-uniform: the padding of the grid)
     const int grp = bid / nib, ib = bid - grp * nib;
+    const HadiJumpList li = list_of(grp);
     const int ntile = kg / (HADI_JUMP_KC / 4);
     // this thread's share of a tile of U: rows lr + 16 q (q < 4), the slot pair (kc + lc, kc + lc + 1)
     const int lr = tid >> 4, lc = 2 * (tid & 15);
     // what this lane owns of the result: rows 16 wave + 4 r + (lane >> 4), output slot so
     const int so = 16 * ib + (lane & 15), io = so < rowp ? hadi_slot_to_i(L, so) : -1;
     const bool so_ok = io >= 0 && io <= L.m1;
-    long long cur = -1;  // the matrix whose strip is staged
-    for (int inst = grp * ipg; inst < n_inst && inst < (grp + 1) * ipg; inst++) {
+    long long cur = -1;  // the matrix whose strip is staged (its offset)
+    for (int c = 0; c < li.count; c++) {
+        const int inst = li.start + c * li.stride;
         const double a = avec[inst];
         if (a == 0.0 || n > ipar[inst].N) continue;  // (block-uniform)
-        const long long mat = g_stride ? (long long)((inst0 + inst) % n_src) : 0;
+        const long long mat = mat_of(inst);
         if (mat != cur) {
             __syncthreads();  // (nobody still reads the strip of the previous matrix)
-            const double2 *__restrict__ src = reinterpret_cast<const double2 *>(G + mat * g_stride + (size_t)ib * kg * 64);
+            const double2 *__restrict__ src = reinterpret_cast<const double2 *>(G + mat + (size_t)ib * kg * 64);
             double2 *dst = reinterpret_cast<double2 *>(Gs);
             for (int e = tid; e < kg * 32; e += HADI_JUMP_THREADS) dst[e] = src[e];
             cur = mat;
@@ -196,4 +202,73 @@ __global__ void __launch_bounds__(HADI_JUMP_THREADS) hadi_jump_kernel(HadiLayout
             }
         }
     }
+}
+
+// hadi_jump_kernel's lists: ipg consecutive instances each.
+HADI_HD inline HadiJumpList hadi_jump_run(int n_inst, int ipg, int grp) {
+    const int rest = n_inst - grp * ipg;
+    return HadiJumpList{grp * ipg, 1, rest < ipg ? rest : ipg};
+}
+
+__global__ void __launch_bounds__(HADI_JUMP_THREADS) hadi_jump_kernel(HadiLayout L, int n_inst, int ipg, int inst0, int n_src,
+                                                                      const double *__restrict__ UT, double *__restrict__ U,
+                                                                      const double *__restrict__ G, long long g_stride,
+                                                                      const double *__restrict__ avec,
+                                                                      const HadiInstPar *__restrict__ ipar, int n) {
+    HADI_DYN_SMEM(double, smem);
+    hadi_jump_step(smem, L, (n_inst + ipg - 1) / ipg, UT, U, G, avec, ipar, n, [=](int grp) { return hadi_jump_run(n_inst, ipg, grp); },
+                   [=](int inst) { return g_stride ? (long long)((inst0 + inst) % n_src) * g_stride : 0ll; });
+}
+
+// ---- the nine groups of an eight-column Jacobian (hadi_compute_jacobian_bates_jumps) --------------------------------------------
+// The batch is 9 groups of n_src source instances, instance k = group k / n_src, source k % n_src.  The groups 0 .. 6 (base, kappa,
+// eta, sigma, rho, V_0, lambda) use the matrices of (mu, sigma), group 7 those of (mu + eps, sigma), group 8 those of (mu, sigma +
+// eps): three sets of `per` matrices, G [3][per], per = n_src (one matrix per source instance and set) or 1 (one per set, shared by
+// the batch).
+#define HADI_JUMP_GROUPS 9
+#define HADI_JUMP_SETS 3
+HADI_HD inline int hadi_jump_set(int g) { return g <= 6 ? 0 : g - 6; }
+// A launch covers the instances inst0 .. inst0 + n_inst of the batch (a sub-batch).  share = 0: the lists are cap consecutive
+// instances, as hadi_jump_kernel's.  share = 1 (per = n_src only): the instances of ONE source instance that fall into the launch
+// and use the same matrix ride on one staged strip -- source `t` of the launch's first min(n_inst, n_src) instances owns
+// nq = ceil(7 / cap) + 2 lists: its set-0 instances t, t + n_src, ... in chunks of cap, then its group-7 and its group-8 instance
+// (a list may be empty: its blocks return at once).
+struct HadiJumpSel { int inst0, n_src, per, share, cap; };
+HADI_HD inline int hadi_jump_sel_nq(const HadiJumpSel &q) { return (7 + q.cap - 1) / q.cap + 2; }
+HADI_HD inline int hadi_jump_sel_ngrp(const HadiJumpSel &q, int n_inst) {
+    if (!q.share) return (n_inst + q.cap - 1) / q.cap;
+    return (n_inst < q.n_src ? n_inst : q.n_src) * hadi_jump_sel_nq(q);
+}
+HADI_HD inline HadiJumpList hadi_jump_sel_list(const HadiJumpSel &q, int n_inst, int grp) {
+    if (!q.share) return hadi_jump_run(n_inst, q.cap, grp);
+    const int nq = hadi_jump_sel_nq(q), t = grp / nq, slot = grp - t * nq;
+    const int g0 = (q.inst0 + t) / q.n_src;                // the group of the owner's first instance of the launch
+    const int C = (n_inst - t + q.n_src - 1) / q.n_src;    // its instances in the launch: groups g0 .. g0 + C - 1
+    int c0 = 7 - g0;                                       // ... of which the first c0 are of set 0
+    c0 = c0 < 0 ? 0 : (c0 > C ? C : c0);
+    if (slot < nq - 2) {
+        const int rest = c0 - slot * q.cap;
+        return HadiJumpList{t + slot * q.cap * q.n_src, q.n_src, rest < 0 ? 0 : (rest < q.cap ? rest : q.cap)};
+    }
+    const int c = (slot == nq - 2 ? 7 : 8) - g0;
+    return HadiJumpList{t + c * q.n_src, q.n_src, (c >= 0 && c < C) ? 1 : 0};
+}
+static inline unsigned hadi_jump_sel_grid(const HadiLayout &L, const HadiJumpSel &q, int n_inst) {
+    return ((unsigned)hadi_jump_sel_ngrp(q, n_inst) * hadi_jump_nib(L) + 7u) & ~7u;
+}
+
+// hadi_jump_kernel for such a batch: instance inst0 + inst uses matrix hadi_jump_set(group) * per + (per > 1 ? source : 0).  Per
+// instance the arithmetic and the summation order are hadi_jump_kernel's: the two share hadi_jump_step.
+__global__ void __launch_bounds__(HADI_JUMP_THREADS) hadi_jump_sel_kernel(HadiLayout L, int n_inst, HadiJumpSel q,
+                                                                          const double *__restrict__ UT, double *__restrict__ U,
+                                                                          const double *__restrict__ G, long long g_stride,
+                                                                          const double *__restrict__ avec,
+                                                                          const HadiInstPar *__restrict__ ipar, int n) {
+    HADI_DYN_SMEM(double, smem);
+    hadi_jump_step(smem, L, hadi_jump_sel_ngrp(q, n_inst), UT, U, G, avec, ipar, n,
+                   [=](int grp) { return hadi_jump_sel_list(q, n_inst, grp); },
+                   [=](int inst) {
+                       const int k = q.inst0 + inst, g = k / q.n_src;
+                       return (long long)(hadi_jump_set(g) * q.per + (q.per > 1 ? k - g * q.n_src : 0)) * g_stride;
+                   });
 }

@@ -33,6 +33,7 @@ struct HadiHandleTuning {
     int resident_sweep = -1;   // resident sweep (hadi_sweep_resident: both passes of every step in one launch, one block per instance): -1 automatic, 0 never, 1 wherever the sub-batch is eligible
     int debug_fault = 0;       // test hook: HADI_DEBUG_* bits handed to the sweep kernels
     int device_vgrid = 1;      // compute_base_prices / compute_jacobian: v-grids rebuilt per instance on the device
+    int jump_share = 1;        // eight-column Bates Jacobian, per-instance matrices: the groups 0 .. 6 of a source instance ride on one staged strip of G
     HadiTuning tune;           // kernel-selection overrides and the constants of the plan's cost model (hadi_plan.h)
 };
 
@@ -52,6 +53,7 @@ static inline const HadiTuneKey *hadi_tuning_key(const char *key) {
         {"cs_strips", &H::cs_strips, nullptr, HADI_TN_CS_STRIPS}, {"graph_max_melems", &H::graph_max_melems, nullptr, HADI_TN_NONNEG},
         {"tile_interleave", &H::tile_il, nullptr, HADI_TN_BOOL}, {"debug_fault", &H::debug_fault, nullptr, HADI_TN_ANY},
         {"team_launch", &H::team_launch, nullptr, HADI_TN_TRI}, {"resident_sweep", &H::resident_sweep, nullptr, HADI_TN_TRI},
+        {"jump_share", &H::jump_share, nullptr, HADI_TN_BOOL},
         {"strip", nullptr, &T::strip, HADI_TN_TRI}, {"row_tile", nullptr, &T::row_tile, HADI_TN_NONNEG},
         {"strip_blocks", nullptr, &T::strip_blocks, HADI_TN_NONNEG}, {"pair_strips", nullptr, &T::pair_strips, HADI_TN_TRI},
         {"col_groups", nullptr, &T::col_groups, HADI_TN_NONNEG}, {"small_waves", nullptr, &T::small_waves, HADI_TN_WAVES},
@@ -100,6 +102,7 @@ struct HadiRouteIn {
     int n_fix_steps = 0;                      // cliquet call: steps at whose end some instance fixes its strike (0: not a cliquet call)
     bool fix_weights = false;                 // ... and some fixing carries a non-zero weight: the packed payoff is read
     bool jumps = false;                       // Bates call with some a_k = lambda_k dt_k != 0: hadi_jump_kernel at the end of every step
+    int jump_sets = 1;                        // ... 3: the nine groups of an eight-column Jacobian -- the route does not depend on this, only its words do
     HadiHandleTuning t;
 };
 
@@ -413,7 +416,8 @@ static inline std::string hadi_describe_route(const HadiRoute &r, const HadiRout
     s += ex_stream;
     s += ko_stream;
     s += fix_stream;
-    if (r.jumps) s += "; Bates: hadi_jump_kernel (fp64 matrix core) behind the last column pass of every step";
+    if (r.jumps && in.jump_sets > 1) s += "; Bates: hadi_jump_sel_kernel (fp64 matrix core, three matrix sets picked by group) behind the last column pass of every step";
+    else if (r.jumps) s += "; Bates: hadi_jump_kernel (fp64 matrix core) behind the last column pass of every step";
     if (team == HADI_TEAM_FELL_BACK) s += " (after a failed instance-resident launch)";
     return s;
 }

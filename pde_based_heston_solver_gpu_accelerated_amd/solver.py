@@ -718,6 +718,21 @@ class HestonADI:
         del keep
         return J, base
 
+    def compute_jacobian_bates_jumps(self, S_0, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                     num_strikes, deviceGrids, U_0, jump_intensity, jump_mean, jump_vol, shared_grid=False, eps=1e-6,
+                                     variant=EU, dividends=None, per_instance=None, scheme=0):
+        """compute_jacobian_bates with the jump law among the columns: (J [n][8], base_prices [n]), columns kappa, eta, sigma, rho,
+        V_0, jump_intensity, jump_mean, jump_vol, forward differences with the one step eps -- nine groups of one batched sweep
+        over three sets of matrices (include/hadi.h).  (jump_intensity + eps) delta_t must not exceed 1."""
+        p = self._jacobian_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, deviceGrids,
+                                   U_0, dividends, per_instance, scheme)
+        j, keep = self._jumps(num_strikes, jump_intensity, jump_mean, jump_vol, shared_grid)
+        J, jptr = self._out(num_strikes, 8, U_0)
+        base, bptr = self._out(num_strikes, 1, U_0)
+        self._call(self._lib.hadi_compute_jacobian_bates_jumps, C.byref(p), float(S_0), float(V_0), float(eps), C.byref(j), jptr, bptr)
+        del keep
+        return J, base
+
     def debug_jump_matrix(self, vec_s, jump_mean, jump_vol):
         """The generator G [m1+1][m1+1] of the jump term on the grid vec_s, natural order, as the sweep's kernel builds it."""
         vs = np.ascontiguousarray(vec_s, dtype=np.float64)
@@ -913,35 +928,66 @@ def knock_out_payoff(grids, U, lower, upper, rebate=None):
 
 
 # ---- LM linear algebra (host; jacobian_computation.cpp:20-195) -------------------------------------
+LM_MAX_PAR = 8  # HADI_LM_MAX_PAR
+
+
+def _lm_width(n_par):
+    if not 1 <= n_par <= LM_MAX_PAR:
+        raise ValueError("the LM functions take 1 .. %d parameters, not %d" % (LM_MAX_PAR, n_par))
+    return n_par
+
+
+def _lm_width_of(partials):
+    """n_par of a partials vector [J^T J n_par^2][J^T r n_par][sum r^2]."""
+    for n_par in range(1, LM_MAX_PAR + 1):
+        if n_par * n_par + n_par + 1 == partials.size:
+            return n_par
+    raise ValueError("%d doubles are no partials vector of 1 .. %d parameters" % (partials.size, LM_MAX_PAR))
+
+
 def lm_partials(J, residuals):
-    """[J^T J (25), J^T r (5), sum r^2 (1)] of this rank's rows: the 31 doubles that are all-reduced."""
+    """[J^T J (n_par^2), J^T r (n_par), sum r^2 (1)] of this rank's rows, n_par = J.shape[1]: the doubles that are all-reduced
+    (31 at five parameters, 73 at eight)."""
     J, r = _host_f64(J), _host_f64(residuals)
-    out = np.empty(31)
-    rc = nat.lib().hadi_lm_partials(J.shape[0], J.ctypes.data_as(_dp), r.ctypes.data_as(_dp), out.ctypes.data_as(_dp))
+    n_par = _lm_width(J.shape[1]) if J.ndim == 2 else 5
+    out = np.empty(n_par * n_par + n_par + 1)
+    if n_par == 5:
+        rc = nat.lib().hadi_lm_partials(J.shape[0], J.ctypes.data_as(_dp), r.ctypes.data_as(_dp), out.ctypes.data_as(_dp))
+    else:
+        rc = nat.lib().hadi_lm_partials_n(J.shape[0], n_par, J.ctypes.data_as(_dp), r.ctypes.data_as(_dp), out.ctypes.data_as(_dp))
     if rc != nat.HADI_OK:
         raise HadiError(rc, "hadi_lm_partials")
     return out
 
 
 def lm_partials_device(solver, J, model_prices, market_prices):
-    """The same 31 doubles reduced on the GPU from device-resident J [n][5], model prices [n] and market prices [n]
-    (CUDA tensors): only 31 doubles leave the device per LM iteration (hadi_lm_partials_device)."""
+    """The same doubles reduced on the GPU from device-resident J [n][n_par], model prices [n] and market prices [n]
+    (CUDA tensors): only they leave the device per LM iteration (hadi_lm_partials_device, hadi_lm_partials_device_n)."""
     n = int(J.shape[0])
-    for t, name, cnt in ((J, "J", 5 * n), (model_prices, "model_prices", n), (market_prices, "market_prices", n)):
+    n_par = _lm_width(int(J.shape[1])) if J.dim() == 2 else 5
+    for t, name, cnt in ((J, "J", n_par * n), (model_prices, "model_prices", n), (market_prices, "market_prices", n)):
         _check_array(t, name, cnt)
         if not _is_device(t):
             raise ValueError("%s must be a CUDA tensor" % name)
     solver.wait_stream()
-    out = np.empty(31)
-    solver._call(solver._lib.hadi_lm_partials_device, n, C.c_void_p(J.data_ptr()), C.c_void_p(model_prices.data_ptr()),
-                 C.c_void_p(market_prices.data_ptr()), out.ctypes.data_as(_dp))
+    out = np.empty(n_par * n_par + n_par + 1)
+    ptrs = (C.c_void_p(J.data_ptr()), C.c_void_p(model_prices.data_ptr()), C.c_void_p(market_prices.data_ptr()), out.ctypes.data_as(_dp))
+    if n_par == 5:
+        solver._call(solver._lib.hadi_lm_partials_device, n, *ptrs)
+    else:
+        solver._call(solver._lib.hadi_lm_partials_device_n, n, n_par, *ptrs)
     return out
 
 
-def lm_solve(partials31, lam):
-    part = _host_f64(partials31)
-    delta = np.empty(5)
-    rc = nat.lib().hadi_lm_solve(part.ctypes.data_as(_dp), float(lam), delta.ctypes.data_as(_dp))
+def lm_solve(partials, lam):
+    """delta [n_par] from a partials vector of lm_partials' layout; n_par follows from its length."""
+    part = _host_f64(partials)
+    n_par = _lm_width_of(part)
+    delta = np.empty(n_par)
+    if n_par == 5:
+        rc = nat.lib().hadi_lm_solve(part.ctypes.data_as(_dp), float(lam), delta.ctypes.data_as(_dp))
+    else:
+        rc = nat.lib().hadi_lm_solve_n(n_par, part.ctypes.data_as(_dp), float(lam), delta.ctypes.data_as(_dp))
     if rc != nat.HADI_OK:
         raise HadiError(rc, "hadi_lm_solve")
     return delta
