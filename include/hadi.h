@@ -557,7 +557,7 @@ int hadi_compute_jacobian_cliquet(hadi_ctx *ctx, const hadi_problem *p, double S
  * Jacobian row share their instance's matrix; hadi_compute_jacobian_bates keeps the five columns (kappa, eta, sigma, rho, V_0): the
  * jump parameters are inputs (hadi_compute_jacobian_bates_jumps below has them as columns).
  * If every a_k is 0 the call is the plain call bit for bit, on whatever route that takes; an instance
- * with a_k = 0 inside a jump call equals its plain solve bit for bit.  A jump call runs the streaming kernels followed by
+ * with a_k = 0 inside a jump call equals its plain solve bit for bit.  A jump call of this block (one without samples) runs the streaming kernels followed by
  * hadi_jump_kernel on the fp64 matrix core: never a whole-loop LDS kernel, hadi_sweep_resident or hadi_team_kernel.
  * hadi_bates_timestepping reads and writes p exactly as hadi_DO_timestepping does; the two launchers rebuild the v-grid and
  * honour V_0_i as hadi_compute_base_prices / hadi_compute_jacobian do.
@@ -589,6 +589,32 @@ int hadi_compute_jacobian_bates(hadi_ctx *ctx, const hadi_problem *p, double S_0
  * group 0 is. */
 int hadi_compute_jacobian_bates_jumps(hadi_ctx *ctx, const hadi_problem *p, double S_0, double V_0, double eps, const hadi_jumps *jumps,
                                       double *J, double *base_prices);
+/* A Bates strike x maturity surface from ONE sweep: the sample calls (hadi_sample_ladder, hadi_compute_base_prices_samples,
+ * hadi_compute_jacobian_samples) with the jump sub-step of hadi_bates_timestepping at the end of every step -- behind the step's last
+ * column pass, in front of the snapshot.  Nothing new is defined: a sample, the row j0, the matrices, shared_grid and its check, and
+ * the weights a_k = lambda_k delta_t_k are as stated above.  Jumps are multiplicative, so the problem is as homogeneous in (s, K) as
+ * Heston's: G depends on the s-grid through ratios only, and scales turn one sweep into every strike (only PROPORTIONAL dividends
+ * keep that).  Snapshot q equals the call with N = snap_steps[q].
+ *   out   [n][n_snap][n_samp]
+ *   J     [n][n_snap][n_samp][n_par], base [n][n_snap][n_samp].  n_par = 5: the six groups of hadi_compute_jacobian_bates; n_par = 8: the
+ *         nine groups and three matrix sets of hadi_compute_jacobian_bates_jumps, with its bumps, its "(lambda_k + eps) delta_t_k <= 1"
+ *         rule and its zero columns 6, 7 where lambda_k = 0; any other n_par is HADI_ERR_INVALID.  Every group's samples are located
+ *         on the group's own rebuilt v-grid, as in hadi_compute_jacobian_samples.
+ * Admitted: HADI_EU and HADI_DIV, calls with r_f = 0, puts, delta_t_i, V_0_i (the two launchers), the predictor-corrector schemes,
+ * both memory spaces.  Refused, each with its parent's status: N_i, HADI_AM / HADI_AM_DIV, HADI_STATE_FP32, call data with r_f != 0,
+ * grids that take the sequential passes, lambda_k delta_t_k > 1; a NULL struct or output is HADI_ERR_INVALID.
+ * If every a_k is 0 the call is the plain sample call bit for bit, on whatever route that takes, with the same words from
+ * hadi_describe_last_sweep; an instance with a_k = 0 inside a jump call equals its plain solve.
+ * Route: the streaming kernels with hadi_jump_kernel / hadi_jump_sel_kernel and then hadi_sample_kernel behind the step, or -- Douglas
+ * steps on a grid that hadi_small_kernel admits -- hadi_small_jump_kernel: the whole time loop in one launch, the sub-step on the
+ * fp64 matrix core out of LDS.  hadi_set_tuning "jump_small": 1 wherever admitted, 0 never, -1 (default) by batch size.  An instance's
+ * sub-step issues the same matrix instructions in the same order on either route. */
+int hadi_bates_sample_ladder(hadi_ctx *ctx, const hadi_problem *p, double V_0, const hadi_samples *samples, int n_snap,
+                             const int *snap_steps, const hadi_jumps *jumps, double *out);
+int hadi_compute_base_prices_bates_samples(hadi_ctx *ctx, const hadi_problem *p, double V_0, const hadi_samples *samples, int n_snap,
+                                           const int *snap_steps, const hadi_jumps *jumps, double *out);
+int hadi_compute_jacobian_bates_samples(hadi_ctx *ctx, const hadi_problem *p, double V_0, double eps, const hadi_samples *samples,
+                                        int n_snap, const int *snap_steps, const hadi_jumps *jumps, int n_par, double *J, double *base);
 /* diagnostics (tests): the natural-order generator G [m1 + 1][m1 + 1] of one grid, built by the kernel the sweep uses.
  * vec_s [m1 + 1] and G_out are HOST arrays. */
 int hadi_debug_jump_matrix(hadi_ctx *ctx, int m1, const double *vec_s, double mu, double sigma, double *G_out);

@@ -493,6 +493,55 @@ inline void compute_jacobian_bates_jumps(Handle &h, double S_0, double V_0, doub
     detail::check(h, hadi_compute_jacobian_bates_jumps(h.ctx, &p, S_0, V_0, eps, &j, J.data(), base_prices.data()));
 }
 
+// A Bates strike x maturity surface from one sweep (hadi_bates_sample_ladder and its two launchers; NOT in the reference): the
+// sample calls above with the jump sub-step at the end of every step, in front of the snapshot.  The argument order is the sample
+// functions' with `jumps` behind snap_steps.  out: [num_strikes][snap_steps.size()][n_samp].
+inline void bates_sample_ladder(Handle &h, double V_0, double /*T*/, double r_d, double r_f, double rho, double sigma, double kappa,
+                                double eta, int m1, int m2, int /*total_size*/, int N, double theta, double delta_t, int num_strikes,
+                                const GridViews &deviceGrids, const DO_Workspace &workspace, const Samples &samples,
+                                const std::vector<int> &snap_steps, const Jumps &jumps, std::vector<double> &out, int variant = HADI_EU,
+                                const std::vector<double> *U_0 = nullptr, const Dividends *div = nullptr, const PutStrikes *put = nullptr) {
+    const hadi_samples s = samples.view();
+    const hadi_jumps j = jumps.view(num_strikes);
+    out.resize((size_t)num_strikes * snap_steps.size() * s.n_samp);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  const_cast<double *>(workspace.U.data()), U_0 ? U_0->data() : nullptr, div, put);
+    detail::check(h, hadi_bates_sample_ladder(h.ctx, &p, V_0, &s, (int)snap_steps.size(), snap_steps.data(), &j, out.data()));
+}
+// ... with the v-grid rebuilt for V_0, as compute_base_prices does
+inline void compute_base_prices_bates_samples(Handle &h, double V_0, double /*T*/, double r_d, double r_f, double rho, double sigma,
+                                              double kappa, double eta, int m1, int m2, int /*total_size*/, int N, double theta,
+                                              double delta_t, int num_strikes, const GridViews &deviceGrids,
+                                              const DO_Workspace &workspace, const Samples &samples, const std::vector<int> &snap_steps,
+                                              const Jumps &jumps, std::vector<double> &out, int variant = HADI_EU,
+                                              const std::vector<double> *U_0 = nullptr, const Dividends *div = nullptr,
+                                              const PutStrikes *put = nullptr) {
+    const hadi_samples s = samples.view();
+    const hadi_jumps j = jumps.view(num_strikes);
+    out.resize((size_t)num_strikes * snap_steps.size() * s.n_samp);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  const_cast<double *>(workspace.U.data()), U_0 ? U_0->data() : nullptr, div, put);
+    detail::check(h, hadi_compute_base_prices_bates_samples(h.ctx, &p, V_0, &s, (int)snap_steps.size(), snap_steps.data(), &j, out.data()));
+}
+// J: [num_strikes][snap_steps.size()][n_samp][n_par], base: [num_strikes][snap_steps.size()][n_samp]; n_par = 8 with jump_columns
+// (kappa, eta, sigma, rho, V_0, lambda, mu_J, sigma_J), else 5
+inline void compute_jacobian_bates_samples(Handle &h, double V_0, double /*T*/, double r_d, double r_f, double rho, double sigma,
+                                           double kappa, double eta, int m1, int m2, int /*total_size*/, int N, double theta,
+                                           double delta_t, int num_strikes, const GridViews &deviceGrids, const std::vector<double> &U_0,
+                                           const Samples &samples, const std::vector<int> &snap_steps, const Jumps &jumps,
+                                           bool jump_columns, std::vector<double> &J, std::vector<double> &base, double eps = 1e-6,
+                                           int variant = HADI_EU, const Dividends *div = nullptr, const PutStrikes *put = nullptr) {
+    const hadi_samples s = samples.view();
+    const hadi_jumps j = jumps.view(num_strikes);
+    const int n_par = jump_columns ? 8 : 5;
+    J.resize((size_t)num_strikes * snap_steps.size() * s.n_samp * n_par);
+    base.resize((size_t)num_strikes * snap_steps.size() * s.n_samp);
+    hadi_problem p = detail::make(variant, num_strikes, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, deviceGrids,
+                                  nullptr, U_0.data(), div, put);
+    detail::check(h, hadi_compute_jacobian_bates_samples(h.ctx, &p, V_0, eps, &s, (int)snap_steps.size(), snap_steps.data(), &j, n_par,
+                                                         J.data(), base.data()));
+}
+
 // jacobian_computation.cpp:204-364 and the three variants.  J: [num_strikes][5], columns kappa, eta, sigma, rho, v0.
 inline void compute_jacobian(Handle &h, double S_0, double V_0, double, double r_d, double r_f, double rho, double sigma,
                              double kappa, double eta, int m1, int m2, int, int N, double theta, double delta_t,

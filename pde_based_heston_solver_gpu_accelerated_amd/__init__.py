@@ -16,7 +16,7 @@ from .solver import (HestonADI, DOWorkspace, Dividends, compute_parameter_update
                      strike_samples)
 from .distributed import Communicator, shard_range  # noqa: F401
 from .calibration import (CalibrationPoint, calibrate, calibrate_american, calibrate_american_dividends,  # noqa: F401
-                          calibrate_american_dividends_multi_maturity, calibrate_bates, calibrate_bates_jumps, calibrate_bermudan, calibrate_dividends, calibrate_european,
+                          calibrate_american_dividends_multi_maturity, calibrate_bates, calibrate_bates_jumps, calibrate_bates_surface, calibrate_bermudan, calibrate_dividends, calibrate_european,
                           calibrate_european_maturity_ladder, calibrate_european_multi_maturity, calibrate_european_surface,
                           clamp_jump_parameters, clamp_parameters,
                           export_calibration_csv, make_calibration_points, make_ladder_points)
@@ -29,7 +29,7 @@ __all__ = ["EU", "AM", "DIV", "AM_DIV", "CALL", "PUT", "lm_partials_device", "ST
            "calibrate_american", "calibrate_dividends", "calibrate_american_dividends",
            "calibrate_european_multi_maturity", "calibrate_american_dividends_multi_maturity",
            "make_calibration_points", "export_calibration_csv", "make_ladder_points", "calibrate_european_maturity_ladder",
-           "calibrate_european_surface", "strike_samples", "calibrate_bermudan", "calibrate_bates", "calibrate_bates_jumps", "clamp_jump_parameters", "exercise_steps", "knock_out_payoff", "monitoring_steps",
+           "calibrate_european_surface", "strike_samples", "calibrate_bermudan", "calibrate_bates", "calibrate_bates_jumps", "calibrate_bates_surface", "clamp_jump_parameters", "exercise_steps", "knock_out_payoff", "monitoring_steps",
            "fixing_steps", "local_return_payoff", "FIX_SHARES", "FIX_RETURN",
            "G_PRICE", "G_DELTA", "G_GAMMA", "G_DV", "G_DVV", "G_DSV",
            "G_THETA", "G_LAMBDA", "N_GREEKS", "GREEK_NAMES"]

@@ -98,6 +98,7 @@ EXPORTS = [
     "hadi_barrier_timestepping", "hadi_compute_base_prices_barrier", "hadi_compute_jacobian_barrier",
     "hadi_cliquet_timestepping", "hadi_compute_base_prices_cliquet", "hadi_compute_jacobian_cliquet",
     "hadi_bates_timestepping", "hadi_compute_base_prices_bates", "hadi_compute_jacobian_bates", "hadi_debug_jump_matrix",
+    "hadi_bates_sample_ladder", "hadi_compute_base_prices_bates_samples", "hadi_compute_jacobian_bates_samples",
     "hadi_compute_jacobian_bates_jumps", "hadi_lm_partials_n", "hadi_lm_partials_device_n", "hadi_lm_solve_n",
     "hadi_compute_base_prices", "hadi_compute_base_prices_american",
     "hadi_compute_base_prices_dividends", "hadi_compute_base_prices_american_dividends",
@@ -206,6 +207,12 @@ def _load(LIB_PATH):
             getattr(L, name).argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, _sp, C.c_int, _ip, C.c_void_p]
         L.hadi_compute_jacobian_samples.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, _sp, C.c_int, _ip,
                                                     C.c_void_p, C.c_void_p]
+    if hasattr(L, "hadi_bates_sample_ladder"):  # (likewise: a build from before the Bates surface calls)
+        _sp, _jp = C.POINTER(Samples), C.POINTER(Jumps)
+        for name in ("hadi_bates_sample_ladder", "hadi_compute_base_prices_bates_samples"):
+            getattr(L, name).argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, _sp, C.c_int, _ip, _jp, C.c_void_p]
+        L.hadi_compute_jacobian_bates_samples.argtypes = [C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, _sp, C.c_int, _ip,
+                                                          _jp, C.c_int, C.c_void_p, C.c_void_p]
     for sfx in ("", "_american", "_dividends", "_american_dividends"):
         getattr(L, "hadi_compute_base_prices" + sfx).argtypes = [
             C.c_void_p, C.POINTER(Problem), C.c_double, C.c_double, C.c_void_p]

@@ -12,6 +12,7 @@ normal equations are all-reduced (31 doubles per iteration, 1 double for the tri
     calibrate_bermudan                          no counterpart: European / dividend sweeps with exercise on chosen steps
     calibrate_european_maturity_ladder          no counterpart: all maturities of a strike from ONE sweep on a shared delta_t
     calibrate_bates, calibrate_bates_jumps      no counterpart: the Bates model, the jump law held fixed / fitted (8 parameters)
+    calibrate_bates_surface                     no counterpart: a Bates strike x maturity surface from ONE sweep per parameter group
 
 `solver` is anything with the mirrored launchers of solver.HestonADI (`compute_jacobian*`, `compute_base_prices*`).
 """
@@ -514,6 +515,81 @@ def calibrate_bates_jumps(solver, S_0, T, r_d, r_f, kappa, eta, sigma, rho, V_0,
                     dividends=dividends, max_iter=max_iter, tol=tol, scheme=scheme, launchers=launch,
                     extra=(jump_intensity, jump_mean, jump_vol), clamp_extra=lambda lj, mj, sj: clamp_jump_parameters(lj, mj, sj, delta_t),
                     solves_per_iteration=10, **kw)
+    res["jump_intensity"], res["jump_mean"], res["jump_vol"] = res.pop("extra")
+    return res
+
+
+def _bates_surface_launchers(solver, variant, r_d, r_f, m1, m2, theta, delta_t, snap_steps, grids, U_0, spots, scales, jumps, dividends,
+                             scheme=0):
+    """The closures of calibrate() over the Bates sample launchers: ONE instance, whose [1][maturity][strike] outputs are already in
+    the residual order m * len(strikes) + s.  jumps: None = the jump law is fitted (eight parameters, the closures take it behind
+    the five), else the fixed (jump_intensity, jump_mean, jump_vol)."""
+    total_size = (m1 + 1) * (m2 + 1)
+    N = int(snap_steps[-1])
+    kw = {"scales": scales, "variant": variant, "dividends": dividends}
+    if scheme:
+        kw["scheme"] = scheme
+
+    def jac(k, e, s, r, v, *rest):
+        law, eps = (rest[:3], rest[3]) if jumps is None else (jumps, rest[0])
+        J, base = solver.compute_jacobian_bates_samples(spots, v, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t, 1, grids,
+                                                        U_0, snap_steps, *law, jump_columns=jumps is None, eps=eps, **kw)
+        return J.reshape(-1, 8 if jumps is None else 5), base.reshape(-1)
+
+    def base(k, e, s, r, v, *rest):
+        ws = _WS()
+        ws.U = _clone(U_0)
+        return solver.compute_base_prices_bates_samples(spots, v, r_d, r_f, r, s, k, e, m1, m2, total_size, N, theta, delta_t, 1, grids,
+                                                        ws, snap_steps, *(rest if jumps is None else jumps), **kw).reshape(-1)
+
+    return jac, base
+
+
+def calibrate_bates_surface(solver, S_0, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, theta, base_strike, strikes, maturities,
+                            delta_t, grids, U_0, market_prices, jump_intensity, jump_mean, jump_vol, fit_jumps=True, dividends=None,
+                            max_iter=15, tol=None, delta_tol=None, n_total=None, scheme=0, **kw):
+    """calibrate_european_surface under the Bates model: `grids` / `U_0` hold ONE instance, built at `base_strike`, and every strike
+    of every maturity is read off its sweep through strike_samples.  Jumps are multiplicative, so the Bates problem is as
+    homogeneous in (s, K) as Heston's (the generator of the jump term depends on the s-grid through ratios only); with `dividends`
+    only PROPORTIONAL ones keep that, as strike_samples says of cash amounts.  A jump law is identified by the short-dated skew
+    ACROSS maturities, which is what this driver fits and a single-maturity driver cannot.
+    fit_jumps True: eight parameters -- the five and the scalars jump_intensity, jump_mean, jump_vol, which are the start values;
+    every iteration is one eight-column Jacobian (compute_jacobian_bates_samples: nine sweeps) and one trial
+    (compute_base_prices_bates_samples); 73 doubles are all-reduced; clamps beside clamp_parameters: clamp_jump_parameters with
+    this delta_t; the result carries jump_intensity, jump_mean, jump_vol.  fit_jumps False: the law is held fixed and the loop is
+    the five-column one (six sweeps and one).  `pde_solves` counts the sweeps actually run.  market_prices:
+    [len(maturities) * len(strikes)] in the order m * len(strikes) + s.  r_f must be 0 for calls (the ladder's rule); every
+    maturity is a whole number of steps of delta_t.  scheme / theta: see calibrate (without dividends only).
+    Measured on one MI355X: profiles/bates_surface_ab.txt (this driver's launchers against one compute_jacobian_bates_jumps /
+    compute_base_prices_bates call per maturity, and the two routes of the new call against each other)."""
+    for x, name in ((jump_intensity, "jump_intensity"), (jump_mean, "jump_mean"), (jump_vol, "jump_vol")):
+        if np.ndim(x) != 0:
+            raise ValueError("%s: calibrate_bates_surface takes one jump law, so a scalar" % name)
+    pts = make_ladder_points(strikes, maturities, delta_t)
+    n_s, n_m = len(strikes), len(maturities)
+    if grids.Vec_s.shape[0] != 1:
+        raise ValueError("a surface takes ONE grid, built at base_strike (%d grids)" % grids.Vec_s.shape[0])
+    market = np.asarray(market_prices, dtype=np.float64).reshape(-1)
+    if market.size != n_s * n_m:
+        raise ValueError("market_prices must hold len(maturities) * len(strikes) prices, maturity by maturity")
+    variant = DIV if dividends is not None and len(dividends) else EU
+    if scheme and variant != EU:
+        raise ValueError("scheme %r: the predictor-corrector schemes price European sweeps only" % (scheme,))
+    spots, scales = _solver.strike_samples(S_0, base_strike, strikes)
+    snap_steps = [pts[m * n_s].time_steps for m in range(n_m)]
+    t, dtol = multi_maturity_tolerances(n_total or len(pts))
+    law = (float(jump_intensity), float(jump_mean), float(jump_vol))
+    launch = _bates_surface_launchers(solver, variant, r_d, r_f, m1, m2, theta, delta_t, snap_steps, grids, U_0, spots, scales,
+                                      None if fit_jumps else law, dividends if variant == DIV else None, scheme=scheme)
+    common = dict(dividends=dividends, max_iter=max_iter, tol=t if tol is None else tol,
+                  delta_tol=dtol if delta_tol is None else delta_tol, scheme=scheme, launchers=launch)
+    common.update(kw)
+    if not fit_jumps:
+        return calibrate(solver, variant, S_0, None, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, None, theta, grids, U_0, market,
+                         **common)
+    res = calibrate(solver, variant, S_0, None, r_d, r_f, kappa, eta, sigma, rho, V_0, m1, m2, None, theta, grids, U_0, market,
+                    extra=law, clamp_extra=lambda lj, mj, sj: clamp_jump_parameters(lj, mj, sj, delta_t), solves_per_iteration=10,
+                    **common)
     res["jump_intensity"], res["jump_mean"], res["jump_vol"] = res.pop("extra")
     return res
 

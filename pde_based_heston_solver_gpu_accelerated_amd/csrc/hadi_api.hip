@@ -71,6 +71,7 @@ struct Ctx {
     // lognormal jumps (Bates calls): the generators in operand order [n_mat][hadi_jump_matrix_doubles] (hadi_jump_matrix_kernel), the
     // weights a_k = lambda_k dt_k [n], the (mu, sigma) pairs of the matrices [n_mat][2], the status word of the shared-grid promise
     DevBuf jmp_G, jmp_a, jmp_par, jmp_stat;
+    DevBuf jmp_mat;  // hadi_small_jump_kernel: every instance's matrix index [n]
     DevBuf snap_steps, snap_node, snap_out;  // maturity ladder: the snapshot steps, the instances' price nodes, the snapshots [n][n_snap]
     // sampled ladder: the spots [n][n_samp] and behind them the scales [n][n_samp] as staged; the tap records [n][n_samp] and behind
     // them the samples' flag words [n][n_samp] (hadi_sample_locate_kernel); the samples [n][n_snap][n_samp]
@@ -354,7 +355,8 @@ int grow_buffers(Ctx *c, Sweep &w) {
                       (rc = ensure(c, c->fix_mode, sizeof(int) * n)) || (rc = ensure(c, c->fix_c, 8 * n * pl.L.nrows_pad))))
         return rc;
     if (r.jumps && ((rc = ensure(c, c->jmp_G, 8 * (size_t)d.jmp_nmat * hadi_jump_matrix_doubles(pl.L))) || (rc = ensure(c, c->jmp_a, 8 * n)) ||
-                    (rc = ensure(c, c->jmp_par, 16 * (size_t)d.jmp_nmat)) || (rc = ensure(c, c->jmp_stat, sizeof(int)))))
+                    (rc = ensure(c, c->jmp_par, 16 * (size_t)d.jmp_nmat)) || (rc = ensure(c, c->jmp_stat, sizeof(int))) ||
+                    (rc = ensure(c, c->jmp_mat, sizeof(int) * n))))
         return rc;
     if (r.need_ut && (rc = ensure(c, c->UT, st))) return rc;
     if (r.need_f32 && ((rc = ensure(c, c->Uf, st / 2)) || (rc = ensure(c, c->Yf, st / 2)))) return rc;
@@ -661,16 +663,29 @@ int small_args(Ctx *c, const Sweep &w, HadiSmallArgs &sm) {
             sm.taps = samp_taps(c); sm.n_samp = d.n_samp; sm.samp_out = ptr<double>(c->samp_out);
         }
     }
+    if (w.r.kind == HADI_ROUTE_SMALL_JUMP) {  // the matrix of an instance: (set of its group) x per + (per > 1 ? source : 0), as hadi_jump_sel_kernel has it
+        const int per = d.jmp_nmat / d.jmp_sets;
+        std::vector<int> mat(d.n);
+        for (int k = 0; k < d.n; k++) mat[k] = (d.jmp_sets > 1 ? hadi_jump_set(k / d.n_src) : 0) * per + (per > 1 ? k % d.n_src : 0);
+        if ((rc = stage_to_device(c, c->jmp_mat.p, mat.data(), sizeof(int) * d.n))) return rc;
+        sm.jmp_G = ptr<double>(c->jmp_G); sm.jmp_a = ptr<double>(c->jmp_a); sm.jmp_mat = ptr<int>(c->jmp_mat);
+        sm.jmp_stride = (long long)hadi_jump_matrix_doubles(w.r.pl.L);
+    }
     return HADI_OK;
 }
 
-// Small grids: the whole instance fits in LDS (hadi_small_sch_kernel, hadi_small_kernel, hadi_small_seq_kernel, hadi_small_seq2_kernel).
+// Small grids: the whole instance fits in LDS (hadi_small_jump_kernel, hadi_small_sch_kernel, hadi_small_kernel, hadi_small_seq_kernel, hadi_small_seq2_kernel).
 int run_small(Ctx *c, Sweep &w) {
     const SweepDesc &d = w.d;
     const HadiLayout &L = w.r.pl.L;
     HadiSel sel{nullptr, (unsigned)d.n, 64, 0};
     HadiLoopFn fn;
-    if (w.r.kind == HADI_ROUTE_SMALL_SCH) {
+    if (w.r.kind == HADI_ROUTE_SMALL_JUMP) {
+        const int W = w.r.small_waves == 8 ? 8 : 4;
+        fn = hadi_small_jump_fn(L.B, W);
+        if (!fn) return fail(c, HADI_ERR_INTERNAL, "no small-grid jump kernel for grid %dx%d", d.m1, d.m2);
+        sel.block = 64 * W; sel.smem = w.r.pl.smem_small_eu;
+    } else if (w.r.kind == HADI_ROUTE_SMALL_SCH) {
         fn = hadi_small_sch_fn(L.B, hadi_route_sch(d.scheme));
         if (!fn) return fail(c, HADI_ERR_INTERNAL, "no small-grid kernel of scheme %d for grid %dx%d", d.scheme, d.m1, d.m2);
         sel.smem = hadi_small_sch_smem(L);
@@ -1719,7 +1734,7 @@ int jacobian_common(Ctx *c, const hadi_problem *p, const CallExtras &x, const Ca
     }
     const size_t nrow = (size_t)n0 * std::max(n_col, 1);  // rows of J
     if (x.ladder)  // (a sample call: the same kernel with n_snap * n_samp columns)
-        hipLaunchKernelGGL(hadi_jacobian_ladder_rows_kernel, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, s, n0, n_col,
+        hipLaunchKernelGGL(hadi_jacobian_ladder_rows_kernel, dim3((unsigned)((nrow + 255) / 256)), dim3(256), 0, s, n0, n_col, NC,
                            n_samp > 0 ? ptr<double>(c->samp_out) : ptr<double>(c->snap_out), eps, dJ, db);
     else if (x.jump_cols)
         hipLaunchKernelGGL(hadi_jacobian_rows8_kernel, dim3((n0 + 255) / 256), dim3(256), 0, s, n0, ptr<double>(c->prices), eps, dJ, db);
@@ -1749,7 +1764,7 @@ void release_handle(Ctx *c) {
                       &c->src_dv, &c->sel_a, &c->sel_b, &c->v0_i, &c->natU, &c->natU0, &c->natOut, &c->prices,
                       &c->status, &c->div_flag, &c->div_amt, &c->div_pct, &c->V, &c->R1, &c->C2, &c->pay_mis, &c->Uf, &c->Yf,
                       &c->order, &c->lm31, &c->team, &c->rs_tab, &c->snap_steps, &c->snap_node, &c->snap_out, &c->samp_in, &c->samp_tap, &c->samp_out, &c->ex_flag,
-                      &c->ko_flag, &c->ko_bounds, &c->ko_iab, &c->ko_rebate, &c->jmp_G, &c->jmp_a, &c->jmp_par, &c->jmp_stat,
+                      &c->ko_flag, &c->ko_bounds, &c->ko_iab, &c->ko_rebate, &c->jmp_G, &c->jmp_a, &c->jmp_par, &c->jmp_stat, &c->jmp_mat,
                       &c->fix_flag, &c->fix_w, &c->fix_ref, &c->fix_iref, &c->fix_mode, &c->fix_c};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
@@ -2228,6 +2243,40 @@ int hadi_compute_jacobian_samples(hadi_ctx *ctx, const hadi_problem *p, double V
     Ctx *c = reinterpret_cast<Ctx *>(ctx);
     if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
     CallExtras x; x.ladder = true; x.n_snap = n_snap; x.snap_steps = snap_steps; x.sampled = true; x.samples = samples;
+    CallOut o; o.V_0 = V_0; o.eps = eps; o.J = J; o.base_prices = base;
+    return jacobian_common(c, p, x, o);
+}
+
+// ---- Bates surface: the sample calls with the jump sub-step at the end of every step, behind the step's last column pass and in
+// front of the snapshot.  Both features' fields of CallExtras are filled; nothing else is new.
+int hadi_bates_sample_ladder(hadi_ctx *ctx, const hadi_problem *p, double V_0, const hadi_samples *samples, int n_snap, const int *snap_steps,
+                             const hadi_jumps *jumps, double *out) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && !jumps) return fail(c, HADI_ERR_INVALID, "jump description missing");
+    if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
+    CallExtras x; x.ladder = true; x.n_snap = n_snap; x.snap_steps = snap_steps; x.sampled = true; x.samples = samples; x.jumps = jumps;
+    CallOut o; o.pick = true; o.V_0 = V_0; o.prices = out;
+    return solve_common(c, p, x, o);
+}
+
+int hadi_compute_base_prices_bates_samples(hadi_ctx *ctx, const hadi_problem *p, double V_0, const hadi_samples *samples, int n_snap,
+                                           const int *snap_steps, const hadi_jumps *jumps, double *out) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && !jumps) return fail(c, HADI_ERR_INVALID, "jump description missing");
+    if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
+    CallExtras x; x.ladder = true; x.n_snap = n_snap; x.snap_steps = snap_steps; x.sampled = true; x.samples = samples; x.jumps = jumps;
+    CallOut o; o.rebuild_v = true; o.pick = true; o.V_0 = V_0; o.prices = out;
+    return solve_common(c, p, x, o);
+}
+
+int hadi_compute_jacobian_bates_samples(hadi_ctx *ctx, const hadi_problem *p, double V_0, double eps, const hadi_samples *samples, int n_snap,
+                                        const int *snap_steps, const hadi_jumps *jumps, int n_par, double *J, double *base) {
+    Ctx *c = reinterpret_cast<Ctx *>(ctx);
+    if (c && !jumps) return fail(c, HADI_ERR_INVALID, "jump description missing");
+    if (c && n_par != 5 && n_par != 8) return fail(c, HADI_ERR_INVALID, "n_par must be 5 or 8 (is %d)", n_par);
+    if (c && (n_snap < 1 || !snap_steps)) return fail(c, HADI_ERR_INVALID, "need 1 <= n_snap <= N snapshot steps");
+    CallExtras x; x.ladder = true; x.n_snap = n_snap; x.snap_steps = snap_steps; x.sampled = true; x.samples = samples; x.jumps = jumps;
+    if (n_par == 8) { x.jump_cols = true; x.jump_eps = eps; }
     CallOut o; o.V_0 = V_0; o.eps = eps; o.J = J; o.base_prices = base;
     return jacobian_common(c, p, x, o);
 }

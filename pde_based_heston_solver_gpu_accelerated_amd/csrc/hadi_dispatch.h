@@ -123,8 +123,18 @@ static inline bool hadi_small_sch_admits(const HadiLayout &L) {
     return L.G == 1 && L.B <= 2 && L.P == 1 && hadi_small_sch_smem(L) <= (size_t)160 * 1024;
 }
 
+// The whole-loop LDS kernel of a sampled Bates ladder (hadi_small_jump_kernel, hadi_k_small.h): hadi_small_kernel<B, W, false> with the
+// jump sub-step inside the time loop, launched from run_sweep outside the table as hadi_small_sch_kernel is.  B: 1 or 2 nodes per
+// lane; W: 4 or 8 wavefronts per instance.  Null where no such instantiation exists: an error for the caller, never a fallback.
+static inline HadiLoopFn hadi_small_jump_fn(int B, int W) {
+    if (B == 1) return W == 4 ? hadi_small_jump_kernel<1, 4> : W == 8 ? hadi_small_jump_kernel<1, 8> : (HadiLoopFn) nullptr;
+    if (B == 2) return W == 4 ? hadi_small_jump_kernel<2, 4> : W == 8 ? hadi_small_jump_kernel<2, 8> : (HadiLoopFn) nullptr;
+    return nullptr;
+}
+
 // Calls f with the address of every kernel of the table, of the two instance-resident team kernels (their own argument
-// block) and of the predictor-corrector schemes' LDS-resident kernels (hadi_small_sch_fn).  hadi_create raises the
+// block), of the predictor-corrector schemes' LDS-resident kernels (hadi_small_sch_fn) and of the sampled Bates ladder's
+// (hadi_small_jump_fn).  hadi_create raises the
 // dynamic-LDS limit of each: no kernel that needs more than the default can be left out.
 template <class F>
 static void hadi_for_each_kernel(F f) {
@@ -138,6 +148,8 @@ static void hadi_for_each_kernel(F f) {
     f(hadi_team_kernel<4>);
     for (int B = 1; B <= 2; B++)
         for (int sch = HADI_SCH_CS; sch <= HADI_SCH_HV; sch++) f(hadi_small_sch_fn(B, sch));
+    for (int B = 1; B <= 2; B++)
+        for (int W = 4; W <= 8; W += 4) f(hadi_small_jump_fn(B, W));
 }
 
 // A selected kernel and its launch geometry.  k is null when the table holds no such instantiation: an error, never a fallback.

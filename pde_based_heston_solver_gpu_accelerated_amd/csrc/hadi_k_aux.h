@@ -340,15 +340,16 @@ __global__ void __launch_bounds__(64) hadi_snap_kernel(HadiLayout L, int n_inst,
     out[(size_t)inst * n_snap + q] = off >= 0 ? U[(size_t)inst * L.inst_stride + off] : nan("");
 }
 
-// hadi_jacobian_rows_kernel for a ladder: prices [6 n0][n_snap] -> J [n0][n_snap][5], base [n0][n_snap].
-__global__ void __launch_bounds__(256) hadi_jacobian_ladder_rows_kernel(int n0, int n_snap, const double *__restrict__ prices,
+// hadi_jacobian_rows_kernel for a ladder: prices [(n_par + 1) n0][n_snap] -> J [n0][n_snap][n_par], base [n0][n_snap].  n_par: 5,
+// or 8 for the nine groups of a Bates call with the jump law among its columns (hadi_compute_jacobian_bates_samples).
+__global__ void __launch_bounds__(256) hadi_jacobian_ladder_rows_kernel(int n0, int n_snap, int n_par, const double *__restrict__ prices,
                                                                         double eps, double *__restrict__ J,
                                                                         double *__restrict__ base) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n0 * n_snap) return;
     const double b = prices[e];
     base[e] = b;
-    for (int g = 1; g <= 5; g++) J[(size_t)e * 5 + (g - 1)] = (prices[(size_t)g * n0 * n_snap + e] - b) / eps;
+    for (int g = 1; g <= n_par; g++) J[(size_t)e * n_par + (g - 1)] = (prices[(size_t)g * n0 * n_snap + e] - b) / eps;
 }
 
 // J(k, param) = (perturbed price - base price) / eps from the 6 n0 prices of a flattened Jacobian sweep (groups: base, kappa,

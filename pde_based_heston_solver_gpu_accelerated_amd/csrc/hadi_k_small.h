@@ -55,6 +55,13 @@ struct HadiSmallArgs {
     const HadiTap *taps = nullptr;
     int n_samp = 0;
     double *samp_out = nullptr;
+    // Lognormal jumps (hadi_bates_sample_ladder; nullptr = none, hadi_small_jump_kernel only): at the END of every step n <= N_k,
+    // behind the column pass and in front of the snapshot, instance k with jmp_a[k] != 0 takes U_row <- U_row + jmp_a[k] (G U_row)
+    // on every v-row, G the matrix jmp_mat[k] of jmp_G (operand order, hadi_k_jumps.h; jmp_stride doubles per matrix)
+    const double *jmp_G = nullptr;
+    const double *jmp_a = nullptr;
+    const int *jmp_mat = nullptr;
+    long long jmp_stride = 0;
 };
 
 // The ladder's running cursor of a whole-loop kernel: wave-uniform (kernel arguments and the step counter only).  `next` is the
@@ -89,8 +96,69 @@ HADI_DEV inline void hadi_sample_lds(const HadiSmallArgs &sm, const HadiLayout &
     }
 }
 
-template <int B, int W, bool AMER>
-__global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, HadiSmallArgs sm) {
+// The jump sub-step of a whole-loop kernel, hadi_jump_step's product on the LDS-resident state: Ul <- Yl + a G Yl on every v-row,
+// Yl the copy of U that the caller made (out of place: every tile reads whole rows of the old field).  One 16-row x 16-output-slot
+// accumulator tile per wavefront at a time, the (row block, slot block) tiles dealt round-robin over the W wavefronts; the K loop
+// runs over ALL kg groups of 4 input slots in ascending slot order, the padding included -- the very sequence of matrix
+// instructions hadi_jump_step issues for the tile, so an instance's sub-step does not depend on the route.  A: lane 16 k + j reads
+// Yl[(j0 + j) rowp + k0 + k], masked as hadi_jump_step's fetch masks (rows >= nrows, slots past the pitch and slots that hold no
+// node read as 0.0: behind Yl's nrows rows lie other tables, and the pad slots hold what the column pass left there).  B: the 64
+// contiguous doubles of G's (block, group) cell straight from global memory (one coalesced 512-byte cell per instruction; a
+// matrix is 61 KB at 50x25 and stays in L2), a chunk of HADI_JUMP_KC / 4 cells in flight ahead of the matrix core.
+// Never written: pad slots, slots beyond m1, the halo rows.  Row i = 0 of G is zero: that column keeps its bits.
+template <int W>
+HADI_DEV HADI_FORCEINLINE void hadi_small_jump_stage(const HadiLayout &L, const double *Yl, double *Ul, const double *__restrict__ Gm,
+                                                     double a, int wave, int lane) {
+    // cells per chunk (kg is a multiple of it).  Measured (profiles/bates_surface_ab.txt): a tile's whole strip in flight at once --
+    // 24 or 40 cells -- was SLOWER than this chunk of 8 with the next chunk's loads behind it (one 50x25 instance x 100 steps 1.94 ->
+    // 2.10 ms, 100x20 3.63 -> 4.13 ms), and was not kept.
+    constexpr int KC = HADI_JUMP_KC / 4;
+    const int kg = hadi_jump_kg(L), nib = hadi_jump_nib(L), rowp = L.rowp, nrows = L.nrows;
+    const int ntiles = ((nrows + 15) / 16) * nib;
+    for (int t = wave; t < ntiles; t += W) {  // (wave-uniform)
+        const int rb = t / nib, sb = t - rb * nib;
+        const double *__restrict__ bp = Gm + (size_t)sb * kg * 64 + lane;
+        const int ja = 16 * rb + (lane & 15);  // the row of this lane's A operands
+        const double *ap = Yl + (size_t)(ja < nrows ? ja : 0) * rowp;
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        double bn[KC], bc[KC];
+#pragma unroll
+        for (int kk = 0; kk < KC; kk++) bn[kk] = bp[64 * kk];
+        for (int g0 = 0; g0 < kg; g0 += KC) {
+#pragma unroll
+            for (int kk = 0; kk < KC; kk++) bc[kk] = bn[kk];
+            if (g0 + KC < kg) {
+#pragma unroll
+                for (int kk = 0; kk < KC; kk++) bn[kk] = bp[(size_t)64 * (g0 + KC + kk)];
+            }
+#pragma unroll
+            for (int kk = 0; kk < KC; kk++) {
+                const int sl = 4 * (g0 + kk) + (lane >> 4);
+                const int il = sl < rowp ? hadi_slot_to_i(L, sl) : -1;
+                const bool ok = ja < nrows && il >= 0 && il <= L.m1;
+                double av = 0.0;
+                if (ok) av = ap[sl];
+                hadi_mfma_f64_16x16x4(av, bc[kk], acc);
+            }
+        }
+        const int so = 16 * sb + (lane & 15), io = so < rowp ? hadi_slot_to_i(L, so) : -1;
+        const bool so_ok = io >= 0 && io <= L.m1;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int j = 16 * rb + 4 * r + (lane >> 4);
+            if (so_ok && j < nrows) {
+                const size_t off = (size_t)j * rowp + so;
+                Ul[off] = Yl[off] + a * acc[r];
+            }
+        }
+    }
+}
+
+// The time loop of hadi_small_kernel and, with JUMP, of hadi_small_jump_kernel (one more stage between the column pass and the
+// snapshot; European sweeps only).
+template <int B, int W, bool AMER, bool JUMP>
+HADI_DEV HADI_FORCEINLINE void hadi_small_body(const HadiSweepArgs &a, const HadiSmallArgs &sm) {
+    static_assert(!(AMER && JUMP), "the jump stage belongs to European sweeps");
     HADI_DYN_SMEM(double, smem);
     constexpr int G = 1, NT = 64 * W;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -158,6 +226,8 @@ __global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, Had
     const int snap_off = sm.n_snap > 0 ? sm.snap_node[inst] : -1;
     HADI_STAMP_DECL(c.stamp_acc_)
     const double *__restrict__ vs = sm.vec_s ? sm.vec_s + (size_t)inst * (m1 + 1) : nullptr;
+    [[maybe_unused]] const double jmp_a = (JUMP && sm.jmp_a) ? sm.jmp_a[inst] : 0.0;
+    [[maybe_unused]] const double *__restrict__ jmp_Gm = (JUMP && sm.jmp_a) ? sm.jmp_G + (size_t)sm.jmp_mat[inst] * sm.jmp_stride : nullptr;
     for (int n = 1; n <= N; n++) {
         // ---- discrete dividend at the start of the step (device_solver.hpp:448-504) ---------------
         const int dv = sm.div_flag ? sm.div_flag[(size_t)inst * sm.flag_stride + n - 1] : -1;
@@ -250,6 +320,19 @@ __global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, Had
             }
         }
         __syncthreads();
+        if constexpr (JUMP) {  // Bates: the jump sub-step behind the column pass (block-uniform; n <= N_k inside this loop)
+            if (jmp_a != 0.0) {
+                // Y is dead behind the column pass: it takes the copy of U.  Only slots that hold a node are copied (the others are
+                // never read here), so Y's pad slots stay what a sweep without jumps has there.
+                for (int e = tid; e < nrows * rowp; e += NT) {
+                    const int i = hadi_slot_to_i(a.L, e % rowp);
+                    if (i >= 0 && i <= m1) Yl[e] = Ul[e];
+                }
+                __syncthreads();
+                hadi_small_jump_stage<W>(a.L, Yl, Ul, jmp_Gm, jmp_a, wave, lane);
+                __syncthreads();
+            }
+        }
         if constexpr (!AMER) {  // Bermudan exercise at the end of the step (European sweeps only; block-uniform)
             if (hadi_ex_listed(sm.ex_flag, sm.ex_stride, inst, n)) {
                 hadi_exercise_lds<B>(Ul, rowp, false, a.U0 + (size_t)inst * a.L.inst_stride, nrows, m1, rowp, tid, NT);
@@ -283,6 +366,18 @@ __global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, Had
         double *__restrict__ Lg = a.LAM + (size_t)inst * a.L.inst_stride;
         for (int e = tid; e < nrows * rowp; e += NT) Lg[e] = LAMl[e];
     }
+}
+
+template <int B, int W, bool AMER>
+__global__ void __launch_bounds__(64 * W) hadi_small_kernel(HadiSweepArgs a, HadiSmallArgs sm) {
+    hadi_small_body<B, W, AMER, false>(a, sm);
+}
+
+// hadi_small_kernel<B, W, false> with the jump sub-step of a Bates call inside the time loop: a sampled Bates ladder is one launch.
+// Its own symbol outside the table of hadi_dispatch.h (hadi_small_jump_fn), as hadi_small_sch_kernel is.
+template <int B, int W>
+__global__ void __launch_bounds__(64 * W) hadi_small_jump_kernel(HadiSweepArgs a, HadiSmallArgs sm) {
+    hadi_small_body<B, W, false, true>(a, sm);
 }
 
 // ------------------------------------------------------------------------------------------------

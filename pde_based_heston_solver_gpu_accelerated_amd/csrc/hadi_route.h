@@ -34,6 +34,7 @@ struct HadiHandleTuning {
     int debug_fault = 0;       // test hook: HADI_DEBUG_* bits handed to the sweep kernels
     int device_vgrid = 1;      // compute_base_prices / compute_jacobian: v-grids rebuilt per instance on the device
     int jump_share = 1;        // eight-column Bates Jacobian, per-instance matrices: the groups 0 .. 6 of a source instance ride on one staged strip of G
+    int jump_small = -1;       // sampled Bates ladder on the whole-loop LDS kernel (hadi_small_jump_kernel): -1 automatic, 0 never, 1 wherever admitted
     HadiTuning tune;           // kernel-selection overrides and the constants of the plan's cost model (hadi_plan.h)
 };
 
@@ -53,7 +54,7 @@ static inline const HadiTuneKey *hadi_tuning_key(const char *key) {
         {"cs_strips", &H::cs_strips, nullptr, HADI_TN_CS_STRIPS}, {"graph_max_melems", &H::graph_max_melems, nullptr, HADI_TN_NONNEG},
         {"tile_interleave", &H::tile_il, nullptr, HADI_TN_BOOL}, {"debug_fault", &H::debug_fault, nullptr, HADI_TN_ANY},
         {"team_launch", &H::team_launch, nullptr, HADI_TN_TRI}, {"resident_sweep", &H::resident_sweep, nullptr, HADI_TN_TRI},
-        {"jump_share", &H::jump_share, nullptr, HADI_TN_BOOL},
+        {"jump_share", &H::jump_share, nullptr, HADI_TN_BOOL}, {"jump_small", &H::jump_small, nullptr, HADI_TN_TRI},
         {"strip", nullptr, &T::strip, HADI_TN_TRI}, {"row_tile", nullptr, &T::row_tile, HADI_TN_NONNEG},
         {"strip_blocks", nullptr, &T::strip_blocks, HADI_TN_NONNEG}, {"pair_strips", nullptr, &T::pair_strips, HADI_TN_TRI},
         {"col_groups", nullptr, &T::col_groups, HADI_TN_NONNEG}, {"small_waves", nullptr, &T::small_waves, HADI_TN_WAVES},
@@ -223,7 +224,8 @@ enum HadiRouteKind {
     HADI_ROUTE_SMALL_SEQ,   // hadi_small_seq_kernel
     HADI_ROUTE_SMALL_SEQ2,  // hadi_small_seq2_kernel
     HADI_ROUTE_TEAM,        // one attempt at the instance-resident launch, then the streaming path if the team protocol failed
-    HADI_ROUTE_STREAMING    // the time loop over the pass kernels (per sub-batch possibly hadi_sweep_resident)
+    HADI_ROUTE_STREAMING,   // the time loop over the pass kernels (per sub-batch possibly hadi_sweep_resident)
+    HADI_ROUTE_SMALL_JUMP   // hadi_small_jump_kernel with small_waves wavefronts per instance: a sampled Bates ladder in one launch
 };
 enum { HADI_ROUTE_OK, HADI_ROUTE_BAD_GRID, HADI_ROUTE_SEQ_UNSUPPORTED, HADI_ROUTE_PLAN_FAILED };
 enum { HADI_TEAM_NOT_RUN, HADI_TEAM_RAN, HADI_TEAM_FELL_BACK };  // what became of a HADI_ROUTE_TEAM (hadi_describe_route)
@@ -239,7 +241,8 @@ struct HadiRoute {
     bool bermudan = false;           // exercise steps: the whole-loop LDS kernels or the streaming kernels with hadi_exercise_kernel
     bool barrier = false;            // monitoring steps: the whole-loop LDS kernels or the streaming kernels with hadi_knockout_kernel
     bool cliquet = false;            // fixing steps: the whole-loop LDS kernels or the streaming kernels with hadi_fixing_gather_kernel + hadi_fixing_kernel
-    bool jumps = false;              // lognormal jumps: the streaming kernels with hadi_jump_kernel behind every step's last column pass
+    bool jumps = false;              // lognormal jumps: the streaming kernels with hadi_jump_kernel behind every step's last column pass,
+                                     // or (a sampled ladder, HADI_ROUTE_SMALL_JUMP) the sub-step inside hadi_small_jump_kernel
     bool read_payoff_shape = false;  // the payoff-shape flags come back to the host: they decide `amp` (filled in by the caller)
     bool pair_tab = false;           // the pairs' coupling table is built
     bool need_u0 = false;            // the packed payoff without a lambda_bar array (a Bermudan call)
@@ -275,8 +278,8 @@ static inline HadiRoute hadi_route(const HadiRouteIn &in) {
     // A cliquet call (strike fixings at the end of its fixing steps) likewise: hadi_fixing_gather_kernel and hadi_fixing_kernel
     // between two steps of the streaming loop, or the event inside the whole-loop LDS kernels.
     const bool cliquet = r.cliquet = in.n_fix_steps > 0 && !in.debug;
-    // A jump call (Bates) takes the streaming path only: the dense sub-step sits between two steps of the streaming loop
-    // (hadi_jump_kernel); it is not built into the whole-loop LDS kernels, the resident sweep or the team launch.
+    // A jump call (Bates) WITHOUT samples takes the streaming path only: the dense sub-step sits between two steps of the streaming
+    // loop (hadi_jump_kernel); it is not built into the whole-loop LDS kernels of the table, the resident sweep or the team launch.
     const bool jumps = r.jumps = in.jumps && !in.debug;
     r.have_div = r.dividend && in.dividends && !in.debug;  // (diagnostics take p->U as the state the pass starts from)
     // (a caller who pins the streaming kernels' geometry -- hadi_set_tuning "strip", "row_tile", "col_groups", "strip_blocks" --
@@ -316,7 +319,18 @@ static inline HadiRoute hadi_route(const HadiRouteIn &in) {
     r.read_payoff_shape = american && t.use_amp && !cs && !takes_small_path && !in.debug && !seq_shape && !ladder;
     r.need_lam_u0 = american;
     r.need_u0 = (bermudan || (cliquet && in.fix_weights)) && !american;
-    r.need_ut = r.dividend || jumps;  // (the sub-step works out of place: it reads the copy of U it finds there)
+    // A jump call WITH samples (a Bates surface: 1 or 9 instances per source on a calibration grid for ~100 steps) may take
+    // hadi_small_jump_kernel, the block kernel of the small path with the sub-step inside its time loop: Douglas steps, fp64 state,
+    // European or dividend sweeps, no profiling, no diagnostics, a grid the block kernel admits; never the one-wavefront
+    // sequential kernels, whatever n; not when the caller pinned the streaming geometry or switched "small_grid" off.
+    // "jump_small" = 1: wherever admitted; 0: never; -1 (default): batches of at least one instance per CU.  Measured
+    // (profiles/bates_surface_ab.txt, 100 steps, ms per call, streaming -> this kernel): one 50x25 instance 1.68 -> 1.94 and nine
+    // 1.74 -> 1.95, one 100x20 instance 1.98 -> 3.63 -- the replayed graph of the streaming loop is AHEAD for the surface driver's own
+    // batches, which therefore stream --; x256 3.6 -> 2.0, x1024 8.9 -> 6.0, x2048 15.9 -> 10.0 at 50x25 and x256 5.7 -> 4.4 at 100x20:
+    // from one instance per CU on the one launch is ahead at every measured size, beyond the spread of the rounds.
+    const bool small_jump = jumps && ladder && in.n_samp > 0 && !cs && !f32 && !american && !in.profiling && t.use_small && !pinned &&
+                            pl.smem_small_eu > 0 && (t.jump_small > 0 || (t.jump_small < 0 && in.n >= cu));
+    r.need_ut = r.dividend || (jumps && !small_jump);  // (the streaming sub-step works out of place: it reads the copy of U it finds there)
     r.need_f32 = f32;
     r.need_v_r1_c2 = cs && !small_sch;  // (hadi_small_sch_kernel keeps V, R1, C2 in LDS)
     r.need_r1 = pl.row_seq != 0;        // (hadi_pass_a_seq parks the Thomas multipliers there)
@@ -340,7 +354,7 @@ static inline HadiRoute hadi_route(const HadiRouteIn &in) {
     // recorded by the kernel, checked by the caller, and the batch is solved again on the streaming path.
     const bool team = hadi_team_grid(pl, in.n, in.theta, in.rates_equal) && (in.variant == HADI_EU || in.variant == HADI_DIV) && !cs && !f32 &&
                       !in.debug && !prof && cu == 256 && !ladder && !bermudan && !barrier && !cliquet && !jumps && (t.team_launch > 0 || (t.team_launch < 0 && !in.team_failed && !pinned));
-    r.kind = small_sch ? HADI_ROUTE_SMALL_SCH : takes_small_path ? (seq2 ? HADI_ROUTE_SMALL_SEQ2 : seq ? HADI_ROUTE_SMALL_SEQ : HADI_ROUTE_SMALL) :
+    r.kind = small_jump ? HADI_ROUTE_SMALL_JUMP : small_sch ? HADI_ROUTE_SMALL_SCH : takes_small_path ? (seq2 ? HADI_ROUTE_SMALL_SEQ2 : seq ? HADI_ROUTE_SMALL_SEQ : HADI_ROUTE_SMALL) :
              team ? HADI_ROUTE_TEAM : HADI_ROUTE_STREAMING;
     return r;
 }
@@ -372,6 +386,11 @@ static inline std::string hadi_describe_route(const HadiRoute &r, const HadiRout
         snprintf(buf, sizeof buf, "hadi_small_sch_kernel<%d,%s>: whole time loop in one launch, one wavefront per instance, predictor and corrector lines solved sequentially in LDS (%zu B)",
                  L.B, sch == HADI_SCH_MCS ? "MCS" : sch == HADI_SCH_HV ? "HV" : "CS", hadi_small_sch_smem(L));
         return buf + ladder_loop + ex_loop + ko_loop + fix_loop;
+    }
+    if (r.kind == HADI_ROUTE_SMALL_JUMP) {
+        snprintf(buf, sizeof buf, "hadi_small_jump_kernel<%d,%d>: whole time loop in one launch, instance resident in LDS (%zu B)", L.B == 1 ? 1 : 2,
+                 r.small_waves == 8 ? 8 : 4, r.pl.smem_small_eu);
+        return buf + ladder_loop + "; Bates: jump sub-step on the fp64 matrix core inside the time loop";
     }
     if (r.kind == HADI_ROUTE_SMALL_SEQ2 || r.kind == HADI_ROUTE_SMALL_SEQ || r.kind == HADI_ROUTE_SMALL) {
         const HadiSel sel = hadi_route_small_sel(r, in.n);

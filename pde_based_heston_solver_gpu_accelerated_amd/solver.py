@@ -107,7 +107,7 @@ class HestonADI:
 
     def set_tuning(self, key, value):
         """Execution-path switch (hadi.h: 'small_grid', 'small_seq', 'small_sch', 'graph', 'american_p', 'strip', 'row_tile', 'col_groups',
-        'small_waves', 'device_vgrid'); results agree to round-off."""
+        'small_waves', 'device_vgrid', 'jump_share', 'jump_small'); results agree to round-off."""
         self._call(self._lib.hadi_set_tuning, key.encode(), int(value))
 
     def get_tuning(self, key):
@@ -732,6 +732,66 @@ class HestonADI:
         self._call(self._lib.hadi_compute_jacobian_bates_jumps, C.byref(p), float(S_0), float(V_0), float(eps), C.byref(j), jptr, bptr)
         del keep
         return J, base
+
+    # ---- a Bates surface from one sweep: the sample calls with the jump sub-step (hadi_bates_sample_ladder and its launchers) ------
+    def bates_sample_ladder(self, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U, spots, V_0, snap_steps,
+                            jump_intensity, jump_mean, jump_vol, shared_grid=False, scales=None, variant=EU, U_0=None,
+                            dividends=None, per_instance=None, scheme=0, option_type=CALL, strikes=None):
+        """sample_ladder under the Bates model: the jump sub-step of bates_timestepping at the end of every step, behind the step's
+        last column pass and in front of the snapshot.  Returns [n][len(snap_steps)][n_samp]; snapshot q is what the call with
+        N = snap_steps[q] returns.  Jumps are multiplicative, so the problem stays homogeneous in (s, K): strike_samples turns one
+        sweep into every strike (only proportional dividends keep that).  Admitted and refused as sample_ladder and
+        bates_timestepping both are.  Zero intensities: sample_ladder, bit for bit."""
+        p = self._problem(variant, m1, m2, N, delta_t, theta, r_d, r_f, rho, sigma, kappa, eta, grids, U=U, U_0=U_0,
+                          dividends=dividends, per_instance=per_instance, scheme=scheme, option_type=option_type,
+                          strikes=strikes)
+        n = grids.Vec_s.shape[0]
+        steps = self._snap(snap_steps)
+        st, keep, n_samp = self._samples(n, spots, scales)
+        j, keepj = self._jumps(n, jump_intensity, jump_mean, jump_vol, shared_grid)
+        out, optr = self._out(n, steps.size * n_samp, U)
+        self._call(self._lib.hadi_bates_sample_ladder, C.byref(p), float(V_0), C.byref(st), int(steps.size),
+                   steps.ctypes.data_as(_ip), C.byref(j), optr)
+        del keep, keepj
+        return out.reshape(n, steps.size, n_samp)
+
+    def compute_base_prices_bates_samples(self, spots, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                          num_strikes, deviceGrids, workspace, snap_steps, jump_intensity, jump_mean, jump_vol,
+                                          shared_grid=False, scales=None, variant=EU, U_0=None, dividends=None, per_instance=None,
+                                          scheme=0):
+        """compute_base_prices_samples under the Bates model (the v-grid rebuilt for V_0 or per_instance['V_0_i']):
+        [n][len(snap_steps)][n_samp].  workspace.U is the initial condition and is not modified."""
+        p = self._base_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, num_strikes,
+                               deviceGrids, workspace, U_0, dividends, per_instance, scheme)
+        steps = self._snap(snap_steps)
+        st, keep, n_samp = self._samples(num_strikes, spots, scales)
+        j, keepj = self._jumps(num_strikes, jump_intensity, jump_mean, jump_vol, shared_grid)
+        out, optr = self._out(num_strikes, steps.size * n_samp, workspace.U)
+        self._call(self._lib.hadi_compute_base_prices_bates_samples, C.byref(p), float(V_0), C.byref(st), int(steps.size),
+                   steps.ctypes.data_as(_ip), C.byref(j), optr)
+        del keep, keepj
+        return out.reshape(num_strikes, steps.size, n_samp)
+
+    def compute_jacobian_bates_samples(self, spots, V_0, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t,
+                                       num_strikes, deviceGrids, U_0, snap_steps, jump_intensity, jump_mean, jump_vol,
+                                       shared_grid=False, jump_columns=False, scales=None, eps=1e-6, variant=EU, dividends=None,
+                                       per_instance=None, scheme=0):
+        """compute_jacobian_samples under the Bates model: (J [n][len(snap_steps)][n_samp][n_par], base [n][len(snap_steps)][n_samp])
+        from ONE sweep.  jump_columns False: n_par = 5, the six groups of compute_jacobian_bates (the jump law held fixed); True:
+        n_par = 8, the nine groups and three matrix sets of compute_jacobian_bates_jumps (columns kappa, eta, sigma, rho, V_0,
+        jump_intensity, jump_mean, jump_vol; (jump_intensity + eps) delta_t must not exceed 1)."""
+        p = self._jacobian_problem(variant, r_d, r_f, rho, sigma, kappa, eta, m1, m2, total_size, N, theta, delta_t, deviceGrids,
+                                   U_0, dividends, per_instance, scheme)
+        steps = self._snap(snap_steps)
+        st, keep, n_samp = self._samples(num_strikes, spots, scales)
+        j, keepj = self._jumps(num_strikes, jump_intensity, jump_mean, jump_vol, shared_grid)
+        n_par = 8 if jump_columns else 5
+        J, jptr = self._out(num_strikes * steps.size * n_samp, n_par, U_0)
+        base, bptr = self._out(num_strikes, steps.size * n_samp, U_0)
+        self._call(self._lib.hadi_compute_jacobian_bates_samples, C.byref(p), float(V_0), float(eps), C.byref(st), int(steps.size),
+                   steps.ctypes.data_as(_ip), C.byref(j), n_par, jptr, bptr)
+        del keep, keepj
+        return J.reshape(num_strikes, steps.size, n_samp, n_par), base.reshape(num_strikes, steps.size, n_samp)
 
     def debug_jump_matrix(self, vec_s, jump_mean, jump_vol):
         """The generator G [m1+1][m1+1] of the jump term on the grid vec_s, natural order, as the sweep's kernel builds it."""
