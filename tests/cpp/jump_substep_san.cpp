@@ -4,8 +4,9 @@
 // product and its staging compute -- operand order, K padding, tiles of U, the lists of hadi_jump_sel_kernel -- is checked against
 // the bounds of plain std::vector buffers sized exactly as the library sizes its own.  Each launch is also held to the isolation
 // rule in long double (jump_cases.substep_ratio), so a run that stays inside its buffers but multiplies wrongly fails as well.
+// Likewise hadi_small_jump_stage<W>, the sub-step of the whole-loop kernel, on every shape of tests/bates_domain_cases.py (run_stage).
 #define EMU_JUMP_SUBSTEP_ALONE 1
-#include "../emu/emu_jump_substep.cpp"
+#include "../emu/emu_small_jump_stage.cpp"  // (includes emu_jump_substep.cpp whole)
 
 #include <cinttypes>
 
@@ -85,8 +86,46 @@ static int run_case(const Case &c) {
     return fails ? 1 : 0;
 }
 
+// hadi_small_jump_stage<W> alone (tests/emu/emu_small_jump_stage.cpp) on an image sized exactly as the block kernel's LDS allocation:
+// a read or write of the stage past it is past a std::vector.  Nothing but U's nodes may change, and U's rows must be hadi_jump_step's
+// bits on the same rows (whose product the cases above hold to the isolation rule).
+static int run_stage(int m1, int m2, int W) {
+    long long o8[8];
+    const long long size = emu_small_jump_stage_layout(m1, m2, o8);
+    if (size <= 0) { std::printf("FAIL no block-kernel layout for %dx%d\n", m1, m2); return 1; }
+    const int m1p = m1 + 1, nrows = m2 + 1, rowp = (int)o8[1];
+    std::vector<double> s(m1p), field((size_t)m1p * nrows), in((size_t)size), out((size_t)size), r0((size_t)nrows * rowp), r1((size_t)nrows * rowp),
+        G((size_t)m1p * m1p);
+    std::vector<unsigned char> kind((size_t)size);
+    make_grid(m1, 0, s.data());
+    for (int j = 0; j < nrows; j++)
+        for (int i = 0; i < m1p; i++) field[(size_t)j * m1p + i] = (0.5 + uniform01()) * (1.0 + s[i]);
+    const double a = (W == 4) ? 1.0 : 0.37;
+    const int rc = emu_small_jump_stage(W, m1, m2, s.data(), LAWS[(m1 + W) % 3][0], LAWS[(m1 + W) % 3][1], field.data(), a, -12345.0, std::nan(""),
+                                        in.data(), out.data(), kind.data(), r0.data(), r1.data(), G.data());
+    if (rc) { std::printf("FAIL stage rc %d\n", rc); return 1; }
+    int fails = 0, moved = 0;
+    for (size_t e = 0; e < (size_t)size; e++) {
+        if (kind[e] != 0 && std::memcmp(&in[e], &out[e], 8)) fails++;
+        if (kind[e] == 0 && std::memcmp(&in[e], &out[e], 8)) moved++;
+    }
+    if (std::memcmp(out.data() + o8[4], r1.data(), sizeof(double) * nrows * rowp)) fails++;
+    if (moved != nrows * m1) fails++;  // (every node but column i = 0)
+    std::printf("stage %4dx%-3d W %d: %d nodes rewritten%s\n", m1, m2, W, moved, fails ? "  FAIL" : "");
+    return fails ? 1 : 0;
+}
+
 int main() {
     int fails = 0;
+    {   // the shapes of tests/bates_domain_cases.py; the largest m2 at 128 by the plan's own admission, walked up from 128x20
+        const int rows[][2] = {{16, 11}, {63, 24}, {64, 31}, {64, 32}, {127, 16}, {128, 20}, {50, 32}, {100, 12}};
+        int top = 20;
+        while (emu_small_jump_stage_layout(128, top + 1, nullptr) > 0) top++;
+        for (int W : {4, 8}) {
+            for (auto &r : rows) fails += run_stage(r[0], r[1], W);
+            fails += run_stage(128, top, W);
+        }
+    }
     for (int m1 : M1_EDGES) {
         const int big = m1 >= 512;
         fails += run_case(Case{0, m1, big ? 3 : 12, big ? 1 : 2, big ? 1 : 2, 0, big ? 1 : 2, 1, 0, 0, 0});

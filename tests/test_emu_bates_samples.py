@@ -4,7 +4,9 @@ block kernel of the small path with the jump sub-step between the column pass an
 
 Bound, the sample calls' (tests/test_emu_samples.py): every sample within 1e-10 sum|w| |scale| max|U_ref| on well-conditioned grids
 (asserted).  Shapes of the whole-loop kernel: 50x25 (B = 1, two row blocks of 16 and 10 rows, the last slot block holds the i = 0 slot
-and pads), 100x12 (B = 2, 13 rows: one row block), 50x32 (33 rows: a last row block of one row), W = 4 and 8.  Invariants: an
+and pads), 100x12 (B = 2, 13 rows: one row block), 50x32 (33 rows: a last row block of one row), W = 4 and 8; and every row of
+tests/bates_domain_cases.py (the whole-loop shapes of event_cases.LDS_ROWS and 128 x the largest m2 the route function admits, found
+with it and never written down) at both widths with N = 3.  Invariants: an
 instance with a_k = 0 is its plain run bit for bit; no pad slot of the packed state differs from the same run without jumps; a
 shared matrix gives the per-instance matrices' bits; the nine groups pick their three matrix sets.  (A ladder shares the step
 indices -- N_i is refused --, so no instance finishes before another inside such a call.)  The route function: jumps without
@@ -18,6 +20,7 @@ import pytest
 
 from oracle import oracle as O
 
+import bates_domain_cases as BD
 import bates_samples_ref as BS
 import common as Cm
 import samples_ref as SR
@@ -144,13 +147,39 @@ WHOLE = [("50x25-W8-call", 8, 50, 25, 6, SNAPS, dict()),
          ("100x12-W4-DIV-call", 4, 100, 12, 4, [1, 3, 4], dict(div=True)),
          ("100x12-W8-put", 8, 100, 12, 4, [2, 4], dict(put=True)),
          ("50x32-W8-call", 8, 50, 32, 3, [1, 3], dict())]
+# ... and every row of bates_domain_cases' table at both widths (m2 None: the largest m2 the route admits at 128, found below)
+WHOLE += [("%dx%d-W%d" % (r.m1, r.m2, W), W, r.m1, r.m2, 3, [1, 3], dict()) for r in BD.FIXED for W in BD.WIDTHS
+          if ("%dx%d-W%d-call" % (r.m1, r.m2, W)) not in [w[0] for w in WHOLE]]
+WHOLE += [("%dxlargest-W%d" % (BD.LARGEST_M1, W), W, BD.LARGEST_M1, None, 3, [1, 3], dict()) for W in BD.WIDTHS]
+
+
+def takes_the_loop(emu, m1, m2, must=None):
+    """The emulator's route function with "jump_small" = 1: does a sampled Bates ladder take hadi_small_jump_kernel<2,..> there?"""
+    o, d = route(emu, 3, m1, m2, True, n_snap=2, n_samp=10, tuning="jump_small=1")
+    loop = d.startswith("hadi_small_jump_kernel<2,")
+    assert loop == (o[1] == SMALL_JUMP) and (loop or (o[1] == STREAMING and d.endswith(JUMP_WORDS) and "row pass" in d)), d
+    return loop
+
+
+def largest_m2(emu):
+    m2 = BD.largest_m2(lambda m1, m2: takes_the_loop(emu, m1, m2))
+    assert not takes_the_loop(emu, BD.LARGEST_M1, m2 + 1)  # (streams: the words are asserted in takes_the_loop)
+    return m2
 
 
 @pytest.mark.parametrize("name,how,m1,m2,N,snaps,kw", WHOLE, ids=[w[0] for w in WHOLE])
 def test_whole_loop_kernel(emu, name, how, m1, m2, N, snaps, kw):
+    if m2 is None:
+        m2 = largest_m2(emu)
+        row = BD.shapes(m2)[-1]
+        name = "%dx%d-W%d" % (m1, m2, how)
+    else:
+        row = next((r for r in BD.FIXED if (r.m1, r.m2) == (m1, m2)), None)
+    if row is not None:
+        print(BD.what(row))
     o4 = (C.c_longlong * 4)()
-    assert emu.emu_bates_samples_layout(m1, m2, 3, o4) == 0 and o4[3] > 0
-    assert (o4[0], o4[2]) == {50: (1, m2 + 1), 100: (2, m2 + 1)}[m1]
+    assert emu.emu_bates_samples_layout(m1, m2, 3, o4) == 0 and 0 < o4[3] <= 76 * 1024
+    assert (o4[0], o4[1], o4[2]) == (BD.geometry(m1, m2)[0], BD.geometry(m1, m2)[1], m2 + 1)
     check(emu, name, how, m1, m2, 3, N, laws(3), snaps=snaps, **kw)
 
 
